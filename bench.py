@@ -13,7 +13,12 @@ Strong scaling (the default for N > 1): ONE global corpus of --s
 takes [r*N/W, (r+1)*N/W) -- and `value` = the corpus bytes / max-over-ranks time.
 --scaling weak gives every rank its own --strings strings instead (labelled "weak").
 
-Launch: python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, config).
+--full adds everything else, after the timed steps or before the GPU is touched: the CPU baselines, the
+exact-match check against the C oracle, the pass timing and roofline, the reduced histogram's record,
+the padded-layout run.  --dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.
+
+Launch: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N = 1 runs in this process.  N > 1 without WORLD_SIZE in the environment: this process starts
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
   bench.py <the same arguments>` as a CHILD (before anything here touches the GPU; never an exec)
@@ -81,7 +86,20 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (RCCL, the real path) or gloo -- gloo lets a rehearsal put several ranks "
                          "on one GPU (device = local_rank mod visible GPUs)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baselines, the exact-match check against the "
+                         "C oracle, the contexts' and the arena checks, the pass timing and roofline, the reduced "
+                         "histogram's record and the padded-layout run (--no-cpu-baseline, --exact-sample, --cpu-sample "
+                         "and --cpu-budget apply to these).  Without it: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all): id_offsets, status, histogram, and the ids of a fixed seeded "
+                         "sample of strings (ids_sample, one row per string of sample_strings, padded with -1); "
+                         "N > 1: <name>_rank<r>.npy per rank")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def log(msg: str) -> None:
@@ -259,6 +277,47 @@ def algorithmic_bytes(n_bytes: int, n_str: int, n_tok: int, id_bytes: int = 4) -
     return n_bytes + id_bytes * n_tok + 8 * (n_str + 1) + 8 * (n_str + 1) + 4 * n_str
 
 
+DUMP_IDS_BYTES = 1 << 25       # --dump-outputs: the ids sample's share of the 64 MB (float32, padded rows)
+DUMP_FULL_MAX_STRINGS = 2_000_000   # ... id_offsets (float64) + status (float32) whole up to here: 12 bytes a string
+
+
+def dump_sample(offs: np.ndarray, n_str: int, seed: int, world: int = 1) -> tuple:
+    """--dump-outputs: (sorted string indices of the ids sample, its row width).  Fixed by the inputs
+    alone -- the corpus' offsets and --seed -- so two builds sample the same strings; a string has at
+    most one id per byte, so the longest string's bytes bound a row.  The ranks share the 64 MB."""
+    width = max(1, int(np.diff(offs).max())) if n_str else 1
+    k = min(n_str, 1 << 18, max(1, DUMP_IDS_BYTES // (4 * width * world)))
+    pick = np.random.default_rng(seed).choice(n_str, size=k, replace=False) if k < n_str else np.arange(n_str)
+    return np.sort(pick).astype(np.int64), width
+
+
+def dump_outputs(path: str, suffix: str, d_ids, d_idoff, d_status, d_hist, offs: np.ndarray, n_str: int, seed: int,
+                 world: int = 1):
+    """Writes the last timed step's outputs (device tensors: CSR ids, id offsets, status, histogram) as
+    .npy files under `path`; returns {name: shape}.  ids fit float32 exactly (< 2^24), offsets need float64."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    pick, width = dump_sample(offs, n_str, seed, world)
+    off_h = d_idoff.cpu().numpy().astype(np.int64)
+    starts, counts = off_h[pick], np.minimum(off_h[pick + 1] - off_h[pick], width)
+    cols = np.arange(width, dtype=np.int64)[None, :]
+    valid = cols < counts[:, None]
+    pos = np.where(valid, starts[:, None] + cols, 0)
+    rows = d_ids[torch.from_numpy(pos).to(d_ids.device)].cpu().numpy().astype(np.float32)
+    rows[~valid] = -1.0
+    arrays = {"histogram": d_hist.cpu().numpy().astype(np.float64), "sample_strings": pick.astype(np.float64),
+              "ids_sample": rows}
+    if n_str * world <= DUMP_FULL_MAX_STRINGS:
+        arrays["id_offsets"] = off_h.astype(np.float64)
+        arrays["status"] = d_status[:n_str].cpu().numpy().astype(np.float32)
+    else:   # the sampled strings' id counts and status
+        arrays["id_counts_sample"] = (off_h[pick + 1] - off_h[pick]).astype(np.float64)
+        arrays["status_sample"] = d_status[:n_str].cpu().numpy()[pick].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def host_path(args):
     """Secondary line: the unchanged callers' shape (main_analyze_s2orc.py:74-78 one dp_tokenize call
     per row, :269-271 a serial loop) and the batched form, from Python str to List[List[int]], host
@@ -425,7 +484,7 @@ def main():
     Lb = int(offs[-1]) // max(M, 1)
     log(f"corpus ready: {M} strings, {int(offs[-1])} bytes")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # before any GPU call: the pool forks plain CPU workers
         args.cpu_sample = min(args.cpu_sample, M)
         sub = offs[: args.cpu_sample + 1]
@@ -542,7 +601,7 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    if inflight == 1:   # the pass timings ride the timed steps' dispatches (dpt_ctx_profile)
+    if args.full and inflight == 1:   # the pass timings ride the timed steps' dispatches (dpt_ctx_profile)
         enc.profile(True)
     torch.cuda.synchronize()
     if world > 1:
@@ -559,6 +618,46 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs:   # the last timed step's context and histogram buffer
+        ids_l, idoff_l, st_l = outs[(n_step[0] - 1) % inflight]
+        dumped = dump_outputs(args.dump_outputs, "" if world == 1 else "_rank%d" % rank, ids_l, idoff_l, st_l,
+                              d_hists[(n_step[0] - 1) % len(d_hists)], offs, M, args.seed, world)
+        log("outputs written to %s: %s" % (args.dump_outputs, dumped))
+    bytes_all = all_sum(float(n_bytes))
+    raw_all = all_sum(float(raw_text_bytes))
+    strings_all = int(all_sum(float(M)))
+    value = bytes_all * args.steps / dt
+    head = {
+        "metric": "input bytes/sec/GPU + exact-match rate vs CPU DP, 256-byte strings"
+                  if args.workload == "cfg2" else "input bytes/sec/GPU + exact-match rate vs CPU DP (%s)" % args.workload,
+        "value": value,
+        "unit": "bytes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": data,
+        "config": {"workload": wl, "strings_total": strings_all,
+                   "strings_per_gpu": M, "bytes_per_string": Lb,
+                   "vocab": ("synthetic byte-level BPE 250680" if bloom else
+                             "synthetic toy 1000" if args.workload == "cfg1" else "synthetic llama-shaped 32000"),
+                   "parallelism": f"dp{world} ({scaling} scaling: corpus shards, 1 all-reduce of the histogram per step)"},
+        "per_gpu_bytes_per_s": value / world,
+        **({"raw_text_bytes_per_s": raw_all * args.steps / dt, "raw_text_bytes": int(raw_all)} if presplit else {}),
+        "batches_in_flight": inflight,   # N > 1: step k on context + stream k % N (small shards; see --inflight)
+        **({"dumped_outputs": dumped} if dumped is not None else {}),
+    }
+    if not args.full:   # the plain run ends here: the exact-match rate and the rest are --full's
+        if rank == 0:
+            print(json.dumps(dict(head, exact_match=None, full=False)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # With batches in flight the passes of consecutive steps overlap, so a call's own pass times mean
     # little and their events cost the timed steps ~1 %: the roofline's pass timing then comes from a
     # separate one-stream run of prof_steps steps after the timed region (the same calls, one context).
@@ -614,9 +713,6 @@ def main():
     n_tok_rank = int(d_idoff[-1].item())
     n_tok_all = int(hist[N_BINS])          # after the all-reduce: all ranks' ids
     ok_strings = int(hist[N_BINS + 2])
-    bytes_all = all_sum(float(n_bytes))
-    raw_all = all_sum(float(raw_text_bytes))
-    strings_all = int(all_sum(float(M)))
 
     # roofline of the dominant kernel (tokenize), SURVEY.md §8d bytes per launch (ids at 4 bytes)
     k_ms = ms_stage[0] / max(launches, 1)
@@ -649,36 +745,16 @@ def main():
         cpu["c_restatement_threads"] = cores
 
     if rank == 0:
-        value = bytes_all * args.steps / dt
         line = {
-            "metric": "input bytes/sec/GPU + exact-match rate vs CPU DP, 256-byte strings"
-                      if args.workload == "cfg2" else "input bytes/sec/GPU + exact-match rate vs CPU DP (%s)" % args.workload,
-            "value": value,
-            "unit": "bytes/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": data,
-            "config": {"workload": wl, "strings_total": strings_all,
-                       "strings_per_gpu": M, "bytes_per_string": Lb,
-                       "vocab": ("synthetic byte-level BPE 250680" if bloom else
-                                 "synthetic toy 1000" if args.workload == "cfg1" else "synthetic llama-shaped 32000"),
-                       "parallelism": f"dp{world} ({scaling} scaling: corpus shards, 1 all-reduce of the histogram per step)"},
-            "per_gpu_bytes_per_s": value / world,
+            **head,
+            "full": True,
             "tokens_per_byte": n_tok_all / max(bytes_all, 1.0),
-            **({"raw_text_bytes_per_s": raw_all * args.steps / dt, "raw_text_bytes": int(raw_all)} if presplit else {}),
             "ok_strings": ok_strings,
             # the reduced histogram itself (tests/test_gpu_sharded.py compares ranks x shards runs)
             "histogram": {"n_bins": N_BINS, "sha256": hashlib.sha256(hist.astype("<i8").tobytes()).hexdigest(),
                           "total_ids": n_tok_all, "total_strings": int(hist[N_BINS + 1]),
                           "status": [int(x) for x in hist[N_BINS + 2:N_BINS + 7]]},
             "exact_match": exact,
-            "batches_in_flight": inflight,   # N > 1: step k on context + stream k % N (small shards; see --inflight)
             "stage_ms_per_step": {"tokenize": ms_stage[0] / max(launches, 1)},   # finish (offsets + CSR ids): rocprof
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,

@@ -135,3 +135,50 @@ def test_bench_refuses_world_size_mismatch_in_a_child():
                          env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode == 2, out.stderr[-2000:]
     assert "WORLD_SIZE" in out.stderr and out.stdout.strip() == ""
+
+
+def test_dump_outputs_sample_and_files(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors: the sample depends on the inputs alone (offsets and seed), every file
+    is float32 / float64, each sampled string's row holds its ids padded with -1, and offsets / status /
+    histogram come back whole."""
+    import torch
+    rng = np.random.default_rng(5)
+    n = 1000
+    cnt = rng.integers(0, 9, size=n)
+    id_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    in_off = np.concatenate([[0], np.cumsum(np.maximum(cnt, 1) + rng.integers(0, 3, size=n))]).astype(np.uint64)
+    ids = torch.from_numpy(rng.integers(0, 32000, size=int(id_off[-1]) + 7).astype(np.int32))
+    st = torch.from_numpy(rng.integers(0, 4, size=n).astype(np.int32))
+    hist = torch.arange(bench.N_BINS + 8, dtype=torch.int64)
+    width = int(np.diff(in_off).max())
+    monkeypatch.setattr(bench, "DUMP_IDS_BYTES", 4 * width * 100)   # 100 of the 1000 strings fit
+    pick, w = bench.dump_sample(in_off, n, 1)
+    assert w == width and len(pick) == 100 and len(set(pick.tolist())) == 100 and (np.diff(pick) > 0).all()
+    assert np.array_equal(pick, bench.dump_sample(in_off, n, 1)[0])
+    assert not np.array_equal(pick, bench.dump_sample(in_off, n, 2)[0])
+    assert np.array_equal(bench.dump_sample(in_off, 50, 1)[0], np.arange(50))   # a small corpus: every string
+    shapes = bench.dump_outputs(str(tmp_path), "", ids, torch.from_numpy(id_off), st, hist, in_off, n, 1)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == set(shapes) == {"histogram", "sample_strings", "ids_sample", "id_offsets", "status"}
+    assert all(a.dtype in (np.float32, np.float64) and list(a.shape) == shapes[k] for k, a in got.items())
+    assert np.array_equal(got["sample_strings"], pick) and got["ids_sample"].shape == (100, width)
+    ids_h = ids.numpy()
+    for row, s in zip(got["ids_sample"], pick):
+        want = ids_h[id_off[s]:id_off[s + 1]]
+        assert np.array_equal(row[:len(want)], want) and (row[len(want):] == -1).all()
+    assert np.array_equal(got["id_offsets"], id_off) and np.array_equal(got["status"], st.numpy())
+    assert np.array_equal(got["histogram"], hist.numpy())
+
+
+def test_plain_and_full_options(monkeypatch):
+    """--full is off by default; --steps sets the timed steps and must be at least 1."""
+    import pytest
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

@@ -39,7 +39,7 @@ def _env(**kw):
     return env
 
 
-ARGS = ["--strings", str(N), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+ARGS = ["--full", "--strings", str(N), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]   # (the checks are --full's)
 
 
 @pytest.fixture(scope="module")

@@ -16,28 +16,28 @@ timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smok
 tail -1 $out/smoke.log
 timeout -k 10 600 python3 tools/pmc_traffic.py 1000000 $tag > $out/traffic.log 2>&1 || { tail -20 $out/traffic.log; exit 1; }
 tail -1 $out/traffic.log | cut -c1-300
-timeout -k 10 400 python -u bench.py > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
 tail -1 $out/bench.log > $out/bench.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 > $out/trace.log 2>&1 || { tail -20 $out/trace.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/trace -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $out/trace.log 2>&1 || { tail -20 $out/trace.log; exit 1; }
 bash tools/pmc.sh $tag > $out/pmc.log 2>&1 || { tail -20 $out/pmc.log; exit 1; }
 cp gpurun_out/pmc_$tag/summary.txt $out/pmc_summary.txt 2>/dev/null
 fi
 [ $part = 1 ] && exit 0
 if [ $part != 2b ]; then
 for wl in cfg1 cfg4 cfg5 bloom cfg2p cfg4p; do
-  timeout -k 10 400 python -u bench.py --workload $wl --steps 10 --warmup 3 > $out/bench_$wl.log 2>&1 || { tail -20 $out/bench_$wl.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --workload $wl --steps 10 --warmup 3 > $out/bench_$wl.log 2>&1 || { tail -20 $out/bench_$wl.log; exit 1; }
   tail -1 $out/bench_$wl.log > $out/bench_$wl.json
 done
 for n in 500000 250000 125000; do
-  timeout -k 10 300 python -u bench.py --strings $n --steps 40 --warmup 5 --no-cpu-baseline > $out/strong_$n.log 2>&1 || { tail -20 $out/strong_$n.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --strings $n --steps 40 --warmup 5 --no-cpu-baseline > $out/strong_$n.log 2>&1 || { tail -20 $out/strong_$n.log; exit 1; }
   grep '^{' $out/strong_$n.log | tail -1 > $out/strong_$n.json
 done
 for n in 500000 250000 125000; do   # the same shards with the per-step RCCL all-reduce the N > 1 runs do (world 1)
-  DPT_BENCH_COLL=1 timeout -k 10 300 python -u bench.py --strings $n --steps 40 --warmup 5 --no-cpu-baseline > $out/strongc_$n.log 2>&1 || { tail -20 $out/strongc_$n.log; exit 1; }
+  DPT_BENCH_COLL=1 timeout -k 10 300 python -u bench.py --full --strings $n --steps 40 --warmup 5 --no-cpu-baseline > $out/strongc_$n.log 2>&1 || { tail -20 $out/strongc_$n.log; exit 1; }
   grep '^{' $out/strongc_$n.log | tail -1 > $out/strong_${n}_rccl.json
 done
 for n in 250000 125000; do   # the same shards with one batch in flight (bench.py --inflight 1)
-  timeout -k 10 300 python -u bench.py --strings $n --steps 40 --warmup 5 --no-cpu-baseline --inflight 1 > $out/strong1_$n.log 2>&1 || { tail -20 $out/strong1_$n.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --strings $n --steps 40 --warmup 5 --no-cpu-baseline --inflight 1 > $out/strong1_$n.log 2>&1 || { tail -20 $out/strong1_$n.log; exit 1; }
   grep '^{' $out/strong1_$n.log | tail -1 > $out/strong_${n}_inflight1.json
 done
 fi

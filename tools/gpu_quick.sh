@@ -16,7 +16,7 @@ for wl in "$@"; do
     cfg2) a="--steps 20 --warmup 3 --no-cpu-baseline" ;;
     *) a="--workload $wl --steps 10 --warmup 3 --no-cpu-baseline" ;;
   esac
-  timeout -k 10 400 python -u bench.py $a > $out/bench_$wl.log 2>&1 || { tail -20 $out/bench_$wl.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full $a > $out/bench_$wl.log 2>&1 || { tail -20 $out/bench_$wl.log; exit 1; }
   tail -1 $out/bench_$wl.log > $out/bench_$wl.json
   python3 -c "import json; d=json.loads(open('$out/bench_$wl.json').read()); print('$wl', '%.2f GB/s' % (d['value']/1e9), 'ms/step %.4f' % d['ms_per_step'], 'exact', d['exact_match']['rate'], d['exact_match']['sample'], 'tok ms %.4f' % d['stage_ms_per_step']['tokenize'])"
 done
