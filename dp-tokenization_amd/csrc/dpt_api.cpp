@@ -27,6 +27,11 @@ struct dpt_vocab {
     int32_t ws_node = -1, ws_base = 0, ws_id = -1;   // the trie node after U+2581 (-1: no such path)
     bool ids16 = false;               // every id in 0..32767: ids are staged as int16 (half the staging traffic)
     uint32_t hash_buckets = 0, hash_probe = 0;   // C2's token hash table (0: none)
+    // dpt_token_spans: byte length per id - id_min (0: no token has this id); null when the ids are too
+    // sparse for a dense table or two tokens of different length share an id (the spans calls: DPT_E_VOCAB)
+    uint16_t *d_tok_len = nullptr;
+    int32_t id_min = 0;
+    uint32_t n_tab = 0;
     dpt_vocab_stats stats{};
 };
 
@@ -302,6 +307,36 @@ std::vector<uint32_t> build_token_hash(const uint8_t *blob, const uint64_t *off,
     return none;
 }
 
+// dpt_token_spans' table: tab[id - id_min] = the byte length of the token with that id, 0 where no token
+// has it -- over the tokens the trie holds (a later duplicate's id replaced the earlier one's there), a
+// token's length being its node's depth.  False (no table) when the id range is too sparse to hold
+// densely or two tokens of different length share an id.
+bool build_tok_len(const dpt::DoubleArray &da, std::vector<uint16_t> &tab, int32_t &id_min) {
+    auto is_tok = [&](uint32_t t) { return da.check[t] != -1 && (da.base[t] & (int32_t)0x80000000) && da.id[t] >= 0; };
+    int32_t lo = INT32_MAX, hi = INT32_MIN;
+    uint64_t n = 0;
+    for (uint32_t t = 1; t < da.n_slots; t++) {
+        if (!is_tok(t)) continue;
+        lo = da.id[t] < lo ? da.id[t] : lo;
+        hi = da.id[t] > hi ? da.id[t] : hi;
+        n++;
+    }
+    if (!n) return false;
+    const uint64_t span = (uint64_t)((int64_t)hi - (int64_t)lo) + 1;
+    if (span > 8 * n + 65536) return false;
+    tab.assign((size_t)span, (uint16_t)0);
+    for (uint32_t t = 1; t < da.n_slots; t++) {
+        if (!is_tok(t)) continue;
+        uint32_t depth = 0;
+        for (int32_t q = (int32_t)t; q > 0; q = da.check[q]) depth++;   // (slot 0 is the root; tokens have at most 65535 bytes)
+        uint16_t &e = tab[(size_t)(da.id[t] - lo)];
+        if (e && e != depth) return false;
+        e = (uint16_t)depth;
+    }
+    id_min = lo;
+    return true;
+}
+
 int kernel_variant(uint32_t max_cp) {
     int v = max_cp <= 16 ? dpt::KERNEL_ROWS16 : dpt::KERNEL_ROWS64;
     if (const char *e = getenv("DPT_KERNEL"))
@@ -422,12 +457,19 @@ int dpt_vocab_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const in
     if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<uint8_t *>(v->d_pair16) + dpt::TOKHASH_OFFSET, th.data(), sizeof(uint32_t) * th.size(), hipMemcpyHostToDevice);
     v->hash_buckets = th[1] ? th[0] + 1 : 0;
     v->hash_probe = th[1];
+    std::vector<uint16_t> tok_len;
+    if (build_tok_len(da, tok_len, v->id_min)) {
+        v->n_tab = (uint32_t)tok_len.size();
+        if (e == hipSuccess) e = hipMalloc((void **)&v->d_tok_len, sizeof(uint16_t) * tok_len.size());
+        if (e == hipSuccess) e = hipMemcpy(v->d_tok_len, tok_len.data(), sizeof(uint16_t) * tok_len.size(), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         dpt::free_double_array(&da);
         if (v->d_slots) (void)hipFree(v->d_slots);
         if (v->d_ids) (void)hipFree(v->d_ids);
         if (v->d_slots4) (void)hipFree(v->d_slots4);
         if (v->d_pair16) (void)hipFree(v->d_pair16);
+        if (v->d_tok_len) (void)hipFree(v->d_tok_len);
         delete v;
         return hip_fail(e, "vocab upload");
     }
@@ -453,7 +495,8 @@ int dpt_vocab_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const in
     v->stats.max_cp = da.max_cp;
     v->stats.hash_max_probe = v->hash_probe;
     v->stats.hash_buckets = v->hash_buckets;
-    v->stats.device_bytes = (uint64_t)da.n_slots * (sizeof(int2) + sizeof(int32_t) + sizeof(int4)) + 65536 * (sizeof(int2) + sizeof(int4)) + (65536 + 256) * sizeof(int16_t) + 65536 * sizeof(uint2);
+    v->stats.device_bytes = (uint64_t)da.n_slots * (sizeof(int2) + sizeof(int32_t) + sizeof(int4)) + 65536 * (sizeof(int2) + sizeof(int4)) + (65536 + 256) * sizeof(int16_t) + 65536 * sizeof(uint2) +
+                            (v->d_tok_len ? (uint64_t)v->n_tab * sizeof(uint16_t) : 0);
     dpt::free_double_array(&da);
     *out = v;
     return DPT_OK;
@@ -466,6 +509,7 @@ int dpt_vocab_destroy(dpt_vocab *v) {
     (void)hipFree(v->d_ids);
     (void)hipFree(v->d_slots4);
     (void)hipFree(v->d_pair16);
+    if (v->d_tok_len) (void)hipFree(v->d_tok_len);
     delete v;
     return DPT_OK;
 }
@@ -951,6 +995,121 @@ int dpt_dp_host_far(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uint8_
     return encode_host_impl(c, v, mode_flags, text, n_bytes, str_off, cut_mask, n_str, dummy_ids, n_bytes ? n_bytes : 1,
                             id_off.data(), status, lengths ? lengths : len_tmp.data(), edges, far ? far : dummy_far,
                             far_cap, n_far);
+}
+
+// Argument checks shared by the two spans entry points (no device is touched, v is not dereferenced
+// before every pointer has been checked).
+static int spans_check(const dpt_vocab *v, int mode, const uint8_t *text, uint64_t n_bytes, const uint64_t *str_off,
+                       const uint8_t *cut_mask, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                       const uint32_t *tok_end, const int32_t *span_status) {
+    if (!v) return fail(DPT_E_ARG, "null vocab");
+    if (!str_off) return fail(DPT_E_ARG, "null str_off");
+    if (!ids) return fail(DPT_E_ARG, "null ids");
+    if (!id_off) return fail(DPT_E_ARG, "null id_off");
+    if (!status) return fail(DPT_E_ARG, "null status");
+    if (!tok_end) return fail(DPT_E_ARG, "null tok_end");
+    if (!span_status) return fail(DPT_E_ARG, "null span_status");
+    if (mode != DPT_MODE_RAW && mode != DPT_MODE_PRESPLIT && mode != DPT_MODE_ATOMS) return fail(DPT_E_ARG, "bad mode");
+    if (mode != DPT_MODE_RAW && !cut_mask) return fail(DPT_E_ARG, "PRESPLIT/ATOMS need cut_mask");
+    if (n_bytes && !text) return fail(DPT_E_ARG, "null text");
+    return DPT_OK;
+}
+
+static dpt::SpansLaunch spans_launch(const dpt_vocab *v, int mode, const uint8_t *text, const uint64_t *str_off,
+                                     const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids, const uint64_t *id_off,
+                                     const int32_t *status, uint32_t *tok_end, uint32_t *tok_word, int32_t *span_status) {
+    dpt::SpansLaunch p;
+    p.mode = mode;
+    p.text = text;
+    p.str_off = str_off;
+    p.cut_mask = cut_mask;
+    p.n_str = n_str;
+    p.ids = ids;
+    p.id_off = id_off;
+    p.status = status;
+    p.tok_end = tok_end;
+    p.tok_word = tok_word;
+    p.span_status = span_status;
+    p.tok_len = v->d_tok_len;
+    p.id_min = v->id_min;
+    p.n_tab = v->n_tab;
+    return p;
+}
+
+int dpt_token_spans(const dpt_vocab *v, int mode, const uint8_t *text, uint64_t n_bytes, const uint64_t *str_off,
+                    const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids, const uint64_t *id_off,
+                    const int32_t *status, uint32_t *tok_end, uint32_t *tok_word, int32_t *span_status, void *hip_stream) {
+    const int rc = spans_check(v, mode, text, n_bytes, str_off, cut_mask, ids, id_off, status, tok_end, span_status);
+    if (rc) return rc;
+    if (!v->d_tok_len) return fail(DPT_E_VOCAB, "vocabulary has no dense per-id token lengths (sparse ids, or one id on tokens of different length)");
+    DeviceGuard g(v->device);
+    const hipError_t e = dpt::launch_spans(spans_launch(v, mode, text, str_off, cut_mask, n_str, ids, id_off, status, tok_end,
+                                                        tok_word, span_status), (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "spans launch");
+    return DPT_OK;
+}
+
+int dpt_token_spans_host(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_t *text, uint64_t n_bytes,
+                         const uint64_t *str_off, const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids,
+                         const uint64_t *id_off, const int32_t *status, uint32_t *tok_end, uint32_t *tok_word,
+                         int32_t *span_status) {
+    // host arguments first (checkable without a device)
+    int rc = spans_check(v, mode, text, n_bytes, str_off, cut_mask, ids, id_off, status, tok_end, span_status);
+    if (rc) return rc;
+    if (!c) return fail(DPT_E_ARG, "null ctx");
+    if (str_off[n_str] - str_off[0] != n_bytes) return fail(DPT_E_ARG, "n_bytes != str_off[n_str]-str_off[0]");
+    for (uint64_t i = 0; i < n_str; i++) {
+        if (str_off[i + 1] < str_off[i]) return fail(DPT_E_ARG, "str_off not monotone");
+        if (str_off[i + 1] - str_off[i] >= (1ull << 32)) return fail(DPT_E_ARG, "a string of 4 GiB or more");
+        if (id_off[i + 1] < id_off[i]) return fail(DPT_E_ARG, "id_off not monotone");
+    }
+    if (c->device != v->device) return fail(DPT_E_ARG, "ctx and vocab on different devices");
+    if (!v->d_tok_len) return fail(DPT_E_VOCAB, "vocabulary has no dense per-id token lengths (sparse ids, or one id on tokens of different length)");
+    if (n_str == 0) return DPT_OK;
+    const uint64_t n_tok = id_off[n_str] - id_off[0];
+    const bool cut = mode != DPT_MODE_RAW;
+    DeviceGuard g(c->device);
+    hipError_t e;
+    auto al8 = [](uint64_t x) { return (x + 7) & ~7ull; };
+    // in:  str_off and id_off rebased to 0 | ids | status | text | cut mask
+    const uint64_t o_ioff = 8 * (n_str + 1), o_ids = o_ioff + 8 * (n_str + 1), o_st = o_ids + al8(4 * n_tok + 4);
+    const uint64_t o_text = o_st + al8(4 * n_str), o_cut = o_text + al8(n_bytes + 1);
+    const uint64_t in_bytes = o_cut + (cut ? al8(n_bytes + 1) : 0);
+    // out: tok_end | tok_word | span_status
+    const uint64_t o_word = al8(4 * n_tok + 4), o_ss = o_word + (tok_word ? al8(4 * n_tok + 4) : 0), out_bytes = o_ss + al8(4 * n_str);
+    if ((e = grow(&c->d_in, &c->cap_in, in_bytes)) != hipSuccess) return hip_fail(e, "hipMalloc(host-path in)");
+    if ((e = grow(&c->d_out, &c->cap_out, out_bytes)) != hipSuccess) return hip_fail(e, "hipMalloc(host-path out)");
+    {   // (a pinned buffer that moved has a new device-side address: the encode host path looks it up again)
+        uint8_t *pi = c->p_in, *po = c->p_out;
+        if ((e = grow_pinned(&c->p_in, &c->cap_pin_in, in_bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc(in)");
+        if ((e = grow_pinned(&c->p_out, &c->cap_pin_out, out_bytes)) != hipSuccess) return hip_fail(e, "hipHostMalloc(out)");
+        if (pi != c->p_in) c->pd_in = nullptr;
+        if (po != c->p_out) c->pd_out = nullptr;
+    }
+    uint64_t *so = reinterpret_cast<uint64_t *>(c->p_in), *io = reinterpret_cast<uint64_t *>(c->p_in + o_ioff);
+    for (uint64_t i = 0; i <= n_str; i++) {
+        so[i] = str_off[i] - str_off[0];
+        io[i] = id_off[i] - id_off[0];
+    }
+    if (n_tok) memcpy(c->p_in + o_ids, ids, 4 * n_tok);
+    memcpy(c->p_in + o_st, status, 4 * n_str);
+    if (n_bytes) memcpy(c->p_in + o_text, text, n_bytes);
+    if (cut && n_bytes) memcpy(c->p_in + o_cut, cut_mask, n_bytes);
+    hipStream_t st = 0;
+    if ((e = hipMemcpyAsync(c->d_in, c->p_in, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D");
+    e = dpt::launch_spans(spans_launch(v, mode, c->d_in + o_text, reinterpret_cast<const uint64_t *>(c->d_in),
+                                       cut ? c->d_in + o_cut : nullptr, n_str, reinterpret_cast<const int32_t *>(c->d_in + o_ids),
+                                       reinterpret_cast<const uint64_t *>(c->d_in + o_ioff),
+                                       reinterpret_cast<const int32_t *>(c->d_in + o_st), reinterpret_cast<uint32_t *>(c->d_out),
+                                       tok_word ? reinterpret_cast<uint32_t *>(c->d_out + o_word) : nullptr,
+                                       reinterpret_cast<int32_t *>(c->d_out + o_ss)), st);
+    if (e != hipSuccess) return hip_fail(e, "spans launch");
+    if ((e = hipMemcpyAsync(c->p_out, c->d_out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+    if (n_tok) memcpy(tok_end, c->p_out, 4 * n_tok);
+    if (n_tok && tok_word) memcpy(tok_word, c->p_out + o_word, 4 * n_tok);
+    memcpy(span_status, c->p_out + o_ss, 4 * n_str);
+    return DPT_OK;
 }
 
 int dpt_token_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist, uint32_t n_bins,

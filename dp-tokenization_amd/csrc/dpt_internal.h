@@ -1,4 +1,4 @@
-// Internal interface between the C-ABI (dpt_api.cpp) and the kernels (dpt_kernels.hip).
+// Internal interface between the C-ABI (dpt_api.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -202,6 +202,24 @@ size_t wsl_scratch_bytes(unsigned max_blocks);
 size_t pend_scratch_bytes(unsigned max_blocks);
 hipError_t launch_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist,
                             uint32_t n_bins, hipStream_t stream);
+// token spans of an encoded batch (dpt_spans.hip; include/dpt.h dpt_token_spans): every pointer a device pointer
+struct SpansLaunch {
+    int mode;
+    const uint8_t *text;
+    const uint64_t *str_off;
+    const uint8_t *cut_mask;
+    uint64_t n_str;
+    const int32_t *ids;
+    const uint64_t *id_off;
+    const int32_t *status;
+    uint32_t *tok_end;
+    uint32_t *tok_word;        // nullable
+    int32_t *span_status;
+    const uint16_t *tok_len;   // the vocabulary's byte length per id - id_min (0: no token has this id)
+    int32_t id_min;
+    uint32_t n_tab;            // entries of tok_len
+};
+hipError_t launch_spans(const SpansLaunch &p, hipStream_t stream);
 hipError_t kernel_init();
 int small_window_bytes();
 int big_window_bytes();

@@ -8,9 +8,9 @@ The reference-compatible names (dp_tokenize_llama, compute_shortest_tokenization
 live in the sibling ``packages`` / ``inspect_tokenizer`` modules of this directory.
 """
 from ._lib import DptError, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
-from .engine import Encoder, Vocab, pack_strings, raise_for_status
+from .engine import Encoder, TokenSpans, Vocab, pack_strings, raise_for_status
 
-__all__ = ["Vocab", "Encoder", "DptError", "pack_strings", "raise_for_status", "dp_tokenize_batch",
+__all__ = ["Vocab", "Encoder", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
            "STATUS_OK", "STATUS_NO_TOKENIZATION", "STATUS_EMPTY_WORD", "STATUS_TOO_LONG", "STATUS_INTERNAL"]
 
 

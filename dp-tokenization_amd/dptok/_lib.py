@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPT_LIB") or os.path.join(HERE, "libdpt.so")
 
 DPT_OK = 0
+DPT_E_VOCAB = -3
 DPT_E_CAP = -4
 DPT_E_RCCL = -6
 DPT_RCCL_ID_BYTES = 128
@@ -72,6 +73,8 @@ def lib():
     L.dpt_dp_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P]
     L.dpt_dp_host_far.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P, P, U64, P]
     L.dpt_token_histogram.argtypes = [P, P, U64, P, ctypes.c_uint32, P]
+    L.dpt_token_spans.argtypes = [P, I32, P, U64, P, P, U64, P, P, P, P, P, P, P]
+    L.dpt_token_spans_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P, P, P, P]
     L.dpt_ctx_set_histogram.argtypes = [P, P, ctypes.c_uint32]
     L.dpt_ctx_set_histogram_ex.argtypes = [P, P, ctypes.c_uint32, I32]
     L.dpt_ctx_profile.argtypes = [P, I32]
@@ -83,7 +86,7 @@ def lib():
     L.dpt_hist_allreduce.argtypes = [P, ctypes.c_size_t, P, P]
     for name in ("dpt_vocab_create", "dpt_vocab_destroy", "dpt_vocab_stats_get", "dpt_ctx_create", "dpt_ctx_destroy",
                  "dpt_ctx_reserve", "dpt_ctx_reserve_vocab", "dpt_ctx_workspace_bytes", "dpt_ctx_long_need", "dpt_encode", "dpt_encode_padded", "dpt_encode_host", "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram",
-                 "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex", "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias",
+                 "dpt_token_spans", "dpt_token_spans_host", "dpt_ctx_set_histogram","dpt_ctx_set_histogram_ex", "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias",
                  "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"):
         getattr(L, name).restype = I32
     _lib = L
@@ -101,5 +104,6 @@ EXPORTED = ["dpt_last_error", "dpt_abi_version", "dpt_vocab_create", "dpt_vocab_
             "dpt_ctx_long_need",
             "dpt_encode", "dpt_encode_padded", "dpt_encode_host",
             "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram", "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex",
+            "dpt_token_spans", "dpt_token_spans_host",
             "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias",
             "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"]

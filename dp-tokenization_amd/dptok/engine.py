@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import gc
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -46,6 +46,41 @@ def csr_lists(ids: np.ndarray, id_off: np.ndarray, status: np.ndarray, none: Opt
     return [([], _lib.STATUS_OK) if nn[i] else
             ((flat[o[i]:o[i + 1]] if (keep_failed or sl[i] == _lib.STATUS_OK) else []), sl[i])
             for i in range(len(sl))]
+class TokenSpans(NamedTuple):
+    """One string's tokenization aligned to its text: ``offsets[k]`` = (start, end) of token k in
+    CHARACTERS of ``text`` (the string the engine tokenized), ``word_ids[k]`` the 0-based word it lies in."""
+    ids: List[int]
+    offsets: List[Tuple[int, int]]
+    word_ids: List[int]
+    text: str
+
+
+def csr_token_spans(text: np.ndarray, offs: np.ndarray, ids: np.ndarray, id_off: np.ndarray, tok_end: np.ndarray,
+                    tok_word: np.ndarray) -> List[TokenSpans]:
+    """``Encoder.encode_csr_spans`` output -> one ``TokenSpans`` per string.  The byte ends become
+    character offsets through one count of non-continuation bytes over the batch (a token ends on a
+    code-point boundary, so the characters before its end are the non-continuation bytes before it)."""
+    o = np.asarray(offs).astype(np.int64)
+    raw = np.asarray(text, dtype=np.uint8)[int(o[0]):int(o[-1])]
+    o = o - o[0]
+    n = len(o) - 1
+    cum = np.zeros(len(raw) + 1, dtype=np.int64)
+    np.cumsum((raw & 0xC0) != 0x80, out=cum[1:])
+    io = np.asarray(id_off).astype(np.int64)
+    io = io - io[0]
+    cnt = np.diff(io)
+    sb = np.repeat(o[:-1], cnt)                     # each token's string start, bytes
+    ce = cum[sb + np.asarray(tok_end).astype(np.int64)] - cum[sb]
+    cs = np.empty_like(ce)
+    cs[1:] = ce[:-1]                                # a token starts where the one before it ends ...
+    cs[io[:-1][cnt > 0]] = 0                        # ... and a string's first token at 0
+    pairs = list(zip(cs.tolist(), ce.tolist()))
+    flat, words, blob = np.asarray(ids).tolist(), np.asarray(tok_word).tolist(), raw.tobytes()
+    ol, il = o.tolist(), io.tolist()
+    return [TokenSpans(flat[il[s]:il[s + 1]], pairs[il[s]:il[s + 1]], words[il[s]:il[s + 1]],
+                       blob[ol[s]:ol[s + 1]].decode("utf-8", "surrogatepass")) for s in range(n)]
+
+
 from ._lib import (DPT_FLAG_LEN_ONLY, DPT_FLAG_UNCAPPED, DPT_MODE_ATOMS, DPT_MODE_PRESPLIT, DPT_MODE_RAW, DptError,
                    check)
 
@@ -291,6 +326,31 @@ class Encoder:
                                          max(n_bytes, 1), _ptr(id_off), _ptr(status), _ptr(capped)), "dpt_encode_host")
         return ids[: int(id_off[-1])], id_off, status[:n], capped[:n]
 
+    def encode_csr_spans(self, text: np.ndarray, offs: np.ndarray, mode="raw", cut_mask: Optional[np.ndarray] = None):
+        """``encode_csr`` followed by dpt_token_spans_host on its outputs -> (ids, id_off, status, capped,
+        tok_end u32[n_tok], tok_word u32[n_tok], span_status int32[n]): token k of string s (index
+        id_off[s] + k) covers bytes [tok_end[k-1] or 0, tok_end[k]) of the string and lies in its word
+        tok_word[k]; span_status[s] is status[s], or 4 if the ids did not tile the string (never expected)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if cut_mask is not None:
+            cut_mask = np.ascontiguousarray(cut_mask, dtype=np.uint8)
+        ids, id_off, status, capped = self.encode_csr(text, offs, mode=mode, cut_mask=cut_mask)
+        n = len(offs) - 1
+        n_bytes = int(offs[-1] - offs[0]) if n >= 0 else 0
+        n_tok = len(ids)
+        ids_buf = ids if n_tok else np.zeros(1, dtype=np.int32)
+        st_buf = status if n else np.zeros(1, dtype=np.int32)
+        tok_end = np.zeros(max(n_tok, 1), dtype=np.uint32)
+        tok_word = np.zeros(max(n_tok, 1), dtype=np.uint32)
+        span_status = np.zeros(max(n, 1), dtype=np.int32)
+        base = int(offs[0])
+        check(_lib.lib().dpt_token_spans_host(self.handle, self.vocab.handle, MODES[mode], _ptr(text[base:] if base else text),
+                                              n_bytes, _ptr(offs), _ptr(cut_mask[base:] if cut_mask is not None else None),
+                                              n, _ptr(ids_buf), _ptr(id_off), _ptr(st_buf), _ptr(tok_end), _ptr(tok_word),
+                                              _ptr(span_status)), "dpt_token_spans_host")
+        return ids, id_off, status, capped, tok_end[:n_tok], tok_word[:n_tok], span_status[:n]
+
     def encode_one(self, s: str) -> Tuple[List[int], int]:
         """One raw-mode string -> (ids, status): the drop-in's per-string call (reference main_analyze_s2orc.py:74-78)
         with as little host work as a ctypes call allows -- the UTF-8 bytes passed as they are, the offsets,
@@ -428,6 +488,19 @@ class Encoder:
                                            ctypes.c_void_p(ids_ptr), ids_cap, ctypes.c_void_p(counts_ptr),
                                            ctypes.c_void_p(status_ptr), ctypes.c_void_p(capped_ptr or None),
                                            ctypes.c_void_p(stream or None)), "dpt_encode_padded")
+
+    def spans_device(self, text_ptr: int, n_bytes: int, off_ptr: int, n_str: int, ids_ptr: int, idoff_ptr: int,
+                     status_ptr: int, tok_end_ptr: int, span_status_ptr: int, tok_word_ptr: int = 0, cut_ptr: int = 0,
+                     stream: int = 0, mode="raw") -> None:
+        """dpt_token_spans on the outputs of an ``encode_device`` call with the same text / offsets / mode:
+        tok_end (uint32 per id), tok_word (uint32 per id, 0: not wanted) and span_status (int32 per string).
+        Device addresses, stream-ordered, no sync, no workspace (the engine's ctx is not used)."""
+        check(_lib.lib().dpt_token_spans(self.vocab.handle, MODES[mode], ctypes.c_void_p(text_ptr), n_bytes,
+                                         ctypes.c_void_p(off_ptr), ctypes.c_void_p(cut_ptr or None), n_str,
+                                         ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr), ctypes.c_void_p(status_ptr),
+                                         ctypes.c_void_p(tok_end_ptr), ctypes.c_void_p(tok_word_ptr or None),
+                                         ctypes.c_void_p(span_status_ptr), ctypes.c_void_p(stream or None)),
+              "dpt_token_spans")
 
     def reserve(self, n_bytes: int, n_str: int, long_bytes: int = 0) -> None:
         """Pre-size the workspace for this vocabulary's staging width (a later call of that size is

@@ -15,6 +15,12 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   like the reference's unbound ``pretokenize_func``.
 * ``dp_tokenize.batch(List[str]) -> List[List[int]]``: the batched form (one GPU launch, in both
   modes).
+* ``dp_tokenize.batch_spans(List[str]) -> List[TokenSpans]``: the batch's ids aligned to the text --
+  per string ``(ids, offsets, word_ids, text)``: ``text`` is the string the engine tokenized (the input
+  in raw mode, the concatenated pieces in llama mode, the concatenated atoms for BLOOM), ``offsets[k]``
+  the (start, end) of token k in characters of ``text``, ``word_ids[k]`` the 0-based word it lies in
+  (what the probe at reference main_analyze_s2orc.py:275-290 re-tokenizes every word to learn).  Same
+  exceptions as ``batch``.
 * ``merge_tokens``, ``pretokenize_with_llama``, ``pretokenize_raw``: the reference's host-side
   string utilities with identical behaviour (pre-tokenization, not the DP).
 """
@@ -28,8 +34,10 @@ _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
-from dptok import Encoder, Vocab, raise_for_status  # noqa: E402
-from dptok.engine import PieceTable  # noqa: E402
+from dptok import DptError, Encoder, Vocab, raise_for_status  # noqa: E402
+from dptok import _lib as _dpt  # noqa: E402
+from dptok.engine import (PieceTable, TokenSpans, csr_token_spans, pack_presplit_words, pack_strings,  # noqa: E402
+                          pack_word_atoms)
 from dptok.hostpool import shared_pool  # noqa: E402
 
 SPACE_TOKEN = "▁"
@@ -138,6 +146,24 @@ def batch_encoder(tokenizer):
     return lambda texts: [tokenizer.encode(t) for t in texts]
 
 
+def _batch_spans(engine, texts, text, offs, mode, cut=None, none=None, fix_status=None) -> List[TokenSpans]:
+    """One encode + spans call over a packed batch -> a ``TokenSpans`` per string.  ``none[i]``: string i
+    has no words (an empty result, whatever its status); ``fix_status(i, status)``: the status that
+    decides string i's exception.  Raises what ``dp_tokenize.batch`` raises, string by string in order,
+    and DptError when a string's ids do not tile it (span status 4: never expected)."""
+    ids, id_off, st, _, tok_end, tok_word, sst = engine.encode_csr_spans(text, offs, mode=mode, cut_mask=cut)
+    out = csr_token_spans(text, offs, ids, id_off, tok_end, tok_word)
+    stl, sstl = st.tolist(), sst.tolist()
+    for i, t in enumerate(texts):
+        if none is not None and none[i]:
+            out[i] = TokenSpans([], [], [], "")
+            continue
+        raise_for_status(fix_status(i, stl[i]) if fix_status else stl[i], t)
+        if sstl[i] != _dpt.STATUS_OK:
+            raise DptError("token spans: the ids do not tile the string (status %d) of %r" % (sstl[i], t[:60]))
+    return out
+
+
 def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
     t2i: Dict[str, int] = dict(llama_tokenizer.get_vocab())
     vocab_bidict = _InverseDict(t2i)
@@ -153,6 +179,10 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
                 raise_for_status(st, t)
                 out.append(ids)
             return out
+
+        def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
+            texts = list(texts)
+            return _batch_spans(engine, texts, *pack_strings(texts), "raw")
     elif pretokenize_option == "llama":
         pretokenize = pretokenize_with_llama(llama_tokenizer, vocab_bidict)
         pieces = PieceTable(t2i)
@@ -173,9 +203,23 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
                 raise_for_status(st, t)
                 out.append(ids)
             return out
+
+        def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
+            # the same two packings as encode_many; ``text`` is the pieces' concatenation
+            texts = list(texts)
+            if pieces.ok and not pieces.empty_piece:
+                text, offs, cut, cnt = host.pack(texts)
+                return _batch_spans(engine, texts, text, offs, "presplit", cut, none=(cnt == 0).tolist())
+            text, offs, cut, n_words, cut_at = pack_presplit_words([pretokenize(t) for t in texts])
+
+            def fix(i, s):   # (Encoder.encode_presplit: a string is cut at its first empty word -> IndexError)
+                return _dpt.STATUS_EMPTY_WORD if cut_at[i] >= 0 and s in (_dpt.STATUS_OK, _dpt.STATUS_EMPTY_WORD) else s
+            return _batch_spans(engine, texts, text, offs, "presplit", cut,
+                                none=[cut_at[i] < 0 and n_words[i] == 0 for i in range(len(texts))], fix_status=fix)
     else:
         def encode_many(texts):
             raise NameError("name 'pretokenize_func' is not defined")
+        spans_many = encode_many
 
     if pretokenize_option == "raw":
         def dp_tokenize(input_str) -> List[int]:
@@ -191,6 +235,7 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
         return llama_tokenizer.decode(encoding)[4:]
 
     dp_tokenize.batch = encode_many
+    dp_tokenize.batch_spans = spans_many
     dp_tokenize.engine = engine
     if pretokenize_option == "llama":
         dp_tokenize.host_pool = host
@@ -243,6 +288,13 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
             out.append(ids)
         return out
 
+    def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
+        # ``text`` is the atoms' concatenation (the byte-level alphabet's characters, one per input byte)
+        texts = list(texts)
+        batch = [[atoms_of(w) for w in pretokenize(t)] for t in texts]
+        text, offs, cut = pack_word_atoms(batch)
+        return _batch_spans(engine, texts, text, offs, "atoms", cut, none=[not words for words in batch])
+
     def dp_tokenize(input_str) -> List[int]:
         return encode_many([input_str])[0]
 
@@ -250,6 +302,7 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
         return bloom_tokenizer.decode(encoding)   # reference :179-181
 
     dp_tokenize.batch = encode_many
+    dp_tokenize.batch_spans = spans_many
     dp_tokenize.engine = engine
     dp_tokenize.vocab_to_index = vocab_to_index
     return dp_tokenize, decode_dp_tokenization

@@ -18,6 +18,8 @@
  *                        (packages/tokenizer_utils.py:7-31, DPT_MODE_PRESPLIT)
  *   dpt_token_histogram <- the length comparison of the S2ORC probe,
  *                        reference main_analyze_s2orc.py:269-297 (len(dp_tokenize(x)))
+ *   dpt_token_spans    <- the probe's per-word comparison, reference main_analyze_s2orc.py:275-290
+ *                        (dp_tokenize on every pre-token, to tell which words the DP shortened)
  *   dpt_hist_allreduce <- SURVEY.md §8(b)/(e): the one collective of a sharded corpus (the
  *                        reference is single-process, llama_s2orc.sh:10; no call site there)
  *
@@ -197,6 +199,47 @@ int dpt_dp_host_far(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uint8_
 #define DPT_HIST_MAX_BINS 16384
 int dpt_token_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str,
                         int64_t *hist, uint32_t n_bins, void *hip_stream);
+
+/*
+ * Token byte spans and word indices of an encoded batch: which part of the input each id covers -- the
+ * offset_mapping / word_ids of the tokenizers the reference sits beside, and what the S2ORC probe's
+ * per-word comparison (reference main_analyze_s2orc.py:269-293) re-tokenizes every word for.
+ * Added within ABI 6 (DPT_ABI_VERSION unchanged): a binding that may meet an older libdpt.so probes for
+ * the symbol.
+ *
+ * text, n_bytes, str_off, cut_mask, n_str and mode are dpt_encode's arguments (same conventions:
+ * str_off[0] need not be 0, text and cut_mask correspond to str_off[0], no alignment needed); ids,
+ * id_off and status are what dpt_encode wrote for them.  Token k of string s is
+ * ids[id_off[s] - id_off[0] + k]; tok_end and tok_word (nullable) use the same index.  Per string s:
+ *   span_status[s] = status[s] when status[s] != 0 (nothing else is written for s); else 0 and
+ *   tok_end[k]   the byte offset within the string, in the caller's text, where token k ends (token k
+ *                starts at tok_end[k-1], token 0 at 0; the last token ends at the string's length)
+ *   tok_word[k]  the 0-based index, within the string, of the word token k lies in.  A word starts at
+ *                offset 0 and -- RAW -- at every ' ' after offset 0, -- PRESPLIT -- where cut_mask != 0,
+ *                -- ATOMS -- where cut_mask & 1
+ * A DP tokenization tiles the atom-expanded string, so the ends follow from the ids' byte lengths: with
+ * E_k the summed length of tokens 0..k, tok_end[k] is the offset p whose expanded offset x(p) is E_k --
+ * x(p) = p in PRESPLIT / ATOMS; RAW: x(0) = 0, x(p) = 3 + p + 2 * (the ' ' in [1, p)) + 5 * (the '\n' in
+ * [1, p)) (pretokenize_raw, reference tokenizer_utils.py:33-50: byte 0 literal behind the word mark).
+ * Ids that do not tile their string -- an id no token has, an E_k no offset attains, a last E_k that is
+ * not x(length) -- give span_status[s] = DPT_STATUS_INTERNAL and unspecified tok_end / tok_word for s
+ * alone; every store stays inside the string's own [id_off[s], id_off[s+1]) whatever the ids hold.
+ * Strings < 4 GiB, str_off and id_off monotone (dpt_token_spans cannot check device-resident offsets).
+ * DPT_E_VOCAB for a vocabulary without a dense per-id length table: ids spread over more than
+ * 8 * n_tokens + 65536 values, or two tokens of different byte length on one id.
+ *
+ * dpt_token_spans: DEVICE pointers on the vocabulary's device; stream-ordered on hip_stream, never
+ * synchronises, allocates nothing and needs no dpt_ctx: any number of calls may be in flight on one vocab.
+ */
+int dpt_token_spans(const dpt_vocab *v, int mode, const uint8_t *text, uint64_t n_bytes, const uint64_t *str_off,
+                    const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids, const uint64_t *id_off,
+                    const int32_t *status, uint32_t *tok_end, uint32_t *tok_word, int32_t *span_status, void *hip_stream);
+/* Same with HOST pointers: copies in through the ctx's host-path staging (grows on demand), runs, copies
+ * out, synchronises.  Checks that both offset arrays are monotone and every string is under 4 GiB. */
+int dpt_token_spans_host(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_t *text, uint64_t n_bytes,
+                         const uint64_t *str_off, const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids,
+                         const uint64_t *id_off, const int32_t *status, uint32_t *tok_end, uint32_t *tok_word,
+                         int32_t *span_status);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
