@@ -50,8 +50,7 @@ struct dpt_ctx {
     uint64_t *counts = nullptr;
     uint32_t *retry_list = nullptr;
     uint64_t cap_str = 0;
-    uint32_t *retry_count = nullptr;  // counter block (dpt::CTR_ALLOC_BYTES): 8 uint32 counters, the uint64 arena
-                                      // counter at byte 32, ..., the first pass's partition counters at byte 256
+    dpt::CounterBlock *ctr = nullptr; // the counter block (dpt::CTR_ALLOC_BYTES)
     uint8_t *wsl_scratch = nullptr;   // word lists of the 256-byte pass (dpt::wsl_scratch_bytes)
     uint4 *pend = nullptr;            // pending residual tokens of the 256-byte pass (dpt::pend_scratch_bytes)
     // two parity regions R0, R1 of batch lines (dpt::BS_LINE u64 per 256-string batch: its sum in the
@@ -141,7 +140,7 @@ uint64_t default_long_bytes(uint64_t n_bytes) {
 }
 
 constexpr uint64_t ARENA_PER_BYTE = 20;   // uint4 rec + int32 stg (dpt_long.hip)
-constexpr size_t COUNTER_BYTES = 64;
+constexpr size_t COUNTER_BYTES = sizeof(dpt::CounterBlock);   // what the host path reads back
 
 // v == nullptr: both staging widths (the vocabulary is not known yet); staging = false: no staging
 // (dpt_encode_padded writes the ids into the caller's buffer)
@@ -162,13 +161,12 @@ int ensure_workspace(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint64_t 
         c->arena_cap = cap / ARENA_PER_BYTE;
     }
     if (n_str > c->cap_str || !c->counts) {
-        uint64_t cap = c->cap_str, cap2 = 3 * c->cap_str;
+        uint64_t cap = c->cap_str, cap2 = dpt::N_RETRY_LISTS * c->cap_str;
         e = grow(&c->counts, &cap, n_str);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(counts)");
-        // the first pass's retry list, the unbounded pass's list, the 2048-byte pass's list after the 512-byte pass
-        e = grow(&c->retry_list, &cap2, 3 * n_str);
+        e = grow(&c->retry_list, &cap2, dpt::N_RETRY_LISTS * n_str);   // (dpt::RetryList)
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(retry_list)");
-        cap2 /= 3;
+        cap2 /= dpt::N_RETRY_LISTS;
         c->cap_str = cap < cap2 ? cap : cap2;
     }
     const uint64_t nbat = (n_str + dpt::FIN_BATCH - 1) / dpt::FIN_BATCH;
@@ -193,10 +191,10 @@ int ensure_workspace(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint64_t 
         e = hipMalloc((void **)&c->pend, dpt::pend_scratch_bytes(c->max_blocks));
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(pend)");
     }
-    if (!c->retry_count) {
+    if (!c->ctr) {
         // zeroed once here; every call's finish kernel resets it for the next call
-        e = hipMalloc((void **)&c->retry_count, dpt::CTR_ALLOC_BYTES);
-        if (e == hipSuccess) e = hipMemset(c->retry_count, 0, dpt::CTR_ALLOC_BYTES);
+        e = hipMalloc((void **)&c->ctr, dpt::CTR_ALLOC_BYTES);
+        if (e == hipSuccess) e = hipMemset(c->ctr, 0, dpt::CTR_ALLOC_BYTES);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(retry_count)");
         fresh = true;
     }
@@ -539,7 +537,7 @@ int dpt_ctx_create(int device, dpt_ctx **out) {
 int dpt_ctx_destroy(dpt_ctx *c) {
     if (!c) return DPT_OK;
     DeviceGuard g(c->device);
-    void *ps[] = {c->staging32, c->staging16, c->arena, c->counts, c->retry_list, c->retry_count, c->wsl_scratch,
+    void *ps[] = {c->staging32, c->staging16, c->arena, c->counts, c->retry_list, c->ctr, c->wsl_scratch,
                   c->pend, c->flags, c->d_in, c->d_out};
     for (void *p : ps)
         if (p) (void)hipFree(p);
@@ -566,10 +564,10 @@ int dpt_ctx_reserve_vocab(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint
 int dpt_ctx_workspace_bytes(const dpt_ctx *c, uint64_t *device_path, uint64_t *host_path) {
     if (!c) return fail(DPT_E_ARG, "null ctx");
     if (device_path)
-        *device_path = c->cap16 * 2 + c->cap32 * 4 + c->arena_cap * ARENA_PER_BYTE + c->cap_str * (8 + 3 * 4) +
+        *device_path = c->cap16 * 2 + c->cap32 * 4 + c->arena_cap * ARENA_PER_BYTE + c->cap_str * (8 + dpt::N_RETRY_LISTS * 4) +
                        flag_words(c->cap_batches) * 8 + (c->wsl_scratch ? dpt::wsl_scratch_bytes(c->max_blocks) : 0) +
                        (c->pend ? dpt::pend_scratch_bytes(c->max_blocks) : 0) +
-                       (c->retry_count ? dpt::CTR_ALLOC_BYTES : 0);
+                       (c->ctr ? dpt::CTR_ALLOC_BYTES : 0);
     if (host_path) *host_path = c->cap_in + c->cap_out;
     return DPT_OK;
 }
@@ -578,9 +576,9 @@ int dpt_ctx_long_need(dpt_ctx *c, uint64_t *need, uint64_t *cap) {
     if (!c || !need) return fail(DPT_E_ARG, "null argument");
     *need = 0;
     if (cap) *cap = c->arena_cap;
-    if (!c->retry_count) return DPT_OK;
+    if (!c->ctr) return DPT_OK;
     DeviceGuard g(c->device);
-    hipError_t e = hipMemcpy(need, reinterpret_cast<uint8_t *>(c->retry_count) + 40, sizeof(uint64_t), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(need, &c->ctr->last_need, sizeof(uint64_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "D2H arena counter");
     *need = *need >= c->counter_bias ? *need - c->counter_bias : 0;   // (0 after an empty call)
     return DPT_OK;
@@ -639,7 +637,7 @@ static int encode_impl(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uin
     p.staging = c->staging32;
     p.counts = c->counts;
     p.retry_list = c->retry_list;
-    p.retry_count = c->retry_count;
+    p.ctr = c->ctr;
     p.wsl_scratch = c->wsl_scratch;
     p.long_span = v->stats.max_cp > 64 ? 1 : 0;
     p.max_tok_bytes = v->stats.max_bytes;
@@ -660,10 +658,10 @@ static int encode_impl(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uin
         // left them 0), so the kernels' offsets have a low word >= 2^31 without a 40-GiB arena; the far
         // list is passed down shifted by as many pairs
         const uint64_t b = c->counter_bias;
-        uint32_t *ctr = c->retry_count;
-        for (unsigned w : {8u, 12u}) {   // (uint64 counters 4 and 6: the arena's claimed bytes, the far pairs)
-            hipError_t e0 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctr + w), (int)(uint32_t)b, 1, st);
-            if (e0 == hipSuccess) e0 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ctr + w + 1), (int)(uint32_t)(b >> 32), 1, st);
+        for (uint64_t *w : {&c->ctr->arena_used, &c->ctr->far_pairs}) {
+            uint32_t *const lo = reinterpret_cast<uint32_t *>(w);
+            hipError_t e0 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lo), (int)(uint32_t)b, 1, st);
+            if (e0 == hipSuccess) e0 = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lo + 1), (int)(uint32_t)(b >> 32), 1, st);
             if (e0 != hipSuccess) return hip_fail(e0, "counter bias");
         }
         if (p.far) {
@@ -683,7 +681,7 @@ static int encode_impl(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uin
     p.no_fallback = no_fallback;
     p.n_bytes = n_bytes;
     // (a per-string dp_tokenize call: one launch instead of two -- the finish kernel was 5 us of its 43)
-    p.solo = !getenv("DPT_NO_SOLO") && no_fallback && n_str == 1 && !padded && !edges && !hist && !c->profile && ctr_snap;
+    p.solo = !dpt::launch_knobs().no_solo && no_fallback && n_str == 1 && !padded && !edges && !hist && !c->profile && ctr_snap;
     if (padded) {   // the ids go straight to their final place (int32), the counts to the caller's array
         p.staging = ids;
         p.staging16 = nullptr;
@@ -709,7 +707,7 @@ static int encode_impl(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uin
     }
     hipError_t e = dpt::launch_encode(p, st, evp);
     if (e != hipSuccess) {
-        (void)hipMemsetAsync(c->retry_count, 0, dpt::CTR_ALLOC_BYTES, st);   // the scan kernel did not reset them
+        (void)hipMemsetAsync(c->ctr, 0, dpt::CTR_ALLOC_BYTES, st);   // the scan kernel did not reset them
         (void)hipMemsetAsync(c->flags, 0, flag_words(c->cap_batches) * sizeof(unsigned long long), st);   // nor zero the batch lines
         c->flag_parity = 0;
         return hip_fail(e, "encode launch");
@@ -743,9 +741,9 @@ static int rerun_too_long(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_
 constexpr uint64_t NO_FALLBACK_CHECK_BYTES = 16384;
 
 // True when no string of a RAW / PRESPLIT call can leave the first pass (dpt_kernels.hip tokenize_kernel):
-// every word fits one 256-byte window (consecutive word starts -- byte 0, then ' ' in RAW mode or a cut
-// byte on a non-continuation byte in PRESPLIT mode -- at most 256 bytes apart, the last one at most 256
-// bytes before the string's end) and every atom (a code point: a byte and its continuation bytes) has at
+// every word fits its window of dpt::SMALL_CH bytes (consecutive word starts -- byte 0, then ' ' in RAW mode
+// or a cut byte on a non-continuation byte in PRESPLIT mode -- at most that far apart, the last one at most
+// that far before the string's end) and every atom (a code point: a byte and its continuation bytes) has at
 // most 4 bytes.  (Vocabularies with tokens of more than 64 code points are not checked: the caller.)
 static bool no_fallback_needed(int mode, const uint8_t *text, const uint64_t *str_off, const uint8_t *cut,
                                uint64_t n_str) {
@@ -762,11 +760,11 @@ static bool no_fallback_needed(int mode, const uint8_t *text, const uint64_t *st
             if (cont > 3) return false;   // an atom of over 4 bytes
             const bool wstart = k > a && (mode == DPT_MODE_RAW ? x == ' ' : (cut[k] != 0 && !is_cont));
             if (wstart) {
-                if (k - ws > 256) return false;
+                if (k - ws > dpt::SMALL_CH) return false;
                 ws = k;
             }
         }
-        if (b - ws > 256) return false;
+        if (b - ws > dpt::SMALL_CH) return false;
     }
     return true;
 }
@@ -838,7 +836,7 @@ static int encode_host_impl(dpt_ctx *c, const dpt_vocab *v, int mode, const uint
     // One string with no fallback pass (a per-string dp_tokenize call): zero-copy -- its lone wave
     // (EncodeLaunch::solo) reads the text from and writes the outputs to the pinned host buffers, so the
     // call is one launch and a sync (two copies and their gaps less)
-    if (no_fb && n_str == 1 && !edges && !c->profile && !getenv("DPT_NO_SOLO")) {
+    if (no_fb && n_str == 1 && !edges && !c->profile && !dpt::launch_knobs().no_solo) {
         int rc = encode_impl(c, v, mode, c->pd_in, n_bytes, reinterpret_cast<const uint64_t *>(c->pd_in + o_off),
                              cut ? c->pd_in + o_cut : nullptr, n_str, reinterpret_cast<int32_t *>(c->pd_out + o_ids),
                              n_bytes ? n_bytes : 1, reinterpret_cast<uint64_t *>(c->pd_out),
@@ -866,7 +864,7 @@ static int encode_host_impl(dpt_ctx *c, const dpt_vocab *v, int mode, const uint
             return hip_fail(e, "D2H");
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
         uint64_t used = 0;
-        if (n_str) memcpy(&used, c->p_out + o_ctr + 40, sizeof(used));   // the call's claimed bytes (finish_kernel)
+        if (n_str) memcpy(&used, c->p_out + o_ctr + offsetof(dpt::CounterBlock, last_need), sizeof(used));   // the call's claimed bytes (finish_kernel)
         if (n_str) used -= c->counter_bias;   // (test-only dpt_ctx_debug_counter_bias)
         if (used > n_bytes) return fail(DPT_E_HIP, "unbounded pass counter out of range");   // never expected
         if (used <= c->arena_cap) break;
@@ -885,7 +883,7 @@ static int encode_host_impl(dpt_ctx *c, const dpt_vocab *v, int mode, const uint
     if (total > ids_cap) return fail(DPT_E_CAP, "ids overflow");
     uint64_t nf = 0;
     if (want_far) {
-        if (n_str) memcpy(&nf, c->p_out + o_ctr + 56, sizeof(nf));   // the call's far edge pairs (finish_kernel)
+        if (n_str) memcpy(&nf, c->p_out + o_ctr + offsetof(dpt::CounterBlock, last_far), sizeof(nf));   // the call's far edge pairs (finish_kernel)
         if (n_str) nf -= c->counter_bias;
         if (n_far) *n_far = nf;
         if (nf > far_cap) return fail(DPT_E_CAP, "far edge list overflow (*n_far holds the pairs needed)");

@@ -9,6 +9,42 @@
 
 namespace dpt {
 
+// window bytes of the windowed passes
+constexpr int SMALL_CH = 256;   // the first pass's window
+constexpr int MID_CH = 512;     // the 512-byte pass's (PRESPLIT / ATOMS calls of 16-lane vocabularies)
+constexpr int BIG_CH = 2048;    // the 2048-byte pass's
+
+// The first 64 bytes of the counter block (CTR_ALLOC_BYTES; from byte PART_CTR_OFFSET the first pass's
+// partition counters and their used-up mask).  Zeroed once at allocation, then reset for the next call
+// (reset_counters, dpt_kernels.hip) by the batch scan or the finish pass -- or, in a one-string host-path
+// call, by the lone wave of the first pass.  The host path reads these 64 bytes back (EncodeLaunch::ctr_snap).
+struct CounterBlock {
+    uint32_t retry_count;       // strings on the 2048-byte pass's list (first pass); the 512-byte pass's input
+    uint32_t big_done;          // 2048-byte blocks done (fallback_kernel)
+    uint32_t big_work;          // the 2048-byte pass's work counter
+    uint32_t long_count;        // strings on the unbounded pass's list
+    uint32_t long_work;         // the unbounded pass's work counter
+    uint32_t mid_work;          // the 512-byte pass's work counter (mid_kernel)
+    uint32_t ticket;            // fallback_kernel's block ticket
+    uint32_t mid_retry_count;   // the 2048-byte pass's list count when the 512-byte pass ran
+    uint64_t arena_used;        // the unbounded pass's claimed arena bytes
+    uint64_t last_need;         // ... of the last call (dpt_ctx_long_need)
+    uint64_t far_pairs;         // far edge pairs found
+    uint64_t last_far;          // ... by the last call (dpt_dp_host_far)
+};
+// (the kernels address the block, partition counters included, as uint32 words)
+inline uint32_t *ctr_words(CounterBlock *c) { return reinterpret_cast<uint32_t *>(c); }
+static_assert(sizeof(CounterBlock) == 64, "counter block");
+static_assert(offsetof(CounterBlock, last_need) == 40 && offsetof(CounterBlock, last_far) == 56, "host read-back");
+
+// EncodeLaunch::retry_list holds three lists of up to n_str string indices each
+enum RetryList {
+    LIST_BIG = 0,             // the 2048-byte pass's, filled by the first pass (the 512-byte pass's input when it runs)
+    LIST_LONG = 1,            // the unbounded pass's
+    LIST_BIG_AFTER_MID = 2,   // the 2048-byte pass's when the 512-byte pass ran: what that pass could not hold
+    N_RETRY_LISTS = 3
+};
+
 struct EncodeLaunch {
     int mode;                // DPT_MODE_* | DPT_FLAG_*
     uint64_t *edges;         // nullable: per atom end E(i)&reachable masks (n_bytes entries)
@@ -26,8 +62,8 @@ struct EncodeLaunch {
     int32_t *staging;
     int16_t *staging16;      // non-null: ids staged as int16 here instead (every vocabulary id in 0..32767)
     uint64_t *counts;
-    uint32_t *retry_list;    // 2 x n_str: the 2048-byte pass's list, then (at + n_str) the unbounded pass's list
-    uint32_t *retry_count;   // the 64-byte counter block (dpt_kernels.hip, finish_kernel)
+    uint32_t *retry_list;    // N_RETRY_LISTS x n_str string indices (retry_list_of below)
+    CounterBlock *ctr;       // the counter block (CTR_ALLOC_BYTES)
     uint8_t *wsl_scratch;    // max_blocks x wsl_scratch_bytes(1) bytes
     int long_span;           // vocabulary tokens longer than 64 code points: words over 64 atoms -> unbounded pass
     uint32_t max_tok_bytes;  // longest vocabulary token, bytes
@@ -165,37 +201,21 @@ __host__ __device__ inline void tokhash(uint32_t w0, uint32_t w1, uint32_t w2, u
 constexpr int KERNEL_ROWS16 = 1;  // 4 strings per wave in 16-lane DPP rows, LDS windows (max_cp <= 16)
 constexpr int KERNEL_ROWS64 = 2;  // 1 string per wave, 64-lane DPP (max_cp <= 64)
 
-// the unbounded pass (dpt_long.hip): strings the windowed kernels routed to the long list
-struct LongLaunch {
-    int mode;
-    const uint8_t *text;
-    const uint64_t *str_off;
-    const uint8_t *cut_mask;
-    int32_t *staging;        // the final ids (int32 vocabularies) at the string's byte offset + k
-    int16_t *staging16;      // as EncodeLaunch: the final ids go here instead when non-null
-    uint8_t *arena;          // scratch: uint4 rec[arena_cap] then int32 stg[arena_cap], per string at its
-    uint64_t arena_cap;      //   claimed offset (input bytes; 20 bytes of scratch per input byte)
-    uint64_t arena_bias;     // test-only: the arena counter starts at it (the kernel's offsets >= bias)
-    unsigned long long *arena_used;   // claimed input bytes (all long strings; > arena_cap: overflow)
-    uint64_t *counts;
-    int32_t *status;
-    int32_t *capped;
-    uint64_t *edges;
-    uint64_t *far;                    // as EncodeLaunch
-    uint64_t far_cap;
-    unsigned long long *far_count;    // pairs found (all of them; > far_cap: the host grows and reruns)
-    unsigned long long *bsum;         // nullable: per FIN_BATCH strings, the sum of their counts (EncodeLaunch::flags)
-    const uint32_t *list;
-    const uint32_t *list_count;
-    uint32_t *work_next;
-    const int2 *slots;
-    const int4 *slots4;
-    uint32_t n_slots;
-    int32_t root_base;
-    uint32_t max_tok_bytes;
-    int long_span;
-    unsigned blocks;
+inline uint32_t *retry_list_of(const EncodeLaunch &p, RetryList which) { return p.retry_list + (uint64_t)which * p.n_str; }
+
+// A/B knobs, read from the environment once per process (launch_knobs); each is off / at its default
+// when its variable is unset
+struct LaunchKnobs {
+    bool generic_ps;      // DPT_GENERIC_PS: plain PRESPLIT / ATOMS calls through the runtime-mode kernels
+    bool generic_raw;     // DPT_GENERIC_RAW: plain RAW calls through the generic 16-lane kernel (r06i: cfg2 +9 %, cfg4 +7 %)
+    bool no_solo_wave;    // DPT_NO_SOLO_WAVE: solo calls on the four-string 16-lane kernels
+    bool no_solo;         // DPT_NO_SOLO: no one-string calls at all (dpt_api.cpp)
+    bool no_mid;          // DPT_NO_MID: the 512-byte pass off
+    bool no_small_wpc;    // DPT_NO_SMALL_WPC: the small-call wave rule off (launch_tok)
+    int fb_big_per_cu;    // DPT_FB_BIG_PER_CU: 2048-byte blocks per CU of non-raw calls (3; <= 0: the small grid)
+    int waves_per_cu;     // DPT_WAVES_PER_CU: the first pass's resident waves per CU (0: by occupancy)
 };
+const LaunchKnobs &launch_knobs();
 
 hipError_t launch_encode(const EncodeLaunch &p, hipStream_t stream, hipEvent_t ev[2]);
 size_t wsl_scratch_bytes(unsigned max_blocks);
@@ -221,8 +241,6 @@ struct SpansLaunch {
 };
 hipError_t launch_spans(const SpansLaunch &p, hipStream_t stream);
 hipError_t kernel_init();
-int small_window_bytes();
-int big_window_bytes();
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

@@ -904,7 +904,7 @@ constexpr unsigned A_REFILL64 = 32;   // the same for the 64-lane kernels (8 / 1
 #ifndef DPT_WPC_LO      // small calls: the persistent grid's fewest resident waves per CU (launch_tok)
 #define DPT_WPC_LO 20
 #endif
-#ifndef DPT_WPC_GRAN    // LDS allocation granule (bytes) that caps the resident waves per CU (resident_per_cu)
+#ifndef DPT_WPC_GRAN    // LDS allocation granule (bytes) that caps the resident waves per CU (launch_tok)
 #define DPT_WPC_GRAN 512
 #endif
 #ifndef DPT_PLAIN_RAW   // A/B knob: the RAW kernels without the edges / uncapped / len_only loop versions too
@@ -938,30 +938,20 @@ __device__ __forceinline__ TrieView tv_of(ConstKernArgs *kp) {
 // (the 16-lane instantiations: the 64-lane ones do not spill, and measured 1.7 % slower with it)
 #define KREFRESH() do { if constexpr (G == 16) asm volatile("" : "+s"(kp)); } while (0)
 
-// Counter block (EncodeLaunch::retry_count, CTR_ALLOC_BYTES; zeroed once at allocation, then reset for
-// the next call by the batch scan or the finish pass -- or, in a one-string host-path call, by the lone
-// wave of the first pass): uint32 [0] retry count, [1] 2048-byte blocks done (fallback_kernel), [2]
-// 2048-byte pass work, [3] long count, [4] long work, [5] the 512-byte pass's work (mid_kernel), [6]
-// fallback_kernel's block ticket, [7] the 2048-byte pass's list count when the 512-byte pass ran; uint64 [4] (byte
-// 32) the unbounded pass's claimed bytes, [5] (byte 40) the last call's claimed bytes
-// (dpt_ctx_long_need), [6] (byte 48) far edge pairs found, [7] (byte 56) the last call's far edge pairs
-// (dpt_dp_host_far); from byte PART_CTR_OFFSET the first pass's partition counters and their used-up
-// mask (dpt_internal.h).
-constexpr unsigned CTR_ARENA64 = 4, CTR_LASTNEED64 = 5, CTR_FAR64 = 6, CTR_LASTFAR64 = 7;
-
-// Reset the counter block for the next call (the claimed arena bytes and far pairs stay readable as
-// the call's "last need" / "last far").
-// snap (nullable): the block's first 64 bytes as the host reads them after the call (the host path's
-// one device-to-host copy carries them, instead of a copy of the counter block of its own)
+// Reset the counter block (CounterBlock, then the partition counters: dpt_internal.h) for the next call
+// (the claimed arena bytes and far pairs stay readable as the call's "last need" / "last far").
+// snap (nullable): the CounterBlock as the host reads it after the call (the host path's one
+// device-to-host copy carries it, instead of a copy of the counter block of its own)
 __device__ __forceinline__ void reset_counters(uint32_t *ctr, uint64_t *snap = nullptr) {
     uint64_t *c64 = reinterpret_cast<uint64_t *>(ctr);
-    c64[CTR_LASTNEED64] = c64[CTR_ARENA64];
-    c64[CTR_ARENA64] = 0;
-    c64[CTR_LASTFAR64] = c64[CTR_FAR64];
-    c64[CTR_FAR64] = 0;
+    constexpr unsigned ARENA = offsetof(CounterBlock, arena_used) / 8, FAR = offsetof(CounterBlock, far_pairs) / 8;
+    c64[offsetof(CounterBlock, last_need) / 8] = c64[ARENA];
+    c64[ARENA] = 0;
+    c64[offsetof(CounterBlock, last_far) / 8] = c64[FAR];
+    c64[FAR] = 0;
     if (snap)
-        for (unsigned q = 0; q < 8; q++) snap[q] = c64[q];
-    ctr[0] = 0; ctr[1] = 0; ctr[2] = 0; ctr[3] = 0; ctr[4] = 0; ctr[5] = 0; ctr[6] = 0; ctr[7] = 0;
+        for (unsigned q = 0; q < sizeof(CounterBlock) / 8; q++) snap[q] = c64[q];
+    for (unsigned q = 0; q < offsetof(CounterBlock, arena_used) / 4; q++) ctr[q] = 0;   // the uint32 counters
     uint32_t *pc = ctr + PART_CTR_OFFSET / 4;
     for (unsigned q = 0; q <= NPART; q++) pc[q * PART_STRIDE] = 0;   // the partition counters and the mask
 }
@@ -3342,10 +3332,6 @@ __global__ void __launch_bounds__(HIST_THREADS) hist_kernel(const uint64_t *__re
 
 // ------------------------------------------------------------------ the fallback passes in one launch
 
-constexpr int SMALL_CH = 256;   // the first pass's window
-constexpr int MID_CH = 512;     // the 512-byte pass's (PRESPLIT / ATOMS calls of 16-lane vocabularies)
-constexpr int BIG_CH = 2048;    // the 2048-byte pass's
-
 // The 2048-byte pass and the unbounded pass as ONE launch (they used to be two, ~5 us each on every call
 // although their lists are usually empty).  Each block takes a ticket: the first n_big tickets run the
 // 2048-byte pass (tokenize_body), the others the unbounded pass (lng::long_body) once every 2048-byte
@@ -3356,7 +3342,7 @@ constexpr int BIG_CH = 2048;    // the 2048-byte pass's
 struct FallbackArgs {
     KernArgs k;              // first: tokenize_body reads it through the kernarg segment pointer
     lng::Args l;
-    uint32_t *ticket, *big_done;   // counter block uint32 [6] / [1] (reset_counters zeroes them)
+    uint32_t *ticket, *big_done;   // CounterBlock's (reset_counters zeroes them)
     unsigned n_big;
 };
 
@@ -3415,39 +3401,219 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) mi
 }
 
 constexpr int MAX_DEVICES = 64;
-// Resident waves per CU for an instantiation (LDS / VGPR limited); DPT_WAVES_PER_CU overrides.
-template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
-static unsigned resident_per_cu() {
+
+const LaunchKnobs &launch_knobs() {
+    static const LaunchKnobs knobs = [] {
+        LaunchKnobs k;
+        k.generic_ps = getenv("DPT_GENERIC_PS") != nullptr;
+        k.generic_raw = getenv("DPT_GENERIC_RAW") != nullptr;
+        k.no_solo_wave = getenv("DPT_NO_SOLO_WAVE") != nullptr;
+        k.no_solo = getenv("DPT_NO_SOLO") != nullptr;
+        k.no_mid = getenv("DPT_NO_MID") != nullptr;
+        k.no_small_wpc = getenv("DPT_NO_SMALL_WPC") != nullptr;
+        const char *fb = getenv("DPT_FB_BIG_PER_CU"), *wpc = getenv("DPT_WAVES_PER_CU");
+        k.fb_big_per_cu = fb ? atoi(fb) : 3;
+        k.waves_per_cu = wpc ? atoi(wpc) : 0;
+        return k;
+    }();
+    return knobs;
+}
+
+// ------------------------------------------------------------------ the launch plan
+// Which kernels a call launches, as plain values: plan_encode decides, the stages of launch_encode below
+// fill the arguments and launch.  tests/test_launch_plan.py asserts the table through
+// dpt_debug_launch_plan.
+
+// The template arguments of the chosen instantiations (their meaning: tokenize_body), g: 16 or 64 lanes
+struct TokChoice { int g; bool wide; int sw; bool raw, solo; int mc; };   // tokenize_kernel<SMALL_CH, g, false, wide, sw, raw, solo, mc>
+struct MidChoice { int sw; bool wide; int mc; };                          // mid_kernel<sw, wide, mc>
+struct FallbackChoice { bool wide, raw; };                                // fallback_kernel<wide, raw>
+// What follows the tokenize passes: memsets only (no strings); nothing (the first pass's lone wave wrote
+// the CSR arrays and reset the counters); reset_kernel (dpt_encode_padded: the ids are in place);
+// batch_scan_kernel + finish_kernel; finish_kernel summing the batch sums itself (2..FIN_FOLD_MAX batches);
+// finish_kernel alone (<= FIN_BATCH strings).  (The values are dpt_debug_launch_plan's, include/dpt.h.)
+enum Tail { TAIL_EMPTY = 0, TAIL_SOLO = 1, TAIL_RESET = 2, TAIL_SCAN = 3, TAIL_FOLD = 4, TAIL_ONE_BATCH = 5 };
+enum HistZero { HZ_NONE = 0, HZ_BIG_PASS = 1, HZ_SCAN = 2, HZ_MEMSET = 3 };   // who zeroes an overwritten histogram
+
+struct PlanKey {   // all the plan depends on: EncodeLaunch's fields of these names (pointers as "given"), and
+    int variant, mode;
+    bool st16, edges, solo, padded, no_fallback;
+    bool profiled;   // dpt_ctx_profile: the first and the fallback launch carry the timestamps
+    uint64_t n_str;
+    bool hist, hist_overwrite;
+    uint32_t hist_bins;
+};
+struct LaunchPlan {
+    TokChoice first;
+    bool mid, fallback;      // the 512-byte pass / the 2048-byte + unbounded launch run ...
+    MidChoice midk;
+    FallbackChoice fb;
+    RetryList big_list;      // ... the 2048-byte pass over this list
+    Tail tail;
+    int fin_width;           // finish_kernel<int16_t> (16) or <int32_t> (32)
+    bool hist_fold;          // the finish pass adds the call's histogram
+    bool hist_store;         // ... by plain stores (one batch, overwrite: nobody zeroes)
+    HistZero hist_zero;      // HZ_BIG_PASS: EncodeArgs::hist_zero of the 2048-byte pass
+    bool hist_separate;      // more than FIN_MAX_BINS bins (or fewer than 2): launch_histogram after the finish pass
+};
+
+// Pure: no HIP call, nothing read but the arguments.
+static LaunchPlan plan_encode(const PlanKey &k, const LaunchKnobs &kn) {
+    LaunchPlan pl = {};
+    const int m = k.mode & DPT_MODE_MASK;
+    const bool wide = m == DPT_MODE_ATOMS;   // atoms of up to 8 bytes
+    const bool raw = m == DPT_MODE_RAW, presplit = m == DPT_MODE_PRESPLIT;
+    const bool rows16 = k.variant == KERNEL_ROWS16;
+    const bool hist = k.hist && !k.padded;
+    const bool fold_hist = hist && k.hist_bins >= 2 && k.hist_bins <= FIN_MAX_BINS;
+    pl.big_list = LIST_BIG;
+    if (k.n_str == 0) {   // no kernel runs; the histogram of no strings
+        pl.tail = TAIL_EMPTY;
+        pl.hist_zero = k.hist && k.hist_overwrite ? HZ_MEMSET : HZ_NONE;
+        return pl;
+    }
+    const bool solo = k.solo && k.n_str == 1 && !k.padded;
+    const int sw = k.st16 && !solo ? 1 : 2;   // (a solo call stages nothing: its ids go to their place as int32)
+    // PRESPLIT (llama mode) and ATOMS run instantiations with the mode a compile-time constant (MC)
+    // ... and, like the RAW ones, only for calls without edges, the uncapped DP or len_only (PLAIN)
+    const bool plain = !k.edges && (k.mode & (DPT_FLAG_UNCAPPED | DPT_FLAG_LEN_ONLY)) == 0;
+    const bool spec = plain && !kn.generic_ps;
+    const int mc = !spec ? -1 : wide ? DPT_MODE_ATOMS : presplit ? DPT_MODE_PRESPLIT : -1;
+    if (rows16) {   // the hot kernel gets the staged id width as a template constant
+        // the one-string kernel: lane-mode B and its C1 walks over the whole wave (forward_lanes, SOLO)
+        if (solo && !wide && !kn.no_solo_wave) pl.first = TokChoice{16, false, 2, raw, true, -1};
+        else if (wide) pl.first = TokChoice{16, true, sw, false, false, mc};
+        else if (raw && plain && !kn.generic_raw) pl.first = TokChoice{16, false, sw, true, false, -1};
+        else pl.first = TokChoice{16, false, sw, false, false, mc};
+    } else {
+        pl.first = wide ? TokChoice{64, true, 0, false, false, mc} : TokChoice{64, false, 0, raw && plain, false, -1};
+    }
+    if (solo) {   // the lone wave does the rest
+        pl.tail = TAIL_SOLO;
+        return pl;
+    }
+    // the 512-byte pass over the retry list; the strings it cannot hold go on to the 2048-byte pass
+    // (wide <=> ATOMS mode; the mode-constant instantiations for PLAIN calls unless DPT_GENERIC_PS)
+    pl.mid = !raw && rows16 && !kn.no_mid;
+    if (pl.mid) {
+        pl.midk = MidChoice{sw, wide, mc};
+        pl.big_list = LIST_BIG_AFTER_MID;
+    }
+    const uint64_t nb = (k.n_str + FIN_BATCH - 1) / FIN_BATCH;
+    const bool fold = fin_fold(k.n_str);
+    if (fold_hist && k.hist_overwrite)   // (the finish pass adds to it, or one batch's stores it)
+        pl.hist_zero = fold ? HZ_BIG_PASS : nb > 1 ? HZ_SCAN : HZ_NONE;
+    // (skipped when the host showed no string needs them -- small host-path calls: two dispatches
+    // of a per-string dp_tokenize call -- unless they time the call or zero its histogram)
+    pl.fallback = !k.no_fallback || k.profiled || pl.hist_zero == HZ_BIG_PASS;
+    pl.fb = FallbackChoice{wide, raw && !wide};
+    if (k.padded) {   // dpt_encode_padded: the ids are in place; only the counters need their reset
+        pl.tail = TAIL_RESET;
+        return pl;
+    }
+    // batch prefixes (and the counter block's reset), then the CSR pass; a one-batch call (<= 256
+    // strings: the drop-in's per-string calls) needs no prefix, and its finish block does the rest.
+    pl.tail = fold ? TAIL_FOLD : nb > 1 ? TAIL_SCAN : TAIL_ONE_BATCH;
+    pl.fin_width = k.st16 ? 16 : 32;
+    pl.hist_fold = fold_hist;
+    pl.hist_store = fold_hist && k.hist_overwrite && nb <= 1;
+    pl.hist_separate = hist && !fold_hist;   // too many bins for the finish pass's LDS: the separate pass
+    if (pl.hist_separate && k.hist_overwrite) pl.hist_zero = HZ_MEMSET;
+    return pl;
+}
+
+// ------------------------------------------------------------------ choice -> instantiation
+// The only places that name an instantiation of tokenize_kernel / mid_kernel / fallback_kernel (besides
+// kernel_init's list of the never-launched BIG_CH tokenize_kernels): each calls f with the chosen kernel,
+// or returns hipErrorNotSupported for a choice that is not instantiated.  (The kernels sit in the code
+// object in the order they are named here.)
+
+// an instantiation as a type: its kernel and its dynamic LDS bytes
+template <auto KERNEL, int LDS> struct Kern {
+    static constexpr auto kernel = KERNEL;
+    static constexpr int lds = LDS;
+};
+
+template <class F> static hipError_t with_first_kernel(const TokChoice &c, F &&f) {
+#define DPT_K(G, WIDE, SW, RAW, SOLO, MC)                                                          \
+    if (c.g == G && c.wide == WIDE && c.sw == SW && c.raw == RAW && c.solo == SOLO && c.mc == MC) \
+        return f(Kern<tokenize_kernel<SMALL_CH, G, false, WIDE, SW, RAW, SOLO, MC>, block_lds_bytes<SMALL_CH, G>()>{});
+    DPT_K(16, false, 2, true, true, -1)
+    DPT_K(16, false, 2, false, true, -1)
+    DPT_K(16, true, 1, false, false, -1)
+    DPT_K(16, true, 2, false, false, -1)
+    DPT_K(16, true, 1, false, false, DPT_MODE_ATOMS)
+    DPT_K(16, true, 2, false, false, DPT_MODE_ATOMS)
+    DPT_K(16, false, 1, true, false, -1)
+    DPT_K(16, false, 2, true, false, -1)
+    DPT_K(16, false, 1, false, false, DPT_MODE_PRESPLIT)
+    DPT_K(16, false, 2, false, false, DPT_MODE_PRESPLIT)
+    DPT_K(16, false, 1, false, false, -1)
+    DPT_K(16, false, 2, false, false, -1)
+#if DPT_STOP != 3   // (this diagnostic build crashes ROCm 7.2's register allocator on the 64-lane first pass)
+    DPT_K(64, true, 0, false, false, DPT_MODE_ATOMS)
+    DPT_K(64, true, 0, false, false, -1)
+    DPT_K(64, false, 0, true, false, -1)
+    DPT_K(64, false, 0, false, false, -1)
+#endif
+#undef DPT_K
+    return hipErrorNotSupported;
+}
+
+template <class F> static hipError_t with_mid_kernel(const MidChoice &c, F &&f) {
+#define DPT_K(SW, WIDE, MC)                           \
+    if (c.sw == SW && c.wide == WIDE && c.mc == MC) \
+        return f(Kern<mid_kernel<SW, WIDE, MC>, block_lds_bytes<MID_CH, 16>()>{});
+    DPT_K(1, true, -1)
+    DPT_K(1, false, -1)
+    DPT_K(2, true, -1)
+    DPT_K(2, false, -1)
+    DPT_K(1, false, DPT_MODE_PRESPLIT)
+    DPT_K(1, true, DPT_MODE_ATOMS)
+    DPT_K(2, false, DPT_MODE_PRESPLIT)
+    DPT_K(2, true, DPT_MODE_ATOMS)
+#undef DPT_K
+    return hipErrorNotSupported;
+}
+
+template <class F> static hipError_t with_fallback_kernel(const FallbackChoice &c, F &&f) {
+    if (c.wide && !c.raw) return f(fallback_kernel<true, false>);
+    if (!c.wide && c.raw) return f(fallback_kernel<false, true>);
+    if (!c.wide && !c.raw) return f(fallback_kernel<false, false>);
+    return hipErrorNotSupported;
+}
+constexpr FallbackChoice FALLBACK_CHOICES[] = {{true, false}, {false, true}, {false, false}};
+
+// ------------------------------------------------------------------ the stages of launch_encode
+
+// Resident blocks (one wave each) per CU of an instantiation by the occupancy API (LDS / VGPR limited),
+// cached per instantiation and device; dflt when the API fails.
+template <class K> static unsigned resident_per_cu(unsigned dflt) {
     static unsigned cached[MAX_DEVICES] = {};   // per device: a process may drive several
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
     if (cached[dev]) return cached[dev];
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, tokenize_kernel<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>, 64, block_lds_bytes<CH, G>()) != hipSuccess || nb <= 0)
-        nb = 8;
-    {   // the residency by LDS at its 512-byte allocation granule: the occupancy API counts 22 blocks of
-        // 7 424 B per CU, the timeline shows 21 resident and the 22nd starting only when another exits
-        // (profiles/r06_ab.log r06b; 21 against 22 at 175k / 250k: +0.9 %, r06o)
-        constexpr int g = DPT_WPC_GRAN;
-        const int fit = (160 * 1024) / ((block_lds_bytes<CH, G>() + g - 1) / g * g);
-        if (fit < nb) nb = fit;
-    }
-    if (const char *e = getenv("DPT_WAVES_PER_CU")) {
-        const int v = atoi(e);
-        if (v > 0) nb = v;
-    }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, K::kernel, 64, K::lds) != hipSuccess || nb <= 0) nb = (int)dflt;
     cached[dev] = (unsigned)nb;
     return cached[dev];
 }
 
-// Persistent grid: every resident wave pulls strings from the work counter until it runs dry.
-template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
-static void launch_tok(const EncodeArgs &a, const TrieView &tv, uint64_t n_units, unsigned n_cu, hipStream_t stream,
-                       hipEvent_t ev_start = nullptr) {
-    constexpr int lds = block_lds_bytes<CH, G>();
-    uint64_t wpc = resident_per_cu<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>();
-    static const bool small_rule = getenv("DPT_NO_SMALL_WPC") == nullptr;   // (A/B: the rule below off)
-    if (G == 16 && !BIG && small_rule) {
+// The first pass, a persistent grid: every resident wave pulls strings from the work counter until it runs dry.
+template <class K>
+static hipError_t launch_tok(K, bool g16, const EncodeArgs &a, const TrieView &tv, uint64_t n_units, unsigned n_cu,
+                             hipStream_t stream, hipEvent_t ev_start) {
+    const LaunchKnobs &kn = launch_knobs();
+    uint64_t wpc = resident_per_cu<K>(8);
+    {   // the residency by LDS at its 512-byte allocation granule: the occupancy API counts 22 blocks of
+        // 7 424 B per CU, the timeline shows 21 resident and the 22nd starting only when another exits
+        // (profiles/r06_ab.log r06b; 21 against 22 at 175k / 250k: +0.9 %, r06o)
+        constexpr int g = DPT_WPC_GRAN;
+        constexpr uint64_t fit = (160 * 1024) / ((K::lds + g - 1) / g * g);
+        if (fit < wpc) wpc = fit;
+    }
+    if (kn.waves_per_cu > 0) wpc = (uint64_t)kn.waves_per_cu;
+    if (g16 && !kn.no_small_wpc) {
         // small calls: no more resident waves than give every slot ~7 strings (rounds of 4 strings per
         // wave; a wave's last round is the tail): 125k strings run 3 % faster at 18 waves per CU than
         // at the occupancy limit of 22, 250k and more are fastest at 22 (profiles/r02_ab_issue_model.log)
@@ -3471,230 +3637,185 @@ static void launch_tok(const EncodeArgs &a, const TrieView &tv, uint64_t n_units
     if (blocks > (uint64_t)n_cu * 64u) blocks = (uint64_t)n_cu * 64u;   // the scratch is sized for 64 per CU
     if (blocks > n_units) blocks = n_units ? n_units : 1;
     if (ev_start)   // the start timestamp rides on the dispatch (a separate hipEventRecord left a ~6 us bubble)
-        hipExtLaunchKernelGGL((tokenize_kernel<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>), dim3((unsigned)blocks), dim3(64), lds, stream,
-                              ev_start, nullptr, 0, KernArgs{a, tv});
+        hipExtLaunchKernelGGL(K::kernel, dim3((unsigned)blocks), dim3(64), K::lds, stream, ev_start, nullptr, 0, KernArgs{a, tv});
     else
-        hipLaunchKernelGGL((tokenize_kernel<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>), dim3((unsigned)blocks), dim3(64), lds, stream, KernArgs{a, tv});
+        hipLaunchKernelGGL(K::kernel, dim3((unsigned)blocks), dim3(64), K::lds, stream, KernArgs{a, tv});
+    return hipSuccess;
 }
 
-hipError_t launch_encode(const EncodeLaunch &p, hipStream_t stream, hipEvent_t ev[2]) {
+// the first pass's arguments (the later passes' are copies with their own lists and counters)
+static EncodeArgs first_pass_args(const EncodeLaunch &p, bool solo) {
     EncodeArgs a;
     a.text = p.text; a.str_off = p.str_off; a.cut_mask = p.cut_mask; a.n_str = p.n_str;
     a.staging = p.staging; a.staging16 = p.staging16; a.counts = p.counts; a.bsum = p.padded ? nullptr : p.flags; a.status = p.status; a.capped = p.capped;
-    a.retry_list = p.retry_list; a.retry_count = p.retry_count; a.work_list = nullptr; a.work_count = nullptr;
-    a.long_list = p.retry_list + p.n_str; a.long_count = p.retry_count + 3;
+    a.retry_list = retry_list_of(p, LIST_BIG); a.retry_count = &p.ctr->retry_count; a.work_list = nullptr; a.work_count = nullptr;
+    a.long_list = retry_list_of(p, LIST_LONG); a.long_count = &p.ctr->long_count;
     a.mode = p.mode;
     a.edges = p.edges;
-    a.work_next = p.retry_count + 1;
-    a.part_ctr = p.retry_count + PART_CTR_OFFSET / 4;
+    a.work_next = &p.ctr->big_done;   // (not read by the first pass: its work counters are part_ctr's)
+    a.part_ctr = ctr_words(p.ctr) + PART_CTR_OFFSET / 4;
     a.wsl_scratch = p.wsl_scratch;
     a.pend = p.pend; a.ws_node = p.ws_node; a.ws_base = p.ws_base; a.ws_id = p.ws_id;
     a.long_span = p.long_span;
     a.hist_zero = nullptr; a.n_hist = 0;
     a.id_off = p.id_off; a.ids = p.ids;
-    a.solo = p.solo ? 1 : 0; a.ctr_snap = p.ctr_snap;
-    const bool solo = p.solo && p.n_str == 1 && !p.padded;
-    int16_t *const st16 = solo ? nullptr : p.staging16;   // (the 16-lane launch below picks the width by it)
-    if (solo) {
+    a.solo = solo ? 1 : 0; a.ctr_snap = p.ctr_snap;
+    if (solo) {   // the lone wave writes the CSR arrays itself
         a.staging = p.ids; a.staging16 = nullptr; a.counts = p.id_off + 1; a.bsum = nullptr;
-    } else {
-        a.solo = 0;
     }
-    TrieView tv{p.slots, p.slot_ids, p.slots4, p.root_base, p.n_slots, p.pair16};
-    const bool wide = (p.mode & DPT_MODE_MASK) == DPT_MODE_ATOMS;   // atoms of up to 8 bytes
-    const bool raw = (p.mode & DPT_MODE_MASK) == DPT_MODE_RAW;
+    return a;
+}
 
-    if (p.n_str == 0) {
-        // no finish kernel runs: id_off[0] = 0, and the call's claimed arena bytes ("last need") and
-        // far edge pairs are 0 (bytes 40..63 of the counter block; the running counters are 0 already)
-        if (p.id_off) {   // (dpt_encode_padded has no offsets)
-            const hipError_t e0 = hipMemsetAsync(p.id_off, 0, sizeof(uint64_t), stream);
-            if (e0 != hipSuccess) return e0;
-        }
-        if (p.hist && p.hist_overwrite) {   // the histogram of no strings
-            const hipError_t e1 = hipMemsetAsync(p.hist, 0, ((size_t)p.hist_bins + 8u) * sizeof(int64_t), stream);
-            if (e1 != hipSuccess) return e1;
-        }
-        return hipMemsetAsync(reinterpret_cast<uint64_t *>(p.retry_count) + CTR_LASTNEED64, 0, 3 * sizeof(uint64_t), stream);
+static hipError_t launch_empty(const EncodeLaunch &p, const LaunchPlan &plan, hipStream_t stream) {
+    // no finish kernel runs: id_off[0] = 0, and the call's claimed arena bytes ("last need") and
+    // far edge pairs are 0 (the running counters are 0 already)
+    if (p.id_off) {   // (dpt_encode_padded has no offsets)
+        const hipError_t e0 = hipMemsetAsync(p.id_off, 0, sizeof(uint64_t), stream);
+        if (e0 != hipSuccess) return e0;
     }
-    // profiling (dpt_ctx_profile): the first pass's dispatch records ev[0], the unbounded pass's ev[1]
-    hipEvent_t e0 = ev ? ev[0] : nullptr;
-    // PRESPLIT (llama mode) and ATOMS run instantiations with the mode a compile-time constant (MC)
-    static const bool generic_ps = getenv("DPT_GENERIC_PS") != nullptr;   // (A/B: the runtime-mode kernels)
-    const bool presplit = (p.mode & DPT_MODE_MASK) == DPT_MODE_PRESPLIT;
-    // ... and, like the RAW ones, only for calls without edges, the uncapped DP or len_only (PLAIN)
-    const bool plain = p.edges == nullptr && (p.mode & (DPT_FLAG_UNCAPPED | DPT_FLAG_LEN_ONLY)) == 0;
-    const bool spec = plain && !generic_ps;
-    if (p.n_str > 0) {
-        {
-            const unsigned n_cu = p.max_blocks / 64;
-            // A/B knob (diagnostic): raw mode through the generic 16-lane kernel (r06i: cfg2 +9 %, cfg4 +7 %)
-            static const bool generic_raw = getenv("DPT_GENERIC_RAW") != nullptr;
-            if (p.variant == KERNEL_ROWS16) {
-                // the hot kernel gets the staged id width as a template constant
-                const uint64_t nu = (p.n_str + 3) / 4;
-                static const bool solo_wave = getenv("DPT_NO_SOLO_WAVE") == nullptr;   // (A/B: solo calls on 16-lane rows)
-                if (solo && !wide && solo_wave) {
-                    // the one-string kernel: lane-mode B and its C1 walks over the whole wave (forward_lanes, SOLO)
-                    if (raw) launch_tok<SMALL_CH, 16, false, false, 2, true, true>(a, tv, 1, n_cu, stream, e0);
-                    else launch_tok<SMALL_CH, 16, false, false, 2, false, true>(a, tv, 1, n_cu, stream, e0);
-                } else if (wide) {
-                    if (!spec) {
-                        if (st16) launch_tok<SMALL_CH, 16, false, true, 1>(a, tv, nu, n_cu, stream, e0);
-                        else launch_tok<SMALL_CH, 16, false, true, 2>(a, tv, nu, n_cu, stream, e0);
-                    } else {
-                        if (st16) launch_tok<SMALL_CH, 16, false, true, 1, false, false, DPT_MODE_ATOMS>(a, tv, nu, n_cu, stream, e0);
-                        else launch_tok<SMALL_CH, 16, false, true, 2, false, false, DPT_MODE_ATOMS>(a, tv, nu, n_cu, stream, e0);
-                    }
-                } else if (raw && plain && !generic_raw) {
-                    if (st16) launch_tok<SMALL_CH, 16, false, false, 1, true>(a, tv, nu, n_cu, stream, e0);
-                    else launch_tok<SMALL_CH, 16, false, false, 2, true>(a, tv, nu, n_cu, stream, e0);
-                } else if (presplit && spec) {
-                    if (st16) launch_tok<SMALL_CH, 16, false, false, 1, false, false, DPT_MODE_PRESPLIT>(a, tv, nu, n_cu, stream, e0);
-                    else launch_tok<SMALL_CH, 16, false, false, 2, false, false, DPT_MODE_PRESPLIT>(a, tv, nu, n_cu, stream, e0);
-                } else {
-                    if (st16) launch_tok<SMALL_CH, 16, false, false, 1>(a, tv, nu, n_cu, stream, e0);
-                    else launch_tok<SMALL_CH, 16, false, false, 2>(a, tv, nu, n_cu, stream, e0);
-                }
-            } else {
-#if DPT_STOP == 3   // (this diagnostic build crashes ROCm 7.2's register allocator on the 64-lane first pass)
-                return hipErrorNotSupported;
-#else
-                if (wide && spec) launch_tok<SMALL_CH, 64, false, true, 0, false, false, DPT_MODE_ATOMS>(a, tv, p.n_str, n_cu, stream, e0);
-                else if (wide) launch_tok<SMALL_CH, 64, false, true>(a, tv, p.n_str, n_cu, stream, e0);
-                else if (raw && plain) launch_tok<SMALL_CH, 64, false, false, 0, true>(a, tv, p.n_str, n_cu, stream, e0);
-                else launch_tok<SMALL_CH, 64, false, false>(a, tv, p.n_str, n_cu, stream, e0);
-#endif
-            }
-        }
-        if (solo) return hipGetLastError();   // the lone wave did the rest
-        // second pass over the strings whose single word (or expansion) did not fit the small window
-        EncodeArgs b = a;
-        b.work_list = p.retry_list; b.work_count = p.retry_count;
-        b.work_next = p.retry_count + 2;
-        static const bool mid_on = getenv("DPT_NO_MID") == nullptr;   // (A/B: the 512-byte pass off)
-        if (!raw && p.variant == KERNEL_ROWS16 && mid_on) {
-            // the 512-byte pass over the retry list; the strings it cannot hold go on to the 2048-byte pass
-            EncodeArgs m = a;
-            m.work_list = p.retry_list; m.work_count = p.retry_count; m.work_next = p.retry_count + 5;
-            m.retry_list = p.retry_list + 2 * p.n_str; m.retry_count = p.retry_count + 7;
-            m.hist_zero = nullptr; m.n_hist = 0;
-            static unsigned mid_per_cu[MAX_DEVICES] = {};
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
-            if (!mid_per_cu[dev]) {
-                int nb = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, st16 ? (wide ? mid_kernel<1, true> : mid_kernel<1, false>)
-                                                                            : (wide ? mid_kernel<2, true> : mid_kernel<2, false>),
-                                                                 64, block_lds_bytes<MID_CH, 16>()) != hipSuccess || nb <= 0)
-                    nb = 4;
-                mid_per_cu[dev] = (unsigned)nb;
-            }
-            uint64_t mb = (uint64_t)(p.max_blocks / 64) * mid_per_cu[dev];
-            mb = mb < p.n_str ? mb : p.n_str;
-            constexpr int mlds = block_lds_bytes<MID_CH, 16>();
-            // (wide <=> ATOMS mode; the mode-constant instantiations for PLAIN calls unless DPT_GENERIC_PS)
-            auto mk = !spec ? (st16 ? (wide ? mid_kernel<1, true> : mid_kernel<1, false>) : (wide ? mid_kernel<2, true> : mid_kernel<2, false>))
-                    : st16 ? (wide ? mid_kernel<1, true, DPT_MODE_ATOMS> : presplit ? mid_kernel<1, false, DPT_MODE_PRESPLIT> : mid_kernel<1, false>)
-                           : (wide ? mid_kernel<2, true, DPT_MODE_ATOMS> : presplit ? mid_kernel<2, false, DPT_MODE_PRESPLIT> : mid_kernel<2, false>);
-            hipLaunchKernelGGL(mk, dim3((unsigned)(mb ? mb : 1)), dim3(64), mlds, stream, KernArgs{m, tv});
-            b.work_list = m.retry_list; b.work_count = m.retry_count;
-        }
-        if (!p.padded && fin_fold(p.n_str) && p.hist && p.hist_overwrite && p.hist_bins >= 2 &&
-            p.hist_bins <= FIN_MAX_BINS) {
-            b.hist_zero = reinterpret_cast<unsigned long long *>(p.hist);   // (the finish pass adds to it)
-            b.n_hist = p.hist_bins + 8u;
-        }
-        // the fallback passes' grids: 1/FALLBACK_DIV of a full one (usually they find no work; 16 / 64
-        // within noise, r03ah)
-        constexpr unsigned FALLBACK_DIV = 4;
-        // (n_units caps the grid: one block per FALLBACK_DIV CUs; the retry list is rare and short)
-        uint64_t fb_units = (uint64_t)(p.max_blocks / 64) / FALLBACK_DIV;
-        // PRESPLIT / ATOMS text carries its word markers as bytes ('\u2581' is 3 of them), so a word the
-        // 256-byte window cannot hold is not rare there (cfg2p: the 6.8 % of 256-character strings without a
-        // space are one 257-code-point word after the dummy prefix): a full grid of 2048-byte blocks (three
-        // per CU: LDS) takes them, instead of one block per four CUs (DPT_FB_BIG_PER_CU overrides)
-        {
-            static const int per_cu = getenv("DPT_FB_BIG_PER_CU") ? atoi(getenv("DPT_FB_BIG_PER_CU")) : 3;
-            if (!raw && per_cu > 0) fb_units = (uint64_t)(p.max_blocks / 64) * (uint64_t)per_cu;
-        }
-        fb_units = fb_units < p.n_str ? fb_units : p.n_str;
-        // (skipped when the host showed no string needs them -- small host-path calls: two dispatches
-        // of a per-string dp_tokenize call -- unless they time the call or zero its histogram)
-        const bool fallback = !p.no_fallback || ev || b.hist_zero;
-        // the unbounded pass over whatever the windowed passes could not hold (usually nothing:
-        // its waves read a zero count and exit)
-        LongLaunch l;
-        l.mode = p.mode; l.text = p.text; l.str_off = p.str_off; l.cut_mask = p.cut_mask;
-        l.staging = p.staging; l.staging16 = p.staging16; l.counts = p.counts; l.bsum = p.padded ? nullptr : p.flags; l.status = p.status; l.capped = p.capped;
-        l.arena = p.arena; l.arena_cap = p.arena_cap; l.arena_bias = p.counter_bias;
-        l.arena_used = reinterpret_cast<unsigned long long *>(p.retry_count + 8);
-        l.edges = p.edges; l.far = p.far; l.far_cap = p.far_cap;
-        l.far_count = reinterpret_cast<unsigned long long *>(p.retry_count) + CTR_FAR64;
-        l.list = a.long_list; l.list_count = a.long_count; l.work_next = p.retry_count + 4;
-        l.slots = p.slots; l.slots4 = p.slots4; l.n_slots = p.n_slots; l.root_base = p.root_base;
-        l.max_tok_bytes = p.max_tok_bytes; l.long_span = p.long_span;
-        const uint64_t lcap = (uint64_t)(p.max_blocks / 16) / FALLBACK_DIV;
-        const uint64_t lb = p.n_str < lcap ? p.n_str : lcap;
-        l.blocks = (unsigned)(lb ? lb : 1);
-        if (fallback) {   // both passes, one launch (fallback_kernel); the end timestamp rides on it
-            FallbackArgs fa;
-            fa.k = KernArgs{b, tv};
-            fa.l = lng::long_args(l);
-            fa.ticket = p.retry_count + 6;
-            fa.big_done = p.retry_count + 1;
-            fa.n_big = (unsigned)(fb_units ? fb_units : 1);
-            const dim3 grid(fa.n_big + l.blocks);
-            constexpr int lds = block_lds_bytes<BIG_CH, 64>();
-            auto go = [&](auto kern) {
-                if (ev) hipExtLaunchKernelGGL(kern, grid, dim3(64), lds, stream, nullptr, ev[1], 0, fa);
-                else hipLaunchKernelGGL(kern, grid, dim3(64), lds, stream, fa);
-            };
-            if (wide) go(fallback_kernel<true, false>);
-            else if (raw) go(fallback_kernel<false, true>);
-            else go(fallback_kernel<false, false>);
-        }
+    if (plan.hist_zero == HZ_MEMSET) {
+        const hipError_t e1 = hipMemsetAsync(p.hist, 0, ((size_t)p.hist_bins + 8u) * sizeof(int64_t), stream);
+        if (e1 != hipSuccess) return e1;
     }
-    if (p.padded) {   // dpt_encode_padded: the ids are in place; only the counters need their reset
-        hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(64), 0, stream, p.retry_count);
+    return hipMemsetAsync(&p.ctr->last_need, 0, sizeof(CounterBlock) - offsetof(CounterBlock, last_need), stream);
+}
+
+// the 512-byte pass over the first pass's list (LIST_BIG); what it cannot hold goes to LIST_BIG_AFTER_MID
+static hipError_t launch_mid(const EncodeLaunch &p, const LaunchPlan &plan, const EncodeArgs &a, const TrieView &tv,
+                             hipStream_t stream) {
+    EncodeArgs m = a;
+    m.work_list = retry_list_of(p, LIST_BIG); m.work_count = &p.ctr->retry_count; m.work_next = &p.ctr->mid_work;
+    m.retry_list = retry_list_of(p, LIST_BIG_AFTER_MID); m.retry_count = &p.ctr->mid_retry_count;
+    m.hist_zero = nullptr; m.n_hist = 0;
+    return with_mid_kernel(plan.midk, [&](auto k) {
+        using K = decltype(k);
+        uint64_t mb = (uint64_t)(p.max_blocks / 64) * resident_per_cu<K>(4);
+        mb = mb < p.n_str ? mb : p.n_str;
+        hipLaunchKernelGGL(K::kernel, dim3((unsigned)(mb ? mb : 1)), dim3(64), K::lds, stream, KernArgs{m, tv});
+        return hipSuccess;
+    });
+}
+
+// The 2048-byte pass over plan.big_list (second pass over the strings whose single word, or expansion,
+// did not fit the smaller windows) and the unbounded pass over whatever the windowed passes could not
+// hold (usually nothing: its waves read a zero count and exit): one launch (fallback_kernel); the end
+// timestamp rides on it
+static hipError_t launch_fallback(const EncodeLaunch &p, const LaunchPlan &plan, const EncodeArgs &a, const TrieView &tv,
+                                  hipStream_t stream, hipEvent_t ev[2]) {
+    const bool after_mid = plan.big_list == LIST_BIG_AFTER_MID;
+    EncodeArgs b = a;
+    b.work_list = retry_list_of(p, plan.big_list);
+    b.work_count = after_mid ? &p.ctr->mid_retry_count : &p.ctr->retry_count;
+    b.work_next = &p.ctr->big_work;
+    if (plan.hist_zero == HZ_BIG_PASS) {
+        b.hist_zero = reinterpret_cast<unsigned long long *>(p.hist);   // (the finish pass adds to it)
+        b.n_hist = p.hist_bins + 8u;
+    }
+    // the fallback passes' grids: 1/FALLBACK_DIV of a full one (usually they find no work; 16 / 64
+    // within noise, r03ah)
+    constexpr unsigned FALLBACK_DIV = 4;
+    // (n_units caps the grid: one block per FALLBACK_DIV CUs; the retry list is rare and short)
+    uint64_t fb_units = (uint64_t)(p.max_blocks / 64) / FALLBACK_DIV;
+    // PRESPLIT / ATOMS text carries its word markers as bytes ('▁' is 3 of them), so a word the
+    // 256-byte window cannot hold is not rare there (cfg2p: the 6.8 % of 256-character strings without a
+    // space are one 257-code-point word after the dummy prefix): a full grid of 2048-byte blocks (three
+    // per CU: LDS) takes them, instead of one block per four CUs (DPT_FB_BIG_PER_CU overrides)
+    const int per_cu = launch_knobs().fb_big_per_cu;
+    if ((p.mode & DPT_MODE_MASK) != DPT_MODE_RAW && per_cu > 0) fb_units = (uint64_t)(p.max_blocks / 64) * (uint64_t)per_cu;
+    fb_units = fb_units < p.n_str ? fb_units : p.n_str;
+    const uint64_t lcap = (uint64_t)(p.max_blocks / 16) / FALLBACK_DIV;
+    const uint64_t lb = p.n_str < lcap ? p.n_str : lcap;
+    FallbackArgs fa;
+    fa.k = KernArgs{b, tv};
+    fa.l = lng::long_args(p);
+    fa.ticket = &p.ctr->ticket;
+    fa.big_done = &p.ctr->big_done;
+    fa.n_big = (unsigned)(fb_units ? fb_units : 1);
+    const dim3 grid(fa.n_big + (unsigned)(lb ? lb : 1));
+    constexpr int lds = block_lds_bytes<BIG_CH, 64>();
+    return with_fallback_kernel(plan.fb, [&](auto kern) {
+        if (ev) hipExtLaunchKernelGGL(kern, grid, dim3(64), lds, stream, nullptr, ev[1], 0, fa);
+        else hipLaunchKernelGGL(kern, grid, dim3(64), lds, stream, fa);
+        return hipSuccess;
+    });
+}
+
+// batch prefixes, the CSR pass and the counter block's reset, as plan.tail says
+static hipError_t launch_tail(const EncodeLaunch &p, const LaunchPlan &plan, hipStream_t fs) {
+    uint32_t *const ctr = ctr_words(p.ctr);
+    if (plan.tail == TAIL_RESET) {
+        hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(64), 0, fs, ctr);
         return hipGetLastError();
     }
-    // batch prefixes (and the counter block's reset), then the CSR pass; a one-batch call (<= 256
-    // strings: the drop-in's per-string calls) needs no prefix, and its finish block does the rest.
-    hipStream_t fs = stream;
     const uint64_t nb = (p.n_str + FIN_BATCH - 1) / FIN_BATCH;
     FinishArgs f;
     f.bsum = nullptr; f.ctr = nullptr; f.fold = nullptr; f.fold_zero = nullptr; f.fold_n = 0;
     f.ctr_snap = p.ctr_snap;
-    const bool fold = fin_fold(p.n_str);
-    const bool fold_hist = p.hist && p.hist_bins >= 2 && p.hist_bins <= FIN_MAX_BINS;
-    f.hist = fold_hist ? reinterpret_cast<unsigned long long *>(p.hist) : nullptr;
+    f.hist = plan.hist_fold ? reinterpret_cast<unsigned long long *>(p.hist) : nullptr;
     f.status = p.status;
     f.n_bins = p.hist_bins;
-    f.hist_store = (fold_hist && p.hist_overwrite && nb <= 1) ? 1 : 0;
-    unsigned long long *hz = (fold_hist && p.hist_overwrite && nb > 1 && !fold) ? f.hist : nullptr;
-    if (fold) { f.fold = p.flags; f.fold_zero = p.zero_other; f.fold_n = p.zero_n; f.ctr = p.retry_count; }
-    else if (nb > 1) hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, fs, p.n_str, p.flags, p.bpre, p.retry_count,
-                                        hz, p.hist_bins + 8u, p.ctr_snap);
-    else { f.bsum = p.flags; f.ctr = p.retry_count; }
+    f.hist_store = plan.hist_store ? 1 : 0;
+    if (plan.tail == TAIL_FOLD) { f.fold = p.flags; f.fold_zero = p.zero_other; f.fold_n = p.zero_n; f.ctr = ctr; }
+    else if (plan.tail == TAIL_SCAN)
+        hipLaunchKernelGGL(batch_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, fs, p.n_str, p.flags, p.bpre, ctr,
+                           plan.hist_zero == HZ_SCAN ? f.hist : nullptr, p.hist_bins + 8u, p.ctr_snap);
+    else { f.bsum = p.flags; f.ctr = ctr; }
     f.staging = p.staging16 ? (const void *)p.staging16 : (const void *)p.staging;
     f.str_off = p.str_off; f.counts = p.counts; f.n_str = p.n_str; f.id_off = p.id_off; f.ids = p.ids;
     f.bpre = p.bpre;
     uint64_t sls = (FIN_TARGET_BLOCKS + nb - 1) / nb;
     f.slices = (unsigned)(sls < 1 ? 1 : (sls > FIN_MAX_SLICES ? FIN_MAX_SLICES : sls));
     const uint64_t fb = nb * f.slices;
-    if (p.staging16) {
-        hipLaunchKernelGGL(finish_kernel<int16_t>, dim3((unsigned)fb), dim3(FIN_THREADS), 0, fs, f);
-    } else {
-        hipLaunchKernelGGL(finish_kernel<int32_t>, dim3((unsigned)fb), dim3(FIN_THREADS), 0, fs, f);
-    }
+    if (plan.fin_width == 16) hipLaunchKernelGGL(finish_kernel<int16_t>, dim3((unsigned)fb), dim3(FIN_THREADS), 0, fs, f);
+    else hipLaunchKernelGGL(finish_kernel<int32_t>, dim3((unsigned)fb), dim3(FIN_THREADS), 0, fs, f);
     hipError_t eh = hipGetLastError();
-    if (eh == hipSuccess && p.hist && !fold_hist) {   // too many bins for the finish pass's LDS: the separate pass
-        if (p.hist_overwrite && (eh = hipMemsetAsync(p.hist, 0, ((size_t)p.hist_bins + 8u) * sizeof(int64_t), fs)) != hipSuccess)
+    if (eh == hipSuccess && plan.hist_separate) {
+        if (plan.hist_zero == HZ_MEMSET &&
+            (eh = hipMemsetAsync(p.hist, 0, ((size_t)p.hist_bins + 8u) * sizeof(int64_t), fs)) != hipSuccess)
             return eh;
         eh = launch_histogram(p.id_off, p.status, p.n_str, p.hist, p.hist_bins, fs);
     }
     return eh;
+}
+
+hipError_t launch_encode(const EncodeLaunch &p, hipStream_t stream, hipEvent_t ev[2]) {
+    const PlanKey key{p.variant, p.mode, p.staging16 != nullptr, p.edges != nullptr, p.solo, p.padded, p.no_fallback,
+                      ev != nullptr, p.n_str, p.hist != nullptr, p.hist_overwrite, p.hist_bins};
+    const LaunchPlan plan = plan_encode(key, launch_knobs());
+    if (plan.tail == TAIL_EMPTY) return launch_empty(p, plan, stream);
+    const EncodeArgs a = first_pass_args(p, plan.tail == TAIL_SOLO);
+    const TrieView tv{p.slots, p.slot_ids, p.slots4, p.root_base, p.n_slots, p.pair16};
+    // profiling (dpt_ctx_profile): the first pass's dispatch records ev[0], the fallback launch's ev[1]
+    hipError_t e = with_first_kernel(plan.first, [&](auto k) {
+        const bool g16 = plan.first.g == 16;
+        const uint64_t n_units = plan.first.solo ? 1 : g16 ? (p.n_str + 3) / 4 : p.n_str;   // 16-lane rows: 4 strings per wave
+        return launch_tok(k, g16, a, tv, n_units, p.max_blocks / 64, stream, ev ? ev[0] : nullptr);
+    });
+    if (e != hipSuccess) return e;
+    if (plan.tail == TAIL_SOLO) return hipGetLastError();
+    if (plan.mid && (e = launch_mid(p, plan, a, tv, stream)) != hipSuccess) return e;
+    if (plan.fallback && (e = launch_fallback(p, plan, a, tv, stream, ev)) != hipSuccess) return e;
+    return launch_tail(p, plan, stream);
+}
+
+extern "C" int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int edges, int solo, int padded, int no_fallback,
+                                     int profiled, uint64_t n_str, int hist, uint32_t hist_bins, unsigned knobs,
+                                     int32_t *out) {
+    if (!out) return DPT_E_ARG;
+    LaunchKnobs kn = {};
+    kn.generic_ps = knobs & 1u; kn.generic_raw = knobs & 2u; kn.no_solo_wave = knobs & 4u; kn.no_mid = knobs & 8u;
+    const LaunchPlan pl = plan_encode(PlanKey{variant, mode_flags, st16 != 0, edges != 0, solo != 0, padded != 0, no_fallback != 0,
+                                              profiled != 0, n_str, hist != 0, hist == 2, hist_bins}, kn);
+    const int32_t v[DPT_LAUNCH_PLAN_INTS] = {
+        pl.first.g, pl.first.wide, pl.first.sw, pl.first.raw, pl.first.solo, pl.first.mc,
+        pl.mid, pl.midk.sw, pl.midk.wide, pl.midk.mc, pl.fallback, pl.fb.wide, pl.fb.raw, pl.big_list,
+        pl.tail, pl.fin_width, pl.hist_fold, pl.hist_store, pl.hist_zero, pl.hist_separate};
+    for (int q = 0; q < DPT_LAUNCH_PLAN_INTS; q++) out[q] = v[q];
+    auto exists = [](auto) { return hipSuccess; };   // every kernel the plan names must be instantiated
+    const bool ok = pl.tail == TAIL_EMPTY || (with_first_kernel(pl.first, exists) == hipSuccess &&
+                                              (!pl.mid || with_mid_kernel(pl.midk, exists) == hipSuccess) &&
+                                              (!pl.fallback || with_fallback_kernel(pl.fb, exists) == hipSuccess));
+    return ok ? DPT_OK : DPT_E_ARG;
 }
 
 size_t pend_scratch_bytes(unsigned max_blocks) { return (size_t)max_blocks * 64 * sizeof(uint4); }
@@ -3720,23 +3841,20 @@ hipError_t kernel_init() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) dev = 0;
     if (done[dev]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&tokenize_kernel<BIG_CH, 64, true, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, block_lds_bytes<BIG_CH, 64>());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&tokenize_kernel<BIG_CH, 64, true, false, 0, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, block_lds_bytes<BIG_CH, 64>());
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&tokenize_kernel<BIG_CH, 64, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, block_lds_bytes<BIG_CH, 64>());
-    for (const void *k : {reinterpret_cast<const void *>(&fallback_kernel<true, false>), reinterpret_cast<const void *>(&fallback_kernel<false, true>),
-                          reinterpret_cast<const void *>(&fallback_kernel<false, false>)})
-        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds_bytes<BIG_CH, 64>());
+    // the kernels with block_lds_bytes<BIG_CH, 64>() of dynamic LDS: the 2048-byte pass as a kernel of its own
+    // (not launched since it shares fallback_kernel's launch; kept instantiated) and the fallback kernels
+    auto big_lds = [](auto kern) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   block_lds_bytes<BIG_CH, 64>());
+    };
+    hipError_t e = big_lds(tokenize_kernel<BIG_CH, 64, true, false>);
+    if (e == hipSuccess) e = big_lds(tokenize_kernel<BIG_CH, 64, true, false, 0, true>);
+    if (e == hipSuccess) e = big_lds(tokenize_kernel<BIG_CH, 64, true, true>);
+    for (const FallbackChoice &c : FALLBACK_CHOICES)
+        if (e == hipSuccess) e = with_fallback_kernel(c, big_lds);
     if (e == hipSuccess) done[dev] = true;
     return e;
 }
-
-int small_window_bytes() { return SMALL_CH; }
-int big_window_bytes() { return BIG_CH; }
 
 #ifdef DPT_STAMPS
 extern "C" int dpt_debug_stamps(unsigned long long *out, int reset) {

@@ -272,6 +272,19 @@ int dpt_ctx_profile_read(dpt_ctx *c, double *ms, uint64_t *launches);
  * (tests/test_gpu_parity.py::test_long_pass_offsets_past_2g).  bias < 2^62; 0 turns it off. */
 int dpt_ctx_debug_counter_bias(dpt_ctx *c, uint64_t bias);
 
+/* TEST-ONLY, needs no device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  The kernels an encode call
+ * with these properties launches (tests/test_launch_plan.py holds the table).  variant: 1 = 16-lane rows,
+ * 2 = 64-lane; hist: 0 none, 1 add, 2 overwrite; knobs: bits 1 DPT_GENERIC_PS, 2 DPT_GENERIC_RAW,
+ * 4 DPT_NO_SOLO_WAVE, 8 DPT_NO_MID.  out: [0..5] the first pass's lanes, WIDE, SW, RAW, SOLO, MC; [6..9] the
+ * 512-byte pass runs, its SW, WIDE, MC; [10..13] the 2048-byte + unbounded launch runs, its WIDE, RAW, the
+ * list the 2048-byte pass reads (0 / 2: the first / 512-byte pass's); [14] the tail: 0 memsets, 1 nothing
+ * (solo), 2 reset_kernel, 3 scan + finish, 4 fold finish, 5 one-batch finish; [15] finish width in bits;
+ * [16..19] the histogram is folded into the finish pass, stored by it, zeroed by (0 nobody, 1 the 2048-byte
+ * pass, 2 the scan, 3 a memset), the separate pass follows.  DPT_E_ARG: a kernel it names does not exist. */
+#define DPT_LAUNCH_PLAN_INTS 20
+int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int edges, int solo, int padded, int no_fallback,
+                          int profiled, uint64_t n_str, int hist, uint32_t hist_bins, unsigned knobs, int32_t *out);
+
 /*
  * Multi-GPU without torch (ABI 6; SURVEY.md §8(b) dpt_hist_allreduce, §8(e) "direct RCCL with a
  * file-store unique id").  One process per GPU: rank 0 calls dpt_rccl_get_unique_id and hands the
