@@ -1,9 +1,13 @@
-// Internal interface between the C-ABI (dpt_api.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip).
+// Internal interface between the C-ABI (dpt_api.cpp), the host table builder (dpt_vocab.cpp) and the
+// kernels (dpt_kernels.hip, dpt_spans.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <string>
+#include <vector>
 
 #include "../../include/dpt.h"
 
@@ -92,7 +96,7 @@ struct EncodeLaunch {
     const int2 *slots;
     const int32_t *slot_ids;
     const int16_t *pair16;   // ids of the one- and two-byte tokens (PAIR16_N int16), then phase A0's byte-pair flags
-                             //   + child filters (65536 uint2) -- dpt_api.cpp dpt_vocab_create
+                             //   + child filters (65536 uint2) -- dpt_vocab.cpp build_vocab_tables
     const int4 *slots4;      // {base | TERM<<31 | LEAF<<30, check, id, child filter}
     uint32_t n_slots;
     int32_t root_base;
@@ -135,7 +139,7 @@ constexpr size_t CTR_ALLOC_BYTES = PART_CTR_OFFSET + (NPART_MAX + 1) * PART_STRI
 // low five bits inside each 32-byte block, so the 26 lowercase letters get distinct bits
 __host__ __device__ inline unsigned child_bit(unsigned b) { return (b ^ (b >> 5)) & 31u; }
 
-// Token hash table (C2's one-lookup ids for tokens of 3..16 expanded bytes; dpt_vocab_create builds
+// Token hash table (C2's one-lookup ids for tokens of 3..16 expanded bytes; build_vocab_tables puts
 // it after the A0 table in the pair16 allocation).  Key: the token's bytes as four little-endian
 // dwords, zero past its length, plus the length.  Buckets of two {fp, id} entries (fp != 0; 0 marks a
 // free entry), two choices per key (cuckoo placement, round 5): bucket h & mask or its partner
@@ -245,20 +249,36 @@ hipError_t kernel_init();
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {
     // slot t: base[t] (| TERM bit 31 when a token ends here, | LEAF bit 30 when no child), check[t] = parent slot (-1 free)
-    int32_t *base = nullptr;
-    int32_t *check = nullptr;
-    int32_t *id = nullptr;
-    uint32_t n_slots = 0;
-    uint32_t n_nodes = 0;
-    uint32_t n_tokens = 0;
-    uint32_t max_bytes = 0;
-    uint32_t max_cp = 0;
+    std::vector<int32_t> base, check, id;   // stats.n_slots each
+    dpt_vocab_stats stats{};                // n_tokens, n_nodes, n_slots, max_bytes, max_cp
     int32_t root_base = 0;
 };
 
 // returns 0 or an error message
 const char *build_double_array(const uint8_t *blob, const uint64_t *off, const int32_t *ids, uint32_t n,
                                DoubleArray *out);
-void free_double_array(DoubleArray *da);
+
+// What the kernels need to know of a vocabulary besides its tables (dpt_vocab holds a copy).
+struct VocabScalars {
+    int32_t root_base = 0;
+    int32_t ws_node = -1, ws_base = 0, ws_id = -1;   // the trie node after U+2581 (-1: no such path)
+    bool ids16 = false;               // every id in 0..32767: ids are staged as int16 (half the staging traffic)
+    uint32_t hash_buckets = 0, hash_probe = 0;   // C2's token hash table (0: none)
+    int32_t id_min = 0;               // tok_len's first id
+    uint32_t n_tab = 0;               // its entries (0: no table)
+    dpt_vocab_stats stats{};
+};
+// Every device table of a vocabulary as host bytes, exactly as dpt_vocab_create uploads them
+// (build_vocab_tables, dpt_vocab.cpp; the formats are described there).
+struct VocabTables : VocabScalars {
+    std::vector<int2> slots;          // n_slots {base, check}, then the two-byte root table (65536 entries)
+    std::vector<int32_t> slot_ids;    // n_slots
+    std::vector<int4> slots4;         // {base, check, id, child filter} per slot, then the root table again
+    std::vector<uint8_t> pair;        // pair16 (PAIR16_N int16) | a0 (65536 uint2) | from TOKHASH_OFFSET: hash header + buckets
+    std::vector<uint16_t> tok_len;    // byte length per id - id_min; empty: no dense table (the spans calls: DPT_E_VOCAB)
+};
+// returns 0 or an error message; calls no HIP function
+const char *build_vocab_tables(const uint8_t *blob, const uint64_t *off, const int32_t *ids, uint32_t n, VocabTables *out);
+void set_last_error(const std::string &msg);   // (dpt_api.cpp)
 
 }  // namespace dpt

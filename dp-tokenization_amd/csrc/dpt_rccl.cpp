@@ -20,12 +20,9 @@
 #include <string>
 
 #include "../../include/dpt.h"
+#include "dpt_internal.h"   // set_last_error
 
 static_assert(sizeof(ncclUniqueId) == DPT_RCCL_ID_BYTES, "ncclUniqueId size");
-
-namespace dpt {
-void set_last_error(const std::string &msg);   // dpt_api.cpp
-}
 
 namespace {
 

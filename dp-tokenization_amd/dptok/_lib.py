@@ -81,6 +81,7 @@ def lib():
     L.dpt_ctx_profile_read.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64)]
     L.dpt_ctx_debug_counter_bias.argtypes = [P, U64]
     L.dpt_debug_launch_plan.argtypes = [I32] * 8 + [U64, I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(I32)]
+    L.dpt_debug_vocab_table.argtypes = [P, P, P, ctypes.c_uint32, I32, P, U64, ctypes.POINTER(U64)]
     L.dpt_rccl_get_unique_id.argtypes = [P]
     L.dpt_rccl_comm_create.argtypes = [P, I32, I32, I32, ctypes.POINTER(P)]
     L.dpt_rccl_comm_destroy.argtypes = [P]
@@ -88,7 +89,7 @@ def lib():
     for name in ("dpt_vocab_create", "dpt_vocab_destroy", "dpt_vocab_stats_get", "dpt_ctx_create", "dpt_ctx_destroy",
                  "dpt_ctx_reserve", "dpt_ctx_reserve_vocab", "dpt_ctx_workspace_bytes", "dpt_ctx_long_need", "dpt_encode", "dpt_encode_padded", "dpt_encode_host", "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram",
                  "dpt_token_spans", "dpt_token_spans_host", "dpt_ctx_set_histogram","dpt_ctx_set_histogram_ex", "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias",
-                 "dpt_debug_launch_plan", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"):
+                 "dpt_debug_launch_plan", "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"):
         getattr(L, name).restype = I32
     _lib = L
     return L
@@ -107,4 +108,4 @@ EXPORTED = ["dpt_last_error", "dpt_abi_version", "dpt_vocab_create", "dpt_vocab_
             "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram", "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex",
             "dpt_token_spans", "dpt_token_spans_host",
             "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias", "dpt_debug_launch_plan",
-            "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"]
+            "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"]

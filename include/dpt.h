@@ -285,6 +285,18 @@ int dpt_ctx_debug_counter_bias(dpt_ctx *c, uint64_t bias);
 int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int edges, int solo, int padded, int no_fallback,
                           int profiled, uint64_t n_str, int hist, uint32_t hist_bins, unsigned knobs, int32_t *out);
 
+/* TEST-ONLY, needs no device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  The bytes dpt_vocab_create
+ * would upload for this vocabulary (its first four arguments), built on the host
+ * (tests/test_vocab_tables.py holds a model of the formats).  which: 0 slots (n_slots + 65536 int32 pairs),
+ * 1 slot ids (n_slots int32), 2 slots4 (n_slots + 65536 x four int32), 3 the pair block (65536 + 256 int16 |
+ * 65536 x two uint32 | hash header + buckets), 4 tok_len (uint16 per id - id_min; size 0: no table),
+ * 5 DPT_VOCAB_SCALAR_INTS int32: root_base, ws_node, ws_base, ws_id, ids16, id_min, n_tab, hash_buckets,
+ * hash_probe, n_tokens, n_nodes, n_slots, max_bytes, max_cp, device_bytes (low, high word).
+ * *size = the table's bytes, always; it is copied to out (nullable) when cap >= *size, else DPT_E_CAP. */
+#define DPT_VOCAB_SCALAR_INTS 16
+int dpt_debug_vocab_table(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok,
+                          int which, void *out, uint64_t cap, uint64_t *size);
+
 /*
  * Multi-GPU without torch (ABI 6; SURVEY.md §8(b) dpt_hist_allreduce, §8(e) "direct RCCL with a
  * file-store unique id").  One process per GPU: rank 0 calls dpt_rccl_get_unique_id and hands the

@@ -100,3 +100,52 @@ def test_one_string_calls(vocabs):
                 got, ref = enc.encode_csr(text, offs), orc.encode_csr(text, offs)
                 for g, r in zip(got, ref):
                     assert np.array_equal(g, r), (name, k, "batch")
+
+
+def test_zero_copy_calls_after_the_spans_path_moved_the_pinned_buffers(vocabs):
+    """The two host paths share one pair of pinned staging buffers (dpt_api.cpp stage_host), and the
+    one-string zero-copy call addresses them from the device: a spans host call that outgrows them moves
+    them, and the next one-string encode must look their device addresses up again.  One Encoder: a
+    one-string call (4096-byte pinned buffers, addresses looked up), a dpt_token_spans_host call on 64
+    strings of 200 bytes whose ids come from the oracle (so no encode call has grown the buffers: both
+    move here), one-string calls, then the same through encode_csr_spans, one-string calls again (empty,
+    ASCII, multi-byte) and a PRESPLIT one -- each exact against the oracle, the spans against the walk of
+    tests/spans_ref.py."""
+    import spans_ref
+    from dptok import Encoder, Vocab, _lib, pack_strings, synth
+    from dptok.engine import pack_presplit_words
+    from oracle import oracle
+    t2i = vocabs["llama32k"]
+    enc, orc = Encoder(Vocab(t2i, 0)), oracle.OracleVocab(t2i)
+
+    def one(s, what):
+        text, offs = pack_strings([s])
+        for g, r, part in zip(enc.encode_csr(text, offs), orc.encode_csr(text, offs), ("ids", "offsets", "status", "capped")):
+            assert np.array_equal(g, r), (what, part, s[:30])
+
+    one("the first call", "before")
+    text, offs = pack_strings(synth.unpack(*synth.random_ascii_corpus(64, 200, seed=13)))
+    ids, id_off, st, _ = orc.encode_csr(text, offs)
+    ids, id_off, st = (np.ascontiguousarray(a, dtype=t) for a, t in ((ids, np.int32), (id_off, np.uint64), (st, np.int32)))
+    n, n_tok, n_bytes = len(st), len(ids), int(offs[-1])
+    assert n == 64 and n_bytes > 4096 and 4 * n_tok > 4096 and not st.any()   # more than the first buffers, in and out
+    ref = spans_ref.expected(t2i, "raw", text, offs, None, ids, id_off, st)
+    end, word, ss = np.zeros(n_tok, np.uint32), np.zeros(n_tok, np.uint32), np.full(n, -1, np.int32)
+    rc = _lib.lib().dpt_token_spans_host(enc.handle, enc.vocab.handle, _lib.DPT_MODE_RAW, text.ctypes.data, n_bytes,
+                                         offs.ctypes.data, None, n, ids.ctypes.data, id_off.ctypes.data, st.ctypes.data,
+                                         end.ctypes.data, word.ctypes.data, ss.ctypes.data)
+    _lib.check(rc, "dpt_token_spans_host")
+    for g, r in zip((end, word, ss), ref):
+        assert np.array_equal(g, r)
+    for s in ("", "after the spans call", "é中😀 x"):
+        one(s, "after the spans call")
+    got = enc.encode_csr_spans(text, offs)
+    assert np.array_equal(got[0], ids) and np.array_equal(got[1], id_off) and np.array_equal(got[2], st)
+    for g, r in zip(got[4:], ref):
+        assert np.array_equal(g, r)
+    for s in ("", "plain ascii words", "naïve 中文 😀 end"):
+        one(s, "after encode_csr_spans")
+    text, offs, cut, _, _ = pack_presplit_words([["▁pre", "▁split", "words", "▁é中"]])
+    for g, r, part in zip(enc.encode_csr(text, offs, mode="presplit", cut_mask=cut),
+                          orc.encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut), ("ids", "offsets", "status", "capped")):
+        assert np.array_equal(g, r), ("presplit", part)
