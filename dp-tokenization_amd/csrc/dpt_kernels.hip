@@ -1968,7 +1968,8 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
             // corrects the two things that depend on it: the final key of the word that ends
             // first in the chunk (cost offset, max with the incoming G) and dg at the positions
             // before that word end (dg = de wherever the incoming G already attains G[i]:
-            // every j in E(i) then ties on max(G[j], cp(span))).  de and E(i) are local.
+            // every j in E(i) then ties on max(G[j], cp(span))).  de and E(i) are local.  The first
+            // is one store; the second is a test in the C1 walk, at the ends it visits.
             auto forward_lanes = [&]() {
               if constexpr (G == 16) {
                 // LW lanes share a window: a 16-lane row per slot, or (the one-string kernel, SOLO) the whole
@@ -2087,14 +2088,16 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
                             if (kk < best) dg = dd;
                             best = kk < best ? kk : best;
                         }
-                        L.rec[i].smask = (uint16_t)best;   // this end's mask was read above
+                        // One dword: the key in the mask half (this end's mask was read above), and the
+                        // local G(i) - 1 (G is 1..16 past rs in a capless window) in bits 11..14 of the
+                        // cpos half (code-point prefixes are < 2048 in a window; every reader of a cpos
+                        // in lane mode masks them off).  C1 finds it there -- the mask halves take the
+                        // walks' tokens: at a word end it is the word's L* - 1 (the longest token to
+                        // select), elsewhere what the walk's dg/de rule compares the incoming G with.
+                        rec32[i] = (best << 16) | (r & 0x87FFu) | ((30u - (best & 31u)) << 11);
                         L.fin[i].v = (uint8_t)(dg | (de << 4));
                         const bool wend = (r & CP_WS) != 0;
                         if (wend) {
-                            // the word ending at i: its G (the longest token to select, L*) - 1 goes
-                            // into bits 11..14 of rec[i].cpos (code-point prefixes are < 2048 in a
-                            // 256-byte window), where C1 finds it (the mask halves take its tokens)
-                            L.rec[i].cpos = (uint16_t)((r & 0x87FFu) | ((30u - (best & 31u)) << 11));
                             T += best >> 6;
                             if (!pe) pe = i;
                         }
@@ -2127,21 +2130,19 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
                 }
                 const unsigned in = gshr<LW, 1>(x, FRESH) & 0xFFFFu;
                 const unsigned gin = 31u - (in & 31u);   // G at rs
-                if (gin) {
-                    const unsigned lim = pe ? pe : re;
-                    for (unsigned q = rs + 1u; q <= lim; q++) {
-                        const unsigned kl = L.rec[q].smask;
-                        if (gin >= 31u - (kl & 31u)) {
-                            const unsigned f = L.fin[q].v;
-                            L.fin[q].v = (uint8_t)((f & 0xF0u) | (f >> 4));
-                        }
-                    }
-                    if (pe) {
-                        const unsigned kl = L.rec[pe].smask;
-                        L.rec[pe].smask = (uint16_t)((in & 0xFFC0u) + (kl & 0xFFC0u) + min(in & 31u, kl & 31u));
-                        if (gin > 31u - (kl & 31u)) L.rec[pe].cpos = (uint16_t)((L.rec[pe].cpos & 0x87FFu) | ((gin - 1u) << 11));
-                    }
+                // The incoming state changes two things.  The final key of the word that ends first in
+                // the chunk: composed here, and its L* := gin where gin > G(pe).  And dg at the ends q in
+                // (rs, lim], lim = that word end (re without one): dg = de where gin >= the local G(q).
+                // Only the ends the C1 walk visits need that, so the walk applies it (fgm below) from the
+                // G(q) - 1 the recurrence left in rec[q]; at pe the bits then hold max(gin, G(pe)) - 1,
+                // which gin - 1 reaches exactly when gin >= the local G(pe).
+                if (gin && pe) {
+                    const unsigned kl = L.rec[pe].smask;
+                    L.rec[pe].smask = (uint16_t)((in & 0xFFC0u) + (kl & 0xFFC0u) + min(in & 31u, kl & 31u));
+                    if (gin > 31u - (kl & 31u)) L.rec[pe].cpos = (uint16_t)((L.rec[pe].cpos & 0x87FFu) | ((gin - 1u) << 11));
                 }
+                const unsigned flim = gin ? (pe ? pe : re) : 0u;   // no incoming G: no end is <= 0
+                const unsigned fgm = gin - 1u;                      // (read only where flim != 0)
                 const unsigned gre = p1in ? max(gin, gl1) : gl1;   // G at re of P1's word (its L* if re_ws)
                 if (DPT_STOP == 27) return;   // diagnostic: + the transfer scan and fix-up
 
@@ -2205,7 +2206,10 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
                             const unsigned f = L.fin[ii].v;
                             const unsigned sp = pend - cpi;
                             A = A > sp ? A : sp;
-                            const unsigned dd = A < Ls ? (f & 15u) : (f >> 4);
+                            // de once A has reached L*, and where the incoming G attains the local G(ii)
+                            // (every j in E(ii) then ties on G: the chunk-start rule, see flim)
+                            const bool tie = (ii <= flim) & (((rr >> 11) & 15u) <= fgm);
+                            const unsigned dd = ((A >= Ls) | tie) ? (f >> 4) : (f & 15u);
                             const unsigned j = ii - 1u - dd;
                             k--;
                             L.rec[k].smask = (uint16_t)j;   // k < rs or a position this walk has left
@@ -2252,8 +2256,8 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
             // A's start masks, rec[j].smask): the token j..i updates i's entry {dg | de << 8 | cp(i)
             // << 16, key} in fin[].  Starts are taken in ascending order, so "<=" keeps the largest j
             // of a tie -- the row recurrence's lowest lane (dp_tokenize.py:40-46).  A wave scan of the
-            // chunk transfers and forward_lanes' fix-up follow; C0/C1 then run as in row mode (they
-            // read fin[] only).
+            // chunk transfers and the chunk-start fix-up follow (here a loop over fin[]; forward_lanes
+            // applies it in its own walk); C0/C1 then run as in row mode (they read fin[] only).
             auto forward_lanes64 = [&]() {
               if constexpr (G == 64 && !BIG) {
                 if (na == 0) return;

@@ -27,7 +27,14 @@ def window(text):
         cpos.append(cpos[-1] + len(a))
     return atoms, ws + [True], cpos
 
-def model(text, vocab, verbose=False):
+def model(text, vocab, verbose=False, fold=True, stats=None):
+    """fold=True: the kernel's form -- the recurrence records g1[i] = the local G(i) - 1 at every end
+    (bits 11..14 of rec[i].cpos), and the C1 walk applies the chunk-start rule (dg = de where the
+    incoming G attains the local G) at the ends it visits.  fold=False: the earlier two-pass form,
+    a fix-up loop over every end of (rs, lim] that rewrites fin[] before the walks; kept so that
+    the equivalence stays testable (tests/test_lane_fold_model.py).  stats (a dict, fold=True):
+    "walk_steps", "fold_changed" (steps where the rule picked de over a different dg) and "g1"
+    (every value the recurrence or the word-end update wrote) are accumulated into it."""
     atoms, wsf, cpos = window(text)
     na = len(atoms)
     # end masks: bit d of em[i] = atoms i-1-d .. i-1 form a token (within a word)
@@ -42,6 +49,7 @@ def model(text, vocab, verbose=False):
                 em[j + L] |= 1 << (L - 1)
     assert all(em[i] & 1 for i in range(1, na + 1)), "not capless"
     key = [0] * (na + 2); fin = [0] * (na + 2); lstar = [0] * (na + 2)
+    g1 = [None] * (na + 2)   # fold: G - 1 at every end (at a word end: L* - 1, as lstar[] - 1)
     C = ((na + 15) >> 4) | 1
     lanes = []
     for d in range(16):
@@ -88,6 +96,7 @@ def model(text, vocab, verbose=False):
                     if kk < best: dg = dd
                     best = min(best, kk)
             key[i] = best; fin[i] = dg | de << 4
+            g1[i] = 30 - (best & 31)
             if wsf[i]:
                 lstar[i] = 31 - (best & 31)
                 T += best >> 6
@@ -113,16 +122,18 @@ def model(text, vocab, verbose=False):
         rs, re, pe, inn = l["rs"], l["re"], l["pe"], l["in"]
         gin = 31 - (inn & 31)
         l["gin"] = gin
+        l["flim"] = (pe if pe else re) if gin else 0
         if gin:
-            lim = pe if pe else re
-            for q in range(rs + 1, lim + 1):
-                if gin >= 31 - (key[q] & 31):
-                    fin[q] = (fin[q] & 0xF0) | (fin[q] >> 4)
+            if not fold:
+                for q in range(rs + 1, l["flim"] + 1):
+                    if gin >= 31 - (key[q] & 31):
+                        fin[q] = (fin[q] & 0xF0) | (fin[q] >> 4)
             if pe:
                 kl = key[pe]
                 key[pe] = (inn & 0xFFC0) + (kl & 0xFFC0) + min(inn & 31, kl & 31)
                 if gin > 31 - (kl & 31):
                     lstar[pe] = gin
+                    g1[pe] = gin - 1
         l["gre"] = max(gin, l["gl1"]) if l["p1in"] else l["gl1"]
     # token bases
     tb = 0
@@ -147,7 +158,12 @@ def model(text, vocab, verbose=False):
             n1 += inp1
             f = fin[ii]
             sp = pend - cpos[ii]; A = max(A, sp)
-            dd = (f & 15) if A < Ls else (f >> 4)
+            tie = fold and ii <= l["flim"] and g1[ii] <= l["gin"] - 1
+            dd = (f >> 4) if (A >= Ls or tie) else (f & 15)
+            if stats is not None:
+                stats["walk_steps"] = stats.get("walk_steps", 0) + 1
+                if tie and A < Ls and (f & 15) != (f >> 4):
+                    stats["fold_changed"] = stats.get("fold_changed", 0) + 1
             j = ii - 1 - dd
             k -= 1; starts[k] = j
             pend = cpos[ii]; ii = j
@@ -167,6 +183,8 @@ def model(text, vocab, verbose=False):
             for c in range(l["n1"]):
                 j = ii - 1 - (fin[ii] >> 4)
                 k -= 1; starts[k] = j; ii = j
+    if stats is not None:
+        stats.setdefault("g1", []).extend(v for v in g1 if v is not None)
     toks = []
     for k in range(tb):
         e = starts[k + 1] if k + 1 < tb else na
