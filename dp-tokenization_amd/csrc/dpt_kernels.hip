@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "dpt_internal.h"
+#include "dpt_wave.h"
 // the unbounded pass (namespace dpt::lng): one translation unit with fallback_kernel, which runs it
 // in the same launch as the 2048-byte pass
 #include "dpt_long.hip"
@@ -57,19 +58,7 @@ namespace dpt {
 // DESIGN.md §9 lists them with their numbers.
 
 // ------------------------------------------------------------------ wave primitives
-
-__device__ __forceinline__ unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// inclusive add-scan over 64 lanes (GFX9 DPP: row_shr 1/2/4/8, row_bcast 15/31)
-__device__ __forceinline__ unsigned wave_incl_scan_add(unsigned v) {
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, true);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xF, 0xF, true);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xF, 0xF, true);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xF, 0xF, true);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false); // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false); // row_bcast:31
-    return v;
-}
+// (lane_id, uni, ballot, wave_incl_scan_add and wave_shift_in: dpt_wave.h, shared with dpt_long.hip and dpt_spans.hip)
 
 // inclusive max-scan over 64 lanes (values >= 0; the same DPP steps as the add scan)
 __device__ __forceinline__ unsigned wave_incl_scan_max(unsigned v) {
@@ -110,12 +99,9 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-// lane l receives x[l-1]; the first lane of each row (row_shr:1) / of the wave (wave_shr:1) receives `in`
+// lane l receives x[l-1]; the first lane of each row receives `in` (row_shr:1; the wave's: wave_shift_in)
 __device__ __forceinline__ unsigned row_shift_in(unsigned x, unsigned in) {
     return (unsigned)__builtin_amdgcn_update_dpp((int)in, (int)x, 0x111, 0xF, 0xF, false);
-}
-__device__ __forceinline__ unsigned wave_shift_in(unsigned x, unsigned in) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)in, (int)x, 0x138, 0xF, 0xF, false);
 }
 
 // Lane-group shifts for lane-mode B: lane l of a group of LW lanes receives x of lane l + K (gshl) / l - K (gshr),
@@ -154,12 +140,9 @@ __device__ __forceinline__ uint64_t wave_incl_scan_add64(uint64_t v, unsigned la
     return v;
 }
 
-__device__ __forceinline__ unsigned uni(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint64_t uni64(uint64_t x) {
     return ((uint64_t)uni((unsigned)(x >> 32)) << 32) | uni((unsigned)x);
 }
-
-__device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 // lowest set bit (v_ffbl_b32: 0xFFFFFFFF for 0, no select needed where 0 cannot matter)
 __device__ __forceinline__ unsigned ffbl(unsigned x) {
@@ -404,11 +387,15 @@ struct EncodeArgs {
 #ifdef DPT_STAMPS
 // diagnostic build only: cycles per phase summed over waves (never in the product build)
 __device__ unsigned long long g_stamps[10];
-#define STAMP_DECL unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long st_prev = __builtin_amdgcn_s_memtime();
-#define STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st_acc[k] += _t - st_prev; st_prev = _t; } while (0)
-#define STAMP_FLUSH do { if (lane == 0) for (int _k = 0; _k < 10; _k++) atomicAdd(&g_stamps[_k], st_acc[_k]); } while (0)
+// (the wave's stamps: the driver's, handed to the one phase that stamps inside itself, C2)
+struct Stamps {
+    unsigned long long acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long prev = __builtin_amdgcn_s_memtime();
+};
+#define STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st.acc[k] += _t - st.prev; st.prev = _t; } while (0)
+#define STAMP_FLUSH do { if (lane == 0) for (int _k = 0; _k < 10; _k++) atomicAdd(&g_stamps[_k], st.acc[_k]); } while (0)
 #else
-#define STAMP_DECL
+struct Stamps {};
 #define STAMP(k)
 #define STAMP_FLUSH
 #endif
@@ -962,107 +949,474 @@ __device__ __forceinline__ void reset_counters(uint32_t *ctr, uint64_t *snap = n
 // The body of tokenize_kernel (and of fallback_kernel's 2048-byte blocks); bid: the block's index
 // among the blocks running it.  The kernel arguments start with a KernArgs (read through the kernarg
 // segment pointer, KREFRESH).
+// The class is the traits of an instantiation (NG, GL, GR, M, GSTR, PLAIN), its view of the wave's LDS (SSr, grp,
+// wsl_of) and the phases that are functions; body() is the driver of a wave's slot loop.
 template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
-__device__ __forceinline__ void tokenize_body(const unsigned bid) {
-    ConstKernArgs *kp = (ConstKernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-#define a (kp->ea)
-#define tv (tv_of(kp))
-    constexpr int NG = 64 / G;
+struct TokPass {
+    static constexpr int NG = 64 / G;
     using GL = GroupLDS<CH, G>;
     using GR = Group<G>;
     using M = typename GR::M;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr unsigned GSTR = (unsigned)group_stride<CH, G>();
-    auto SSr = [&](unsigned g) -> SlotState & { return *reinterpret_cast<SlotState *>(smem + g * GSTR + group_lds_bytes<CH, G>()); };
-    auto grp = [&](unsigned g) -> GL & { return *reinterpret_cast<GL *>(smem + g * GSTR); };
-    auto wsl_of = [&](unsigned g) -> uint8_t * {
-        return GL::WSLG ? a.wsl_scratch + ((size_t)bid * NG + g) * GL::WSL_STRIDE : nullptr;
-    };
-
-    const unsigned lane = lane_id();
-    const unsigned mg = lane / G;        // my group
-    const unsigned d = lane % G;         // my back distance - 1
-    const uint64_t n_work = BIG ? (uint64_t)(*a.work_count) : a.n_str;
-    if constexpr (BIG)
-        if (a.hist_zero && bid == 0)
-            for (uint32_t b = lane; b < a.n_hist; b += 64u) a.hist_zero[b] = 0;
-    if (BIG && n_work == 0) return;   // no retries: no counter traffic
-    const uint64_t base_off = a.str_off[0];
-    // (the other instantiations keep the mode a run-time value: folding raw = false into the atoms-mode
-    // 16-lane kernel crashes ROCm 7.2's greedy register allocator)
-    // RAW / MC >= 0: the mode as a compile-time constant (PRESPLIT, ATOMS; the other instantiations read it)
-    const int mode = RAW ? 0 : (MC >= 0 ? MC : (a.mode & DPT_MODE_MASK));
-    const bool raw = mode == 0;
+    static constexpr unsigned GSTR = (unsigned)group_stride<CH, G>();
     // PLAIN: the mode-constant instantiations serve only calls without edges, the uncapped DP or len_only
     // (launch_encode sends those to the runtime-mode kernels): their loop versions are compiled out
-    constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0) && !SOLO;
-    const bool uncapped = !PLAIN && (a.mode & DPT_FLAG_UNCAPPED) != 0;   // f2: inspect_tokenizer's inf-initialised DP
-    const bool len_only = !PLAIN && (a.mode & (DPT_FLAG_UNCAPPED | DPT_FLAG_LEN_ONLY)) != 0;
-    // Strings are handed out by npart device counters (each in its own 256-byte line).  Partition p
-    // holds the FIN_BATCH-string chunks p, p + npart, p + 2 npart, ... of the batch, in that order
-    // (part_size / part_string): the partitions advance through the batch side by side, so strings
-    // finish roughly in batch order.  A wave claims as many strings as it has free slots from its current partition (starting on
-    // blockIdx mod npart) and, when a claim reaches the partition's end, marks the partition in a
-    // shared mask and moves to the next unmarked one.  Round 1's single counter (one same-address
-    // atomic per refill) bound the whole kernel: a prep-only build ran 2.91 of the full build's 2.99
-    // ms, every wave queued behind ~5.6k others' atomics (profiles/r02_phase_diag.txt).  No string is
-    // claimed ahead of a free slot: strings held in reserve by one wave left others idle at the end
-    // of multi-window batches (cfg4 4.35 -> 4.56 ms with 4-string claims).
-    const unsigned npart = (BIG || (DPT_DIAG_PREP & 1)) ? 1u : (unsigned)min((uint64_t)NPART, max((uint64_t)1, n_work / 4096u));
-    [[maybe_unused]] uint64_t diag_k = 0;   // DPT_DIAG_PREP & 1: the wave's claims so far
-    unsigned part = BIG ? 0u : bid % npart;
-    bool exhausted = false, claimed_all = false;
-    unsigned n_pend = 0;   // 16-lane first pass: residual tokens waiting in the wave's pending row
-    // one claim of up to req strings (uniform): partition-local [nb, ne) of partition cp, possibly
-    // empty once every partition is used up
-#ifdef DPT_WSTAMPS
-    unsigned wst_claims = 0;
-#define WST_CLAIM() (wst_claims++)
-#else
-#define WST_CLAIM()
-#endif
-    auto claim = [&](unsigned req, uint64_t &nb, uint64_t &ne, unsigned &cp) {
-        for (;;) {
-            WST_CLAIM();
-            uint32_t *ctr = BIG ? a.work_next : a.part_ctr + part * PART_STRIDE;
-            const uint64_t hi = BIG ? n_work : part_size((unsigned)n_work, npart, part);
-            unsigned b = 0;
-            if constexpr (!BIG && (DPT_DIAG_PREP & 1)) {   // diagnostic: wave bid's k-th claim, blocks of 4
-                b = (unsigned)((diag_k * gridDim.x + bid) * 4u);
-                diag_k++;
-            } else {
-                if (lane == 0) b = atomicAdd(ctr, req);
-                if constexpr (!BIG && (DPT_DIAG_PREP & 4)) {   // diagnostic: one more dependent atomic round trip
-                    unsigned x = 0;
-                    asm volatile("" : "+v"(b));
-                    if (lane == 0) x = atomicAdd(ctr + (b >> 31), 0u);
-                    asm volatile("" : "+v"(x));
-                    b |= (x >> 31) << 31;
+    static constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0) && !SOLO;
+
+    // the wave's LDS: slot g's arrays at g * GSTR, then its SlotState (group_stride); its word list in global scratch
+    static __device__ __forceinline__ unsigned char *lds() {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+        return smem;
+    }
+    static __device__ __forceinline__ SlotState &SSr(unsigned g) {
+        return *reinterpret_cast<SlotState *>(lds() + g * GSTR + group_lds_bytes<CH, G>());
+    }
+    static __device__ __forceinline__ GL &grp(unsigned g) { return *reinterpret_cast<GL *>(lds() + g * GSTR); }
+    static __device__ __forceinline__ uint8_t *wsl_of(ConstKernArgs *kp, unsigned bid, unsigned g) {
+        return GL::WSLG ? kp->ea.wsl_scratch + ((size_t)bid * NG + g) * GL::WSL_STRIDE : nullptr;
+    }
+
+    // ---- C0: per-window token counts and validity (row mode)
+    static __device__ __forceinline__ void phase_c0(ConstKernArgs *kp, const unsigned bid, const unsigned lane) {
+#define a (kp->ea)
+#define tv (tv_of(kp))
+        if constexpr (GL::WSLG) {
+            // the word list (word -> first atom, then the window end) from the word-start bits
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                const unsigned na = uni(SSr(g).n_atoms);
+                if (na == 0) continue;
+                const GL &L = grp(g);
+                uint8_t *gw = wsl_of(kp, bid, g);
+                unsigned wi = 0;
+                for (unsigned j0 = 0; j0 <= na; j0 += 64u) {
+                    const unsigned j = j0 + lane;
+                    const bool ws = j <= na && (L.rec[j].cpos & CP_WS) != 0;   // atom na: the window end
+                    const uint64_t m = ballot(ws);
+                    if (ws) gw[wi + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (uint8_t)j;
+                    wi += (unsigned)__builtin_popcountll(m);
                 }
             }
-            cp = __builtin_amdgcn_readfirstlane(part);
-            nb = (uint32_t)__builtin_amdgcn_readlane(b, 0);
-            ne = nb < hi ? (nb + req < hi ? nb + req : hi) : nb;
-            if (nb + req >= hi) {   // the partition is used up (by this claim or earlier ones)
-                if (BIG) {
-                    claimed_all = true;
+        }
+        unsigned pre[NG + 1];
+        pre[0] = 0;
+#pragma unroll
+        for (int g = 0; g < NG; g++) pre[g + 1] = pre[g] + (uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).n_words) : 0u);
+        const unsigned total = pre[NG];
+        for (unsigned u0 = 0; u0 < total; u0 += 64) {
+            const unsigned u = u0 + lane;
+            unsigned g = 0;
+#pragma unroll
+            for (int k = 1; k < NG; k++) g += u >= pre[k] ? 1u : 0u;
+            unsigned wbase = 0;
+#pragma unroll
+            for (int k = 0; k < NG; k++) wbase = g == (unsigned)k ? pre[k] : wbase;
+            unsigned cost = 0, inv = 0, lng = 0;
+            if (u < total) {
+                const GL &L = grp(g);
+                const unsigned we = L.word_end(wsl_of(kp, bid, g), u - wbase);
+                const typename Wfin<G>::T F = L.wkey(we);
+                cost = Wfin<G>::cost(F);
+                inv = Wfin<G>::invalid(F) ? 1u : 0u;
+                // a vocabulary token longer than G code points could span more than G atoms,
+                // beyond the walks: such a word is outside the engine's limits (status 3)
+                if (a.long_span) lng = we - L.word_start(wsl_of(kp, bid, g), u - wbase) > (unsigned)G ? 1u : 0u;
+            }
+            // per-group sums over this chunk: groups own contiguous lane ranges
+#pragma unroll
+            for (int k = 0; k < NG; k++) {
+                const unsigned lo = pre[k] > u0 ? pre[k] - u0 : 0u, hi = pre[k + 1] > u0 ? pre[k + 1] - u0 : 0u;
+                if (hi <= lo) continue;
+                const bool mine = lane >= lo && lane < (hi < 64u ? hi : 64u);
+                const unsigned cs = wave_incl_scan_add(mine ? cost : 0u);
+                const unsigned csum = __builtin_amdgcn_readlane(cs, 63);
+                const unsigned anyinv = (ballot(mine && inv) != 0 ? 1u : 0u) | (ballot(mine && lng) != 0 ? 2u : 0u);
+                if (lane == 0) { SSr(k).wtok += csum; SSr(k).inval |= anyinv; }
+            }
+        }
+#undef a
+#undef tv
+    }
+
+    // ---- C2: ids (lanes over all slots' tokens): the bulk pass, the hash pass, the walkers.  n_pend: the residual
+    //      tokens waiting in the wave's pending row; st: the driver's phase stamps (diagnostic builds)
+    static __device__ __forceinline__ void phase_c2(ConstKernArgs *kp, const unsigned bid, const unsigned lane, const bool raw,
+                                                    const bool len_only, unsigned &n_pend, [[maybe_unused]] Stamps &st) {
+#define a (kp->ea)
+#define tv (tv_of(kp))
+        unsigned char *const smem = lds();
+        unsigned pre[NG + 1], na_g[NG];
+        uint64_t obase[NG];       // staging element of the window's first token, per slot
+        const bool n16 = SW == 1 || (SW == 0 && a.staging16 != nullptr);   // int16 staging (uniform)
+        // per slot, bit 0: the window starts the string (raw '▁' + first atom); bit 1: a '\u2581'-compressed
+        // PRESPLIT window (its ' ' bytes expand to '\u2581' as raw mode's do)
+        unsigned firstmask = 0;
+        pre[0] = 0;
+#pragma unroll
+        for (int g = 0; g < NG; g++) {
+            const bool gv = !len_only && uni(SSr(g).inval) == 0 && uni(SSr(g).status) == 0 && uni(SSr(g).n_atoms) > 0;
+            pre[g + 1] = pre[g] + (gv ? uni(SSr(g).wtok) : 0u);
+            na_g[g] = uni(SSr(g).n_atoms);
+            firstmask |= ((raw && uni64(SSr(g).pos) == 0 ? 1u : 0u) | (uni(SSr(g).cpw) ? 2u : 0u)) << (2 * g);
+            const uint64_t e0 = uni64(SSr(g).sb) + uni(SSr(g).ntok);
+            obase[g] = e0;
+        }
+        const unsigned total = pre[NG];
+        // per-slot token range, atom count, first-window flag and staging row, in the slot's
+        // fin[] (dead after C1): a token start reads its slot's record with one LDS load
+        // instead of selecting among NG sets of registers
+        struct C2Slot {
+            uint32_t base, ntk, na, fw;
+            uint64_t ob;   // staging element (an offset, not a pointer: stores through a.staging* stay
+                           // global_store -- a pointer read back from LDS becomes a flat store, whose
+                           // lgkmcnt makes the next LDS wait on the store's completion)
+        };
+        static_assert(sizeof(typename GR::Fin) * GL::NA >= sizeof(C2Slot), "C2Slot fits fin[]");
+        if (lane == 0) {
+#pragma unroll
+            for (int g = 0; g < NG; g++) {
+                C2Slot &q = *reinterpret_cast<C2Slot *>(&grp(g).fin[0]);
+                q.base = pre[g]; q.ntk = pre[g + 1] - pre[g]; q.na = na_g[g]; q.fw = (firstmask >> (2 * g)) & 3u; q.ob = obase[g];
+            }
+        }
+        wave_sync();
+        // 16-lane first pass: a bulk pass resolves every token of one or two expanded bytes with
+        // ONE lookup (a one-byte token's root child, a two-byte token's root-table entry: .z = the
+        // id of the node reached) and lists the rest -- word starts ('\u2581'), newlines, tokens of
+        // three or more bytes -- by their token number in the rec[].cpos halves (dead in C2:
+        // entry i in group i / 256's rec[i % 256]).  A short list (< 64 tokens of <= 8 bytes: the
+        // walker would run with idle lanes) joins the wave's pending row, which is walked from
+        // the stored bytes once a round would overflow it (walk_pending); a longer one is walked
+        // below by the refill walker.
+        constexpr bool BULK = G == 16 && !BIG;
+        constexpr unsigned PEND_CAP = 64;   // residual tokens a wave's pending row holds (its scratch row)
+        unsigned wbeg = 0, wend = total;
+        // the list of tokens left for the walkers: in the rec[].cpos halves (dead in C2) -- G = 16:
+        // entry i in group i / 256's rec[i % 256]; G = 64 (one slot): rec[i]
+        auto list_ref = [&](unsigned i) -> uint16_t & {
+            if constexpr (G == 16)
+                return *reinterpret_cast<uint16_t *>(smem + (i >> 8) * GSTR + (i & 255u) * 4u);
+            else
+                return grp(0).rec[i].cpos;
+        };
+        // hash pass over n tokens (token number of entry i: src(i)): a token of at most
+        // TOKHASH_MAX_BYTES expanded bytes without a newline atom gets its id from ONE bucket load
+        // of the token hash table (dpt_internal.h); the others are listed, in order, at the front of
+        // the list for the walkers.  Returns their number (n without a table).
+        auto hash_pass = [&](unsigned n, auto src) -> unsigned {
+            const uint8_t *hbase = reinterpret_cast<const uint8_t *>(tv.pair16) + TOKHASH_OFFSET;
+            const TokHashHeader hh = *reinterpret_cast<const TokHashHeader *>(hbase);
+            if (!hh.max_probe) {
+                for (unsigned i = lane; i < n; i += 64u) list_ref(i) = (uint16_t)src(i);
+                return n;
+            }
+            const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(
+                (void *)(hbase + sizeof(TokHashHeader)), (short)0, (int)((hh.mask + 1u) * 16u), 0x00020000);
+            // token rounds of 64 per iteration, their loads before any store (a load waits for every
+            // older store of the wave; 1 or 4 rounds measured slower, r03)
+            constexpr int HP_U = DPT_HP_U;
+            unsigned r2 = 0;
+            for (unsigned i0 = 0; i0 < n; i0 += 64u * HP_U) {
+                unsigned tt[HP_U], hh2[HP_U], fpv[HP_U];
+                uint64_t oqv[HP_U];
+                bool hs[HP_U], inr[HP_U];
+#pragma unroll
+                for (int u = 0; u < HP_U; u++) {
+                    const unsigned i = i0 + 64u * (unsigned)u + lane;
+                    const bool in = i < n;
+                    const unsigned t = in ? src(i) : 0u;
+                    unsigned g = 0;
+#pragma unroll
+                    for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
+                    const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
+                    const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
+                    const unsigned k = in ? t - q.base : 0u;
+                    const unsigned jj = (unsigned)L.rec[k].smask;
+                    const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
+                    const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
+                    const unsigned p0 = L.aoff[jj];
+                    const unsigned nbytes = (typename GL::Idx)(L.aoff[j1] - p0);
+                    const unsigned fa = q.fw & 1u & (unsigned)(jj == 0);   // (bit 0: raw mode only)
+                    uint32_t h = 0, fp = 0;
+                    bool hashed;
+                    if constexpr (G == 16) {
+                        uint32_t w[4];
+                        unsigned E = 0;
+                        hashed = in && token_key<CH>(L.bytes, p0, nbytes, raw || (q.fw >> 1) != 0u, fa, w, E);
+                        if (hashed) tokhash(w[0], w[1], w[2], w[3], E, hh.seed, h, fp);
+                    } else {   // 64-lane rows (BLOOM-scale vocabularies): keys of up to 64 bytes
+                        hashed = in && token_hash_long<CH>(L.bytes, p0, nbytes, raw, fa, hh.seed, h, fp);
+                    }
+                    tt[u] = t; hh2[u] = h & hh.mask; fpv[u] = fp; oqv[u] = q.ob + k; hs[u] = hashed; inr[u] = in;
+                }
+                int32_t idv[HP_U];
+                if constexpr (HASH_BOTH) {
+                    // every round's two buckets (the key's two choices) at once, then the stores
+#pragma unroll
+                    for (int u = 0; u < HP_U; u++) {
+                        const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
+                        const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
+                        idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : e[2] == fpv[u] ? (int32_t)e[3] :
+                                 f[0] == fpv[u] ? (int32_t)f[1] : f[2] == fpv[u] ? (int32_t)f[3] : -1;
+                    }
                 } else {
-                    unsigned m = 0;
-                    if (lane == 0) m = atomicOr(a.part_ctr + (unsigned)NPART * PART_STRIDE, 1u << part);
-                    m = __builtin_amdgcn_readlane(m, 0) | (1u << part);
-                    const unsigned all = (npart >= 32u ? 0u : (1u << npart)) - 1u;
-                    if ((m & all) == all) {
-                        claimed_all = true;
-                    } else {   // the next unmarked partition after this one
-                        const unsigned free = ~m & all;
-                        const unsigned hi_free = free & ~((2u << part) - 1u);
-                        part = (unsigned)__builtin_ctz(hi_free ? hi_free : free);
+                    // every round's home bucket, then the partner buckets of the keys not found there
+                    // (one more load round for the wave, never a chain), then the stores
+#pragma unroll
+                    for (int u = 0; u < HP_U; u++) {
+                        const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
+                        idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : (e[2] == fpv[u] ? (int32_t)e[3] : INT32_MIN);
+                    }
+                    bool miss = false;
+#pragma unroll
+                    for (int u = 0; u < HP_U; u++) miss |= hs[u] && idv[u] == INT32_MIN;
+                    if (ballot(miss)) {
+#pragma unroll
+                        for (int u = 0; u < HP_U; u++) {
+                            if (hs[u] && idv[u] == INT32_MIN) {
+                                const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
+                                idv[u] = f[0] == fpv[u] ? (int32_t)f[1] : (f[2] == fpv[u] ? (int32_t)f[3] : -1);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < HP_U; u++) {
+                    if (hs[u]) {
+                        if (n16) a.staging16[oqv[u]] = (int16_t)idv[u];
+                        else a.staging[oqv[u]] = idv[u];
+                    }
+                }
+                // every lane read its entries above (list sources): the compacted rest lands below i0 + 64 * HP_U
+#pragma unroll
+                for (int u = 0; u < HP_U; u++) {
+                    const bool rest = inr[u] && !hs[u];
+                    const uint64_t m = ballot(rest);
+                    if (rest) list_ref(r2 + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) = (uint16_t)tt[u];
+                    r2 += (unsigned)__builtin_popcountll(m);
+                }
+            }
+            return r2;
+        };
+        if constexpr (BULK) {
+            const bool i16 = n16;
+            unsigned r = 0;
+            // The bulk pass over every selected token, 4 per lane per round of 256.  int16 ids from the
+            // pair table: all the window-set's lookups first, then all its stores -- a load waits for
+            // every OLDER vector-memory op of the wave, stores included (MI355X_MICROARCH.md: vmcnt
+            // counts loads and stores together, in issue order), so a store between two rounds of
+            // lookups put a store's full latency on every round.  (Every round's lookups before any
+            // store held the ids in registers and spilled: cfg2 -4.1 %, r03.)
+            constexpr int BU = DPT_BULK_U;   // tokens per lane per round
+            auto bulk_round = [&](unsigned t0, int32_t (&ix)[BU], unsigned (&kind)[BU], uint64_t (&oq)[BU]) {
+#pragma unroll
+                for (int u = 0; u < BU; u++) {
+                    const unsigned t = t0 + 64u * (unsigned)u + lane;
+                    const bool in = t < total;
+                    unsigned g = 0;
+#pragma unroll
+                    for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
+                    const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
+                    const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
+                    const unsigned k = in ? t - q.base : 0u;
+                    const unsigned jj = (unsigned)L.rec[k].smask;
+                    const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
+                    const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
+                    const unsigned p0 = L.aoff[jj];
+                    const unsigned nbytes = (uint8_t)(L.aoff[j1] - p0);
+                    const uint32_t *w = reinterpret_cast<const uint32_t *>(L.bytes) + (p0 >> 2);
+                    const unsigned two = __builtin_amdgcn_alignbyte(w[1], w[0], p0 & 3u);
+                    const unsigned b0 = two & 0xFFu, b1 = (two >> 8) & 0xFFu;
+                    // raw mode (and '\u2581'-compressed PRESPLIT windows, q.fw bit 1) expands ' ' (a word start),
+                    // '\n' and the string's first atom
+                    const unsigned expd = ((raw ? 1u : 0u) | (q.fw >> 1)) &
+                                          ((unsigned)(b0 == ' ') | (unsigned)(b0 == '\n') | (q.fw & 1u & (unsigned)(jj == 0)) |
+                                           ((unsigned)(nbytes == 2u) & ((unsigned)(b1 == ' ') | (unsigned)(b1 == '\n'))));
+                    const unsigned bulk = (unsigned)in & (unsigned)(nbytes - 1u <= 1u) & (expd ^ 1u);
+                    if constexpr (SW == 1)   // int16 ids: the 128-KB pair table (L1-resident for ASCII)
+                        ix[u] = bulk ? (int32_t)(nbytes == 1u ? 65536u + b0 : (b0 << 8) + b1) : 0;
+                    else
+                        ix[u] = bulk ? (nbytes == 1u ? tv.root_base + (int32_t)b0 : (int32_t)(tv.n_slots + (b0 << 8) + b1)) : 0;
+                    kind[u] = bulk ? nbytes : 0u;
+                    oq[u] = q.ob + k;
+                    const bool res = in && !bulk;
+                    const uint64_t m = ballot(res);
+                    if (res) list_ref(r + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) = (uint16_t)t;
+                    r += (unsigned)__builtin_popcountll(m);
+                }
+            };
+            for (unsigned t0 = 0; t0 < total; t0 += 64u * (unsigned)BU) {
+                int32_t ix[BU];
+                unsigned kind[BU];   // 0: not here, 1 / 2: a token of that many bytes
+                uint64_t oq[BU];
+                bulk_round(t0, ix, kind, oq);
+                if constexpr (SW == 1) {
+                    int16_t pv[BU];
+#pragma unroll
+                    for (int u = 0; u < BU; u++) pv[u] = tv.pair16[ix[u]];
+#pragma unroll
+                    for (int u = 0; u < BU; u++)
+                        if (kind[u]) a.staging16[oq[u]] = pv[u];
+                    continue;
+                }
+                int4 ent[BU];
+#pragma unroll
+                for (int u = 0; u < BU; u++) ent[u] = trie_slotA(tv, ix[u]);
+#pragma unroll
+                for (int u = 0; u < BU; u++) {
+                    if (kind[u]) {
+                        // the walker's rule: the id of the node reached when every step's check held
+                        const bool ok = kind[u] == 1u ? ent[u].y == 0 : (ent[u].y & 0x3FFFFFFF) != 0;
+                        const int32_t idv = ok ? ent[u].z : -1;
+                        if (i16) a.staging16[oq[u]] = (int16_t)idv;
+                        else a.staging[oq[u]] = idv;
                     }
                 }
             }
-            if (ne > nb || claimed_all) return;
+            wave_sync();
+            STAMP(5);
+            if (DPT_C2STOP == 1) r = 0;   // diagnostic: the bulk pass only
+            if (r > 0) {
+                r = hash_pass(r, [&](unsigned i) -> unsigned { return list_ref(i); });
+                wave_sync();
+            }
+            STAMP(6);
+            if (DPT_C2STOP == 2) r = 0;   // diagnostic: + the hash pass
+            wend = r;
+            if (r > 0 && r < (unsigned)PEND_CAP) {
+                uint4 ent = make_uint4(0u, 0u, 0u, 0u);
+                bool lng = false;
+                if (lane < r) {
+                    const unsigned t = list_ref(lane);
+                    unsigned g = 0;
+#pragma unroll
+                    for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
+                    const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
+                    const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
+                    const unsigned k = t - q.base;
+                    const unsigned jj = (unsigned)L.rec[k].smask;
+                    const unsigned nx = (unsigned)L.rec[k + 1].smask;
+                    const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
+                    const unsigned p0 = L.aoff[jj];
+                    const unsigned len = (uint8_t)(L.aoff[j1] - p0);
+                    const unsigned fi = q.fw & 1u & (unsigned)(jj == 0);
+                    const unsigned rl = (raw ? 1u : 0u) | (q.fw >> 1);   // raw mode's expansions
+                    lng = len > 8u;
+                    const uint64_t by = load_bytes(L.bytes, p0, lng ? 8u : len);
+                    const uint64_t out = q.ob + k;
+                    ent = make_uint4((uint32_t)out, ((uint32_t)(out >> 32) & 0xFFFFu) | (len << 16) | (fi << 24) | (rl << 25),
+                                     (uint32_t)by, (uint32_t)(by >> 32));
+                }
+                if (!ballot(lng)) {
+                    if (n_pend + r > (unsigned)PEND_CAP) {
+                        walk_pending(kp, bid, lane, n_pend);
+                        n_pend = 0;
+                    }
+                    if (lane < r) a.pend[(uint64_t)bid * 64u + n_pend + lane] = ent;
+                    n_pend += r;
+                    wend = 0;
+                }
+            }
         }
-    };
+        if constexpr (!BULK) {   // the walkers take what the hash pass leaves
+            if (total > 0) {
+                wend = hash_pass(total, [](unsigned i) -> unsigned { return i; });
+                wave_sync();
+            }
+        }
+        auto tok_at = [&](unsigned i) -> unsigned { return list_ref(i); };
+        // One token walk per lane; a lane whose token is resolved writes the id and takes the
+        // next token (ballot + mbcnt), so each iteration is one trie step for 64 tokens.  A
+        // token's bytes do not depend on the trie, so each iteration issues the trie load
+        // first and does the LDS work of the next byte / atom / token (known before the
+        // load returns: the token ends when its last atom's bytes run out) under it.
+        struct Tok {
+            unsigned jj, j1, cnt, lbase;
+            uint64_t seq;
+            uint64_t out;
+            bool rl;   // raw mode's expansions (raw mode, or a '\u2581'-compressed PRESPLIT window)
+        };
+        auto tstart = [&](unsigned t) -> Tok {
+            Tok T;
+            unsigned g = 0;
+#pragma unroll
+            for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
+            T.lbase = g * GSTR;
+            const GL &L = *reinterpret_cast<const GL *>(smem + T.lbase);
+            const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
+            const unsigned k = t - q.base;
+            T.jj = (unsigned)L.rec[k].smask;
+            const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
+            T.j1 = k + 1 < q.ntk ? nx : q.na;
+            T.rl = raw || (q.fw >> 1) != 0u;
+            T.seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[T.jj], L.atom_len(T.jj), 0, q.fw & 1u & (unsigned)(T.jj == 0)), T.rl, T.cnt);
+            T.out = q.ob + k;
+            return T;
+        };
+        // NW token walks per lane (tokens lane, lane + 64, ... first), so that many trie loads are
+        // in flight per lane in every iteration
+        constexpr int NW = 1;
+        bool active[NW];
+        Tok C[NW];
+        int32_t node[NW], nb[NW];
+        bool ok[NW];
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            active[w] = wbeg + lane + 64u * w < wend;
+            C[w].jj = C[w].j1 = C[w].cnt = C[w].lbase = 0; C[w].seq = 0; C[w].out = 0; C[w].rl = raw;
+            if (active[w]) C[w] = tstart(tok_at(wbeg + lane + 64u * w));
+            node[w] = 0; nb[w] = tv.root_base; ok[w] = true;
+        }
+        unsigned nxt = wbeg + 64u * NW;
+        for (;;) {
+            bool any = false;
+#pragma unroll
+            for (int w = 0; w < NW; w++) any |= active[w];
+            if (!ballot(any)) break;
+            int32_t sl[NW];
+            int4 ent[NW];
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                sl[w] = nb[w] + (int32_t)(C[w].seq & 0xFFu);
+                ent[w] = trie_slot4(tv, sl[w]);   // buffer load: inactive walks read harmlessly
+            }
+            // ---- under the loads: the next byte or atom
+            bool done[NW];
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                C[w].seq >>= 8;
+                C[w].cnt -= 1u;
+                const unsigned aend = (active[w] ? 1u : 0u) & (unsigned)(C[w].cnt == 0);
+                const unsigned dn = aend & (unsigned)(C[w].jj + 1 == C[w].j1);
+                done[w] = dn != 0;
+                if (aend & (dn ^ 1u)) {
+                    C[w].jj++;
+                    const GL &L = *reinterpret_cast<const GL *>(smem + C[w].lbase);
+                    C[w].seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[C[w].jj], L.atom_len(C[w].jj), 0, 0), C[w].rl, C[w].cnt);
+                }
+            }
+            // ---- the trie steps; finished walks write their id and take the next token
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                ok[w] &= ent[w].y == node[w];
+                node[w] = sl[w];
+                nb[w] = ent[w].x & BASE_MASK;
+                const uint64_t dm = ballot(done[w]);
+                if (done[w]) {
+                    const int32_t idv = ok[w] ? ent[w].z : -1;   // the id arrives with the token's last node
+                    if (n16) a.staging16[C[w].out] = (int16_t)idv;
+                    else a.staging[C[w].out] = idv;
+                    const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(dm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)dm, 0u));
+                    active[w] = uu < wend;
+                    if (active[w]) C[w] = tstart(tok_at(uu));
+                    node[w] = 0; nb[w] = tv.root_base; ok[w] = true;
+                }
+                nxt += (unsigned)__builtin_popcountll(dm);
+            }
+        }
+#undef a
+#undef tv
+    }
+
     // The wave's pending residual tokens (16-lane first pass, C2): one walk per lane from the entry's
     // bytes -- the C2 walker's byte rule (atom_from_info: raw mode expands the string's first atom to
     // '\u2581' + its bytes, ' ' to '\u2581', '\n' to "<0x0A>") as a byte generator, so one trie step
@@ -1071,18 +1425,19 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
     // staging element (.x, .y bits 0..15), byte length (.y bits 16..23, <= 8), first atom of the
     // string (.y bit 24), raw mode's expansions (.y bit 25: raw mode, or a '\u2581'-compressed PRESPLIT
     // window), the bytes (.z, .w).
-    auto walk_pending = [&](unsigned P) {
+    static __device__ __forceinline__ void walk_pending(ConstKernArgs *kp, unsigned bid, unsigned lane, unsigned P) {
+        const auto &a = kp->ea;
         wave_sync();   // the entries other lanes stored
         if (lane < P) {
             const uint4 e = a.pend[(uint64_t)bid * 64u + lane];
             const uint64_t out = (uint64_t)e.x | ((uint64_t)(e.y & 0xFFFFu) << 32);
             const unsigned len = (e.y >> 16) & 0xFFu;
-            const bool raw = RAW || ((e.y >> 25) & 1u);   // (shadows the mode's: this token's bytes)
+            const bool raw = RAW || ((e.y >> 25) & 1u);   // (this token's bytes, not the mode's)
             const bool fi = raw && ((e.y >> 24) & 1u);
             const uint64_t by = (uint64_t)e.z | ((uint64_t)e.w << 32);
             const unsigned b0 = (unsigned)(by & 0xFFu);
             const bool ws = (fi || (raw && b0 == ' ')) && a.ws_node >= 0;
-            int32_t node = ws ? a.ws_node : 0, nb = ws ? a.ws_base : tv.root_base, id = ws ? a.ws_id : -1;
+            int32_t node = ws ? a.ws_node : 0, nb = ws ? a.ws_base : tv_of(kp).root_base, id = ws ? a.ws_id : -1;
             bool ok = true;
             unsigned k = (ws && !fi) ? 1u : 0u;   // ws: '\u2581' is consumed (a first atom still emits its bytes)
             uint64_t pnd = 0;
@@ -1100,7 +1455,7 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
                 const int32_t sl = nb + (int32_t)(pnd & 0xFFu);
                 pnd >>= 8;
                 pc--;
-                const int4 en = trie_slot4(tv, sl);
+                const int4 en = trie_slot4(tv_of(kp), sl);
                 ok = ok && en.y == node;
                 node = sl;
                 nb = en.x & BASE_MASK;
@@ -1110,1827 +1465,12 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
             if (SW == 1 || (SW == 0 && a.staging16 != nullptr)) a.staging16[out] = (int16_t)id;
             else a.staging[out] = id;
         }
-    };
+    }
 
-    STAMP_DECL
-    WST_REC(0, WST_NOW());
-    [[maybe_unused]] unsigned wst_it = 0;
-
-    if (lane < (unsigned)NG) SSr(lane).active = 0;
-    wave_sync();
-
-    for (;;) {
-        KREFRESH();
-        // ---------------------------------------------------------- slots: fetch strings, find windows, prep
-        // Inactive slots are refilled together (one counter atomic, offsets loaded by one lane
-        // per slot), and every slot's window bytes are loaded before any is atomised, so the
-        // HBM round trips of the NG slots overlap.
-        unsigned busy = 0, prepared = 0;
-        for (;;) {
-            unsigned need = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) need |= uni(SSr(g).active) ? 0u : (1u << g);
-            if (need && !exhausted) {
-                // claims until every free slot has a string or every partition is used up (a claim
-                // that reaches a partition's end may return fewer strings than asked)
-                unsigned rem = need;
-                // partition-local strings [nb, ne) of partition cp into the free slots of rem, in order
-                auto assign = [&](uint64_t nb, uint64_t ne, unsigned cp) {
-                    const unsigned got = (unsigned)(ne - nb);
-                    if (lane < (unsigned)NG && ((rem >> lane) & 1u)) {
-                        const unsigned k = (unsigned)__builtin_popcount(rem & ((1u << lane) - 1u));
-                        if (k < got) {
-                            const uint64_t idx = nb + k;
-                            const uint64_t s = BIG ? (uint64_t)a.work_list[idx] : part_string(npart, cp, (unsigned)idx);
-                            uint64_t o0, o1;
-                            if constexpr (!BIG && (DPT_DIAG_PREP & 2)) { o0 = s * 256u; o1 = o0 + 256u; }   // diagnostic (cfg2)
-                            else { o0 = a.str_off[s]; o1 = a.str_off[s + 1]; }
-                            SlotState &S = SSr(lane);
-                            S.s = (uint32_t)s; S.sb = o0 - base_off; S.slen = (uint32_t)(o1 - o0); S.pos = 0; S.active = 1;
-                            S.status = o1 == o0 ? 2u : 0u;  // pretokenize_raw('') == [[]] -> IndexError
-                            S.ntok = 0; S.capsum = 0; S.abase = 0;
-                        }
-                    }
-                    for (unsigned q = 0; q < got; q++) rem &= rem - 1u;   // those slots are filled
-                };
-                while (rem && !claimed_all) {
-                    const unsigned n_need = (unsigned)__builtin_popcount(rem);
-                    uint64_t nb = 0, ne = 0;
-                    unsigned cp = 0;
-                    claim(n_need, nb, ne, cp);
-                    assign(nb, ne, cp);
-                }
-                if (claimed_all) exhausted = true;
-                wave_sync();
-            }
-            unsigned todo = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) todo |= (uni(SSr(g).active) && !((prepared >> g) & 1u)) ? (1u << g) : 0u;
-            if (!todo) break;
-            WinRegs<CH> W[NG];
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                if (!((todo >> g) & 1u)) continue;
-                const uint64_t sb = uni64(SSr(g).sb);
-                load_window<CH>(W[g], a.text + sb, raw ? nullptr : a.cut_mask + sb, uni64(SSr(g).pos), uni64(SSr(g).slen), raw, lane);
-            }
-            bool refill = false;
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                if (!((todo >> g) & 1u)) continue;
-                GL &L = grp(g);
-                SlotState &S = SSr(g);
-                const uint64_t slen = uni64(S.slen), pos = uni64(S.pos);
-                unsigned status = uni(S.status);
-                unsigned wlen = 0, na = 0, nw = 0, cpw = 0;
-                bool ok = status != 2;
-                if (ok) ok = window_bounds<CH>(W[g], slen, pos, mode, lane, wlen);
-                if (ok) ok = prep_window<CH, G, WIDE>(L, wsl_of(g), W[g], pos, wlen, mode, lane, na, nw, cpw);
-                if (ok) {
-                    if (lane == 0) { S.wlen = wlen; S.n_atoms = na; S.n_words = nw; S.wtok = 0; S.inval = 0; S.capb = 0; S.cpw = (uint8_t)cpw; }
-                    prepared |= 1u << g;
-                    busy++;
-                    continue;
-                }
-                // the string ends here: empty, or a word (or atom) too long for this pass -- the
-                // 2048-byte pass retries it, then the unbounded pass (status 3 is overwritten there)
-                if (status != 2) status = 3;
-                if (lane == 0) {
-                    const uint64_t s = S.s;
-                    if (status == 3) {
-                        // (the 512-byte pass, mid_kernel: its retry_* fields are the 2048-byte pass's list)
-                        uint32_t *cnt = (BIG && CH > 512) ? a.long_count : a.retry_count;
-                        uint32_t *lst = (BIG && CH > 512) ? a.long_list : a.retry_list;
-                        lst[atomicAdd(cnt, 1u)] = (uint32_t)s;
-                    }
-                    a.status[s] = (int32_t)status;
-                    if (a.capped) a.capped[s] = status == 2 ? 0 : -1;
-                    S.active = 0;
-                    a.counts[s] = 0;
-                }
-                refill = true;
-            }
-            wave_sync();
-            if (!refill || exhausted) break;
-        }
-        if (lane < (unsigned)NG && !((prepared >> lane) & 1u)) { SSr(lane).n_atoms = 0; SSr(lane).n_words = 0; SSr(lane).capb = 0; }
-        wave_sync();
-        if (busy == 0) break;
-        STAMP(0);
-
-        // ---------------------------------------------------------- A: match discovery (all slots)
-        KREFRESH();
-        if (DPT_STOP > 1) {
-            // A0 (16-lane rows, raw mode): slots whose window is pure ASCII -- atoms are its bytes --
-            // get every walk's first lookup here, byte-parallel with four loads in flight per lane;
-            // the walks it cannot finish (word starts, the string's first atom, '\n', and walks that
-            // go on past the two-byte root entry: ~6 % in cfg2 with the child filters) are marked
-            // (bit 4g + u of `mark`: atom 4 * lane + u of slot g) and redone by the walker below,
-            // which also takes every atom of the other slots.
-            unsigned a0mask = 0;
-            uint32_t mark = 0;
-            if constexpr (G == 16 && !BIG) {
-                if (!raw) {   // PRESPLIT: the '\u2581'-compressed windows (prep_window)
-#pragma unroll
-                    for (int g = 0; g < NG; g++)
-                        if (uni(SSr(g).n_atoms) > 0 && uni(SSr(g).cpw)) a0mask |= 1u << g;
-                } else {
-#pragma unroll
-                    for (int g = 0; g < NG; g++) {
-                        const unsigned wl = uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).wlen) : 0u;
-                        const uint32_t *b32 = reinterpret_cast<const uint32_t *>(grp(g).bytes);
-                        const uint32_t w0 = 4u * lane < wl ? b32[lane] : 0u;
-                        const unsigned nv = wl > 4u * lane ? min(wl - 4u * lane, 4u) : 0u;   // valid bytes in w0
-                        const uint32_t hi = w0 & (nv >= 4u ? 0x80808080u : ((1u << (8u * nv)) - 1u) & 0x80808080u);
-                        if (wl && !ballot(hi != 0)) a0mask |= 1u << g;
-                    }
-                }
-            }
-            unsigned nstart[NG];   // walker starts per slot: all atoms, or A0's marked ones
-#pragma unroll
-            for (int g = 0; g < NG; g++) nstart[g] = uni(SSr(g).n_atoms);
-            unsigned fwmask = 0;   // slots whose window starts the string (raw: '▁' + first atom)
-#pragma unroll
-            for (int g = 0; g < NG; g++) fwmask |= (raw && uni(SSr(g).pos) == 0 ? 1u : 0u) << g;
-            // One walk per lane.  Walk state: start atom j, the LDS byte offset of its slot's group,
-            // atoms matched so far (len), the trie node, the expanded bytes left of the current atom
-            // (seq, cnt) and its descriptor (info).  Finished walks take the next start (ballot +
-            // mbcnt), so the wave stays busy.
-            unsigned j = 0, lbase = 0, len = 0, cnt = 0, info = 0, t2 = 0, gsel = 0;
-            unsigned capm = 0;   // bit g: slot g's capb (set after the walks)
-            bool split = false;
-            int32_t nb = tv.root_base, node = 0;
-            uint64_t seq = 0;
-            M mask = 0;   // G = 16: bit 0 only (the single-atom span is a token)
-            // G = 16: the span of len atoms ending at end position e is a token: clear bit len-1
-            // of e's inverted end mask (the high half of rec[e]; one LDS atomic, no return)
-            auto end_token = [&](unsigned e, unsigned ln) {
-                uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + lbase);
-                __hip_atomic_fetch_and(&r32[e], ~(1u << (15u + ln)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            };
-            auto end_token_at = [&](unsigned lb, unsigned e, unsigned ln) {   // (the group at LDS byte lb)
-                uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + lb);
-                __hip_atomic_fetch_and(&r32[e], ~(1u << (15u + ln)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            };
-            auto grp_bytes_at = [&](unsigned lb, unsigned p) -> unsigned {   // window byte p (p < CH + 16) of that group
-                return reinterpret_cast<const GL *>(smem + lb)->bytes[p];
-            };
-            auto start_gj = [&](unsigned gs, unsigned jj) {
-                j = jj;
-                gsel = gs;
-                lbase = gs * GSTR;
-                const GL &L = *reinterpret_cast<const GL *>(smem + lbase);
-                info = ainfo_get(L, j, raw && ((fwmask >> gs) & 1u));
-                seq = atom_from_info<CH, WIDE>(L.bytes, info, raw, cnt);
-                nb = tv.root_base; node = 0; len = 0; mask = 0;
-                // The first two expanded bytes go through one lookup of the two-byte root table
-                // (TrieView): within atom j, or across its end when the word continues (then
-                // atom j+1 is loaded now instead of at the first atom end).
-                const unsigned b0 = (unsigned)(seq & 0xFFu);
-                if (cnt >= 2) {
-                    t2 = tv.n_slots + (b0 << 8) + (unsigned)((seq >> 8) & 0xFFu);
-                    split = false;
-                    seq >>= 16;
-                    cnt -= 2;
-                } else if (!(info & AInfo<CH>::STOP)) {
-                    info = ainfo_get(L, j + 1, false);
-                    seq = atom_from_info<CH, WIDE>(L.bytes, info, raw, cnt);
-                    t2 = tv.n_slots + (b0 << 8) + (unsigned)(seq & 0xFFu);
-                    split = true;
-                    seq >>= 8;
-                    cnt -= 1;
-                } else {
-                    t2 = 0;
-                }
-            };
-            if constexpr (G == 16 && !BIG) {
-                if (a0mask) {
-                    constexpr unsigned END = 0x100u;
-#pragma unroll
-                    for (int g = 0; g < NG; g++) {
-                        if (!((a0mask >> g) & 1u)) continue;
-                        // (window bytes in LDS = atoms: raw ASCII windows and '\u2581'-compressed ones alike)
-                        const unsigned wl = uni(SSr(g).n_atoms);
-                        const bool first = raw && uni(SSr(g).pos) == 0;
-                        const unsigned gbase = (unsigned)g * GSTR;
-                        const uint32_t *b32 = reinterpret_cast<const uint32_t *>(grp(g).bytes);
-                        const unsigned k0 = 4u * lane;
-                        if constexpr (A0_SWAR) {
-                            // The lane's four bytes as one 32-bit word (SWAR): every per-byte flag is bit 7 of
-                            // its byte, so one VALU op tests four bytes.  Views: w0 = bytes k0..k0+3 (b), n1w =
-                            // k0+1.. (the next byte), n2w = k0+2.. (the one after).
-                            constexpr uint32_t H = 0x80808080u;
-                            const uint32_t w0 = b32[lane], w1 = b32[lane + 1u];
-                            const uint32_t n1w = __builtin_amdgcn_alignbyte(w1, w0, 1u);
-                            const uint32_t n2w = __builtin_amdgcn_alignbyte(w1, w0, 2u);
-                            // lookups at (b, n1) as read: the table holds (b, '<')'s entry at (b, '\n') too,
-                            // and (b, END)'s flags of b are (b, anything)'s (dpt_api.cpp)
-                            uint2 ent[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++)
-                                ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[
-                                    __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)];
-                            // bytes past the window (END): byte q of the 8 is valid while q < nv
-                            const unsigned nv = wl > k0 ? min(wl - k0, 8u) : 0u;
-                            const uint64_t vm = nv >= 8u ? ~0ull : ((1ull << (8u * nv)) - 1ull);
-                            const uint32_t vlo = (uint32_t)vm, vhi = (uint32_t)(vm >> 32);
-                            const uint32_t v0 = vlo & H, v1 = __builtin_amdgcn_alignbyte(vhi, vlo, 1u) & H,
-                                           v2 = __builtin_amdgcn_alignbyte(vhi, vlo, 2u) & H;
-                            auto eq80 = [](uint32_t x, uint32_t c) -> uint32_t {   // bit 7 of each byte of x equal to c's
-                                const uint32_t t = x ^ c;
-                                return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-                            };
-                            const uint32_t sp0 = eq80(w0, 0x20202020u), sp1w = eq80(w1, 0x20202020u);
-                            const uint32_t nl0 = eq80(w0, 0x0A0A0A0Au), nl1w = eq80(w1, 0x0A0A0A0Au);
-                            const uint32_t sp1 = __builtin_amdgcn_alignbyte(sp1w, sp0, 1u), sp2 = __builtin_amdgcn_alignbyte(sp1w, sp0, 2u);
-                            const uint32_t nl1 = __builtin_amdgcn_alignbyte(nl1w, nl0, 1u), nl2 = __builtin_amdgcn_alignbyte(nl1w, nl0, 2u);
-                            const uint32_t special = sp0 | nl0 | ((first && lane == 0) ? 0x80u : 0u);   // the walker's
-                            const uint32_t norm = v0 & ~special;
-                            const uint32_t cont = v1 & ~sp1;   // n1 is in the word
-                            // the entries' flag bytes side by side (bit 0 root child, 1 b a token, 2 node b n1,
-                            // 3 it ends a token, 4 it is a leaf) and their child-filter bits for n2
-                            const uint32_t xs = __builtin_amdgcn_perm(ent[1].x, ent[0].x, 0x0C0C0400u) |
-                                                (__builtin_amdgcn_perm(ent[3].x, ent[2].x, 0x0C0C0400u) << 16);
-                            const uint32_t cb = n2w ^ ((n2w >> 5) & 0x07070707u);   // child_bit(byte) in each byte's low 5 bits
-                            const uint32_t f0 = ent[0].y >> (cb & 31u), f1 = ent[1].y >> ((cb >> 8) & 31u),
-                                           f2 = ent[2].y >> ((cb >> 16) & 31u), f3 = ent[3].y >> ((cb >> 24) & 31u);
-                            const uint32_t fb = (__builtin_amdgcn_perm(f1, f0, 0x0C0C0400u) |
-                                                 (__builtin_amdgcn_perm(f3, f2, 0x0C0C0400u) << 16)) << 7;
-                            const uint32_t tok1 = (xs << 7) & (xs << 6);
-                            const uint32_t has2 = norm & cont & (xs << 5);
-                            // go on past two bytes: n2 in the word with a child for it; '\n' at n1 or n2 ("<0x0A>")
-                            // always (the walker redoes such starts whole)
-                            const uint32_t more = has2 & ~(xs << 3) & (nl1 | (v2 & (nl2 | (~sp2 & fb))));
-                            const uint32_t tk1 = norm & tok1;                  // a one-atom token ends at k0+1+u
-                            const uint32_t tk2 = has2 & ~nl1 & (xs << 4);      // a two-atom token ends at k0+2+u
-                            uint32_t mk = ((v0 & special) | more) & H;   // walker starts
-                            if constexpr (A0_R2) {
-                                // Third-byte round: a walk that goes on past two plain bytes of the word takes
-                                // its root-table step (the node after the pair) and its third step here,
-                                // byte-parallel, and stays for the walker only if it goes on past three
-                                // (cfg4: ~97 % of these walks end there).  The three-atom token, if any, is
-                                // recorded here.  Slots with few such walks leave them to the walker.
-                                const uint32_t r2 = more & ~nl1 & ~nl2 & H;
-                                if (__builtin_popcountll(ballot(r2 != 0)) >= A0_R2_MIN) {
-                                    const uint32_t v3 = __builtin_amdgcn_alignbyte(vhi, vlo, 3u) & H;
-                                    const uint32_t sp3 = __builtin_amdgcn_alignbyte(sp1w, sp0, 3u);
-                                    const uint32_t nl3 = __builtin_amdgcn_alignbyte(nl1w, nl0, 3u);
-                                    const uint32_t n3w = __builtin_amdgcn_alignbyte(w1, w0, 3u);
-                                    constexpr int32_t OOB = 0x7FFFFFF;   // past the table: the buffer load returns zeros
-                                    int4 e2r[4], e3[4];
-#pragma unroll
-                                    for (int u = 0; u < 4; u++)   // the root table's entry of (b, n1)
-                                        e2r[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ? (int32_t)(tv.n_slots +
-                                                 __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)) : OOB);
-#pragma unroll
-                                    for (int u = 0; u < 4; u++)   // the node after n2
-                                        e3[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ?
-                                                (int32_t)((e2r[u].x & BASE_MASK) + ((n2w >> (8 * u)) & 0xFFu)) : OOB);
-                                    uint32_t c3 = 0, t3 = 0;
-#pragma unroll
-                                    for (int u = 0; u < 4; u++) {
-                                        const unsigned n3 = (n3w >> (8 * u)) & 0xFFu;
-                                        const unsigned ok3 = ((r2 >> (8 * u + 7)) & 1u) & (unsigned)(e3[u].y == (e2r[u].y & 0x3FFFFFFF));
-                                        const unsigned leaf3 = ((unsigned)e3[u].x >> 30) & 1u;
-                                        const unsigned in3 = ((v3 & ~sp3) >> (8 * u + 7)) & 1u;
-                                        const unsigned ch3 = (((unsigned)e3[u].w >> child_bit(n3)) & 1u) | ((nl3 >> (8 * u + 7)) & 1u);
-                                        t3 |= (ok3 & ((unsigned)e3[u].x >> 31)) << (8 * u + 7);
-                                        c3 |= (ok3 & (leaf3 ^ 1u) & in3 & ch3) << (8 * u + 7);
-                                    }
-                                    mk = ((v0 & special) | (more & ~r2) | c3) & H;
-                                    if (ballot(t3 != 0)) {   // a three-atom token ends at k0+3+u
-                                        uint32_t *q32 = reinterpret_cast<uint32_t *>(smem + gbase);
-#pragma unroll
-                                        for (int u = 0; u < 4; u++)
-                                            __hip_atomic_fetch_and(&q32[k0 + 3u + u],
-                                                                   ~(((t3 >> (8 * u + 7)) & 1u) << 18),
-                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                    }
-                                }
-                            }
-                            const uint32_t t2e = (tk2 << 8) | wave_shift_in(tk2 >> 24, 0u);
-                            // end k0+1+u: bit 0 of byte u of d a one-atom token, bit 1 a two-atom one
-                            const uint32_t d = ((tk1 & H) >> 7) | ((t2e & H) >> 6);
-                            uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
-                            if (ballot(d != 0)) {
-#pragma unroll
-                                for (int u = 0; u < 4; u++)
-                                    __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~(((d >> (8 * u)) & 3u) << 16),
-                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            }
-                            if (ballot((norm & ~tok1) != 0) && lane == 0) SSr(g).capb = 1;
-                            // the slot's marked atoms, in order, into its fin[] (free until phase B)
-                            const unsigned c = (unsigned)__builtin_popcount(mk);
-                            const unsigned incl = wave_incl_scan_add(c);
-                            unsigned o = incl - c;
-                            GL &Lg = grp(g);
-#pragma unroll
-                            for (int u = 0; u < 4; u++)
-                                if ((mk >> (8 * u + 7)) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
-                            nstart[g] = __builtin_amdgcn_readlane(incl, 63);
-                            continue;
-                        }
-                        // bytes k0 .. k0+7 (past the window: masked by wl below)
-                        const uint64_t w = (uint64_t)b32[lane] | ((uint64_t)b32[lane + 1u] << 32);
-                        auto byte_at = [&](unsigned q) -> unsigned {   // byte k0+q, END past the window
-                            return k0 + q < wl ? (unsigned)((w >> (8u * q)) & 0xFFu) : END;
-                        };
-                        uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
-                        bool nocap = false;
-                        unsigned tk1 = 0, tk2 = 0;
-                        // the packed byte-pair table over (byte, next byte): the flags of the first byte do
-                        // not depend on the second; four lookups in flight per lane
-                        uint2 ent[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const unsigned b = byte_at(u), n1 = byte_at(u + 1);
-                            const unsigned e1 = n1 == '\n' ? (unsigned)'<' : n1;
-                            ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[((b & 0xFFu) << 8) | (e1 & 0xFFu)];
-                        }
-                        // Per byte: tk1 bit u = a one-atom token ends at k0+1+u, tk2 bit u = a two-atom
-                        // token ends at k0+2+u (the end masks are written once below)
-                        // (flags as 0/1 integers combined with & and |: short-circuit forms become
-                        // exec-mask branches here)
-#pragma unroll
-                        for (int u = 0; u < 4; u++) {
-                            const unsigned k = k0 + (unsigned)u;
-                            const unsigned b = byte_at(u), n1 = byte_at(u + 1), n2 = byte_at(u + 2);
-                            const auto e = ent[u];
-                            const unsigned valid = (unsigned)(b != END);
-                            const unsigned special = (unsigned)(b == ' ') | (unsigned)(b == '\n') | ((unsigned)first & (unsigned)(k == 0));   // the walker's
-                            const unsigned norm = valid & (special ^ 1u);
-                            // n1 ends the word: the lookup was the atom's own root slot
-                            const unsigned wend = (unsigned)(n1 == END) | (unsigned)(n1 == ' ');
-                            const unsigned xterm = ((unsigned)e.x >> 3) & 1u, xleaf = ((unsigned)e.x >> 4) & 1u;
-                            const unsigned tok1 = (unsigned)e.x & ((unsigned)e.x >> 1) & 1u;
-                            const unsigned node2 = ((unsigned)e.x >> 2) & 1u;
-                            const unsigned filt = (unsigned)e.y;
-                            nocap |= (norm & (tok1 ^ 1u)) != 0;
-                            // a node after two bytes: n1 = '\n' leaves the walk inside "<0x0A>" after
-                            // its '<'; otherwise atom k+1 is consumed (the span k .. k+2)
-                            const unsigned has2 = norm & (wend ^ 1u) & node2;
-                            const unsigned nl1 = (unsigned)(n1 == '\n');
-                            const unsigned e2 = nl1 ? (unsigned)'0' : (n2 == '\n' ? (unsigned)'<' : n2);
-                            const unsigned more = has2 & (xleaf ^ 1u) & (nl1 | ((unsigned)(n2 != END) & (unsigned)(n2 != ' '))) &
-                                                  ((filt >> child_bit(e2)) & 1u);
-                            tk1 |= (norm & tok1) << u;
-                            tk2 |= (has2 & (nl1 ^ 1u) & xterm) << u;
-                            mark |= ((valid & special) | more) << (4 * g + u);
-                        }
-                        // end k0+1+u: tk1 bit u, and tk2 bit u-1 (u = 0: the previous lane's bit 3)
-                        const unsigned t2e = ((tk2 << 1) & 0xEu) | wave_shift_in((tk2 >> 3) & 1u, 0u);
-                        if (ballot((tk1 | t2e) != 0)) {
-                            // (lane l's dwords are 4l+1 .. 4l+4: lanes l, l+8, l+16, l+24 of a 32-lane group hit
-                            // one bank; a rotated order (r03) and a transposed one -- round q's lane l taking
-                            // end 64q+l+1, its bits gathered by ds_bpermute (r04) -- cost VGPR spills instead)
-#pragma unroll
-                            for (int u = 0; u < 4; u++)
-                                __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~((((tk1 >> u) & 1u) << 16) | (((t2e >> u) & 1u) << 17)),
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        if (ballot(nocap) && lane == 0) SSr(g).capb = 1;
-                        // the slot's marked atoms, in order, into its fin[] (free until phase B)
-                        const unsigned mg = (mark >> (4 * g)) & 15u;
-                        const unsigned c = (unsigned)__builtin_popcount(mg);
-                        const unsigned incl = wave_incl_scan_add(c);
-                        unsigned o = incl - c;
-                        GL &Lg = grp(g);
-#pragma unroll
-                        for (int u = 0; u < 4; u++)
-                            if ((mg >> u) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
-                        nstart[g] = __builtin_amdgcn_readlane(incl, 63);
-                    }
-                }
-            }
-            // ASCII walker: the marked starts of A0 slots (pure-ASCII raw windows: an atom is one byte, a
-            // word start ' ' is '\u2581' = the trie node ws_node, '\n' is "<0x0A>", the string's first
-            // atom '\u2581' + its byte) walked byte by byte without the generic walker's atom
-            // descriptors.  A "more" start (a plain byte whose walk goes past A0's two-byte lookup, its one-
-            // and two-atom tokens already recorded by A0) repeats that lookup in the root table and goes on
-            // from the node after two bytes.  The generic walker below takes the other slots.
-            if constexpr (G == 16 && !BIG) {
-                if (a0mask) {
-                    unsigned fpre[NG + 1];
-                    fpre[0] = 0;
-#pragma unroll
-                    for (int g = 0; g < NG; g++) {
-                        fpre[g + 1] = fpre[g] + (((a0mask >> g) & 1u) ? nstart[g] : 0u);
-                        if ((a0mask >> g) & 1u) nstart[g] = 0;
-                    }
-                    const unsigned ftotal = fpre[NG];
-                    const int32_t wsn = a.ws_node, wsb = a.ws_base;
-                    const unsigned wst = a.ws_id >= 0 ? 1u : 0u;   // '\u2581' alone is a token
-                    const int32_t rb = tv.root_base;
-                    const unsigned nsl = tv.n_slots;
-                    // "<0x0A>" after its '<': with pc bytes left the next is byte 5 - pc of "0x0A>" (a 32-bit
-                    // constant and '>' instead of a 64-bit register pair of the bytes still to come)
-                    auto nl_byte = [](unsigned pc) -> unsigned { return pc >= 2u ? (0x41307830u >> (8u * (5u - pc))) & 0xFFu : 0x3Eu; };
-                    unsigned fj = 0, flen = 0, fp = 0, fwl = 0, cur = 0, pc = 0, fgs = 0, fl = 0, isr = 0, one = 0;
-                    // (the walker's "capb" flags, per lane and slot, written once after the walk)
-                    int32_t fnode = 0, fnb = 0, ft2 = 0;
-                    bool act = false;
-                    // a start: (walk state, or over at once -- the '\u2581' node missing / the word ends)
-                    auto fstart = [&](unsigned uu) -> bool {
-                        unsigned gs = 0;
-#pragma unroll
-                        for (int g = 1; g < NG; g++) gs += uu >= fpre[g] ? 1u : 0u;
-                        unsigned base = 0;
-#pragma unroll
-                        for (int g = 0; g < NG; g++) base = (gs == (unsigned)g) ? fpre[g] : base;
-                        fgs = gs;
-                        fl = gs * GSTR;
-                        const GL &L = *reinterpret_cast<const GL *>(smem + fl);
-                        const unsigned jj = L.fin[uu - base].v;
-                        fj = jj;
-                        fwl = SSr(gs).n_atoms;   // (= the LDS bytes: one per atom)
-                        const unsigned b0 = L.bytes[jj];
-                        isr = 0; one = 0; pc = 0;
-                        if (((fwmask >> gs) & 1u) && jj == 0) {   // '\u2581' + b0: one atom
-                            fnode = wsn; fnb = wsb; cur = b0; fp = 1; flen = 0;
-                            return wsn >= 0;
-                        }
-                        if (b0 == '\n') {
-                            fnode = 0; fnb = rb; cur = '<'; pc = 5; fp = jj + 1; flen = 0;
-                            return true;
-                        }
-                        if (b0 != ' ') {   // a "more" start: the root table over (b0, next byte)
-                            const unsigned n1 = L.bytes[jj + 1];
-                            isr = 1; one = 1;
-                            if (n1 == '\n') {   // inside atom jj+1's "<0x0A>" after its '<'
-                                ft2 = (int32_t)(nsl + (b0 << 8) + (unsigned)'<');
-                                flen = 1; cur = '0'; pc = 4; fp = jj + 2;
-                            } else {             // two atoms; A0 saw a third that is no word start
-                                ft2 = (int32_t)(nsl + (b0 << 8) + n1);
-                                const unsigned n2 = L.bytes[jj + 2];
-                                flen = 2; fp = jj + 3;
-                                if (n2 == '\n') { cur = '<'; pc = 5; }
-                                else cur = n2;
-                            }
-                            return true;
-                        }
-                        // a word start: the atom '\u2581' is the node ws_node
-                        if (wsn < 0) return false;
-                        fnode = wsn; fnb = wsb; flen = 1; one = wst;
-                        if (wst) end_token_at(fl, jj + 1, 1);
-                        if (jj + 1 >= fwl) return false;
-                        const unsigned n1 = L.bytes[jj + 1];
-                        if (n1 == ' ') return false;
-                        fp = jj + 2;
-                        if (n1 == '\n') { cur = '<'; pc = 5; }
-                        else cur = n1;
-                        return true;
-                    };
-                    unsigned nxt = DPT_STOP == 21 ? ftotal : 0u;   // diagnostic: A0 only
-                    for (;;) {
-                        {
-                            const uint64_t im = ballot(!act);
-                            const unsigned nidle = (unsigned)__builtin_popcountll(im);
-                            if (nxt < ftotal && (nidle >= A_REFILL || ftotal - nxt <= nidle)) {
-                                if (!act) {
-                                    const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
-                                    if (uu < ftotal) {
-                                        act = fstart(uu);
-                                        capm |= (unsigned)(!act && !one) << fgs;   // the start atom is no token
-                                    }
-                                }
-                                nxt += nidle;
-                            }
-                        }
-                        // (a start can be over at once, so a refill may leave every lane idle with starts left:
-                        // the step then runs with no lane active and changes nothing -- one back edge, so
-                        // the walk state stays in its registers across it)
-                        if (!ballot(act) && nxt >= ftotal) break;
-                        // the next raw byte, read before the trie load returns (masked off past the window)
-                        // (kept ahead of the load by a scheduling barrier: else its address register may
-                        // reuse the load's dead .z and wait for it)
-                        const unsigned nbv = grp_bytes_at(fl, fp);
-                        __builtin_amdgcn_sched_barrier(0);
-                        const int32_t t = isr ? ft2 : fnb + (int32_t)cur;
-                        const int4 ent = trie_slotA(tv, t);
-                        const unsigned y = (unsigned)ent.y;
-                        const unsigned av = act ? 1u : 0u;
-                        // (both lookups' tests as 0/1 integers: a ?: over them became an exec-mask diamond)
-                        const unsigned okr = ((y >> 30) & 1u) & (unsigned)((y & 0x3FFFFFFFu) != 0);
-                        const unsigned okp = (unsigned)(ent.y == fnode);
-                        const unsigned ok = av & ((isr & okr) | ((isr ^ 1u) & okp));
-                        fnode = isr ? (int32_t)(y & 0x3FFFFFFFu) : t;
-                        fnb = ent.x & BASE_MASK;
-                        const unsigned leaf = ((unsigned)ent.x >> 30) & 1u;
-                        // plain step: cur consumed; the atom ends unless its expansion has bytes left
-                        const unsigned aend = ok & (isr ^ 1u) & (unsigned)(pc == 0);
-                        const unsigned inexp = (isr ^ 1u) & (unsigned)(pc != 0);
-                        cur = inexp ? nl_byte(pc) : cur;
-                        pc = inexp ? pc - 1u : pc;
-                        isr = 0;
-                        flen += aend;
-                        const unsigned term = aend & ((unsigned)ent.x >> 31);
-                        one |= term & (unsigned)(flen == 1);
-                        if (term) end_token_at(fl, fj + flen, flen);
-                        // the next atom (after an atom end): a byte of the word, "<0x0A>", or the end
-                        const unsigned past = (unsigned)(fp >= fwl) | (unsigned)(flen == 16u) | (unsigned)(nbv == ' ');
-                        const unsigned stop = aend & past;
-                        const unsigned nxa = aend & (past ^ 1u);
-                        const unsigned isnl = (unsigned)(nbv == '\n');
-                        cur = nxa ? (isnl ? (unsigned)'<' : nbv) : cur;
-                        pc = (nxa & isnl) ? 5u : pc;
-                        fp += nxa;
-                        const unsigned nochild = (((unsigned)ent.w >> child_bit(cur)) & 1u) ^ 1u;
-                        const unsigned done = av & ((ok ^ 1u) | leaf | stop | nochild);
-                        capm |= (done & (one ^ 1u)) << fgs;
-                        act = act && !done;
-                    }
-                }
-            }
-            // Byte-stream walker (the 64-lane 256-byte kernel, non-raw modes -- BLOOM-scale byte-level
-            // vocabularies): no expansions, so a walk from atom j consumes the window's bytes from
-            // aoff[j] on, and one u16 of bf[] per step says which byte comes next and whether an atom
-            // ends (or the word) before it.  The first two bytes go through the root table; each later
-            // step is one 8-byte trie load plus that one LDS read under it (the generic walker below reads
-            // the next atom's descriptor and bytes -- four LDS reads and the expansion logic -- per step).
-            // Whole-word shortcut (not when edges are an output): a word that is ONE vocabulary token has
-            // cost 1 and that token as its only shortest tokenization (every other split costs >= 2:
-            // dp_tokenize.py:24-47 then selects it); the walk from its first atom reaching the word's end
-            // on a token marks it (scf[]) and B pushes only that edge (forward_lanes64).  (Walking the word
-            // starts first, to skip the other atoms of such words, left the 64 lanes idle behind the
-            // longest walks: BLOOM 4.90 -> 5.45 ms, r05f; and so did one pass over a word-starts-first list that
-            // skips the starts inside words already known to be one token: +2 %, r05k.)
-            if constexpr (GL::BSTREAM && !BIG) {
-                if (!raw && nstart[0] > 0) {
-                    const unsigned na_ = nstart[0];
-                    nstart[0] = 0;   // (the generic walker gets nothing)
-                    GL &L = grp(0);
-                    const bool wsc = PLAIN || a.edges == nullptr;
-                    const int32_t rb = tv.root_base;
-                    const unsigned nsl = tv.n_slots;
-                    for (unsigned jj = lane; jj < na_; jj += 64u) L.scf[jj] = 0;
-                    {
-                        const unsigned tot = na_;
-                        unsigned bj = 0, bp = 0, blen = 0, bcur = 0;
-                        int32_t bnode = 0, bnb = 0;
-                        bool bisr = false, bact = false, bws = false;
-                        uint64_t bmask = 0;
-                        // a start: p = aoff[j]; two bytes of the word: the root table, else one root step
-                        auto bstart = [&](unsigned jj) {
-                            bj = jj;
-                            const unsigned p = L.aoff[jj];
-                            const unsigned f1 = L.bf[p + 1u];   // p + 1 <= wlen
-                            const unsigned f0 = L.bf[p];
-                            const unsigned b0 = f0 & 0xFFu;
-                            bws = wsc && (f0 & BF_STOP) != 0;   // a word's first atom
-                            bisr = (f1 & BF_STOP) == 0;         // the word has a second byte
-                            bcur = bisr ? (nsl + (b0 << 8) + (f1 & 0xFFu)) : (unsigned)rb + b0;
-                            bp = p;
-                            bnode = 0; bnb = rb; blen = 0; bmask = 0;
-                        };
-                        unsigned nxt2 = DPT_STOP == 21 ? tot : 0u;
-                        for (;;) {
-                            {
-                                const uint64_t im = ballot(!bact);
-                                const unsigned nidle = (unsigned)__builtin_popcountll(im);
-                                if (nxt2 < tot && (nidle >= A_REFILL64 || tot - nxt2 <= nidle)) {
-                                    if (!bact) {
-                                        const unsigned uu = nxt2 + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
-                                        if (uu < tot) { bact = true; bstart(uu); }
-                                    }
-                                    nxt2 += nidle;
-                                }
-                            }
-                            if (!ballot(bact)) break;
-                            const int2 e2 = trie_slot(tv, (int32_t)bcur);
-                            // under the load: the flags (and byte) after this step's last byte
-                            const unsigned q = bp + (bisr ? 2u : 1u);   // <= wlen
-                            const unsigned fq = L.bf[q];
-                            const unsigned fq1 = bisr ? (unsigned)L.bf[bp + 1u] : 0u;
-                            const unsigned av = bact ? 1u : 0u;
-                            const unsigned y = (unsigned)e2.y;
-                            unsigned ok;
-                            if (bisr) {
-                                // root table: .y = node after two bytes | first byte exists << 30 | it ends a token << 31
-                                const unsigned tok1 = av & (unsigned)((fq1 & BF_ATOM) != 0) & (y >> 30) & (y >> 31);
-                                bmask |= (uint64_t)tok1;
-                                blen = (fq1 & BF_ATOM) ? 1u : 0u;
-                                ok = av & (y >> 30) & (unsigned)((y & 0x3FFFFFFFu) != 0);
-                                bnode = (int32_t)(y & 0x3FFFFFFFu);
-                            } else {
-                                ok = av & (unsigned)(e2.y == bnode);
-                                bnode = (int32_t)bcur;
-                            }
-                            bnb = e2.x & BASE_MASK;
-                            const unsigned leaf = ((unsigned)e2.x >> 30) & 1u;
-                            const unsigned aend = ok & (unsigned)((fq & BF_ATOM) != 0);
-                            blen += aend;
-                            const unsigned term = aend & ((unsigned)e2.x >> 31);
-                            bmask |= term ? 1ull << (blen - 1u) : 0ull;
-                            const unsigned stop = aend & (unsigned)((fq & BF_STOP) != 0);
-                            const unsigned done = av & ((ok ^ 1u) | leaf | stop | (unsigned)(blen == (unsigned)G));
-                            bcur = (unsigned)bnb + (fq & 0xFFu);
-                            bp = q;
-                            bisr = false;
-                            if (done) {
-                                L.rec[bj].smask = bmask;
-                                if (bws && (stop & term)) L.scf[bj] = 1;   // the word is one token
-                            }
-                            capm |= done & (((unsigned)bmask & 1u) ^ 1u);
-                            bact = bact && !done;
-                        }
-                    }
-                }
-            }
-            unsigned pre[NG + 1];
-            pre[0] = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) pre[g + 1] = pre[g] + nstart[g];
-            const unsigned total = pre[NG];
-            auto start = [&](unsigned uu) {
-                unsigned gs = 0;
-#pragma unroll
-                for (int g = 1; g < NG; g++) gs += uu >= pre[g] ? 1u : 0u;
-                unsigned base = 0;
-#pragma unroll
-                for (int g = 0; g < NG; g++) base = (gs == (unsigned)g) ? pre[g] : base;
-                unsigned jj = uu - base;
-                if constexpr (G == 16 && !BIG)
-                    if ((a0mask >> gs) & 1u) jj = grp(gs).fin[jj].v;   // A0 slot: its marked list
-                start_gj(gs, jj);
-            };
-            // Refills are batched: idle lanes take new starts only once A_REFILL of them are idle
-            // (or the remaining starts fit), so the refill code runs on a fraction of the steps.
-            bool active = false;
-            unsigned nxt = DPT_STOP == 21 ? total : 0u;   // diagnostic: A0 only
-            for (;;) {
-                {
-                    const uint64_t im = ballot(!active);
-                    const unsigned nidle = (unsigned)__builtin_popcountll(im);
-                    if (nxt < total && (nidle >= (G == 64 ? A_REFILL64 : A_REFILL) || total - nxt <= nidle)) {
-                        if (!active) {
-                            const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
-                            if (uu < total) { active = true; start(uu); }
-                        }
-                        nxt += nidle;
-                    }
-                }
-                if (!ballot(active)) break;
-                const int32_t t = t2 ? (int32_t)t2 : nb + (int32_t)(seq & 0xFFu);
-                // (the 64-lane kernels' walks read the 8-byte slots -- no child filter: half the footprint
-                // of a BLOOM-scale trie, one more failing lookup per walk)
-                int4 ent;
-                if constexpr (G == 64) {
-                    const int2 e2 = trie_slot(tv, t);
-                    ent = make_int4(e2.x, e2.y, 0, -1);
-                } else {
-                    ent = trie_slotA(tv, t);   // buffer load: inactive lanes read harmlessly
-                }
-                // The step as selects (few exec-mask branches: their scalar bookkeeping costs issue
-                // slots like the vector work does).  Root-table entry (t2): .y = node after two
-                // bytes (0: none) | first byte exists << 30 | first byte ends a token << 31; .x =
-                // that node's base word.  Plain step: the slot is the child iff its check is node.
-                // (flags as 0/1 integers: && / || chains become exec-mask branches here)
-                const unsigned act = active ? 1u : 0u;
-                const unsigned isr = (unsigned)(t2 != 0);
-                const unsigned y30 = ((unsigned)ent.y >> 30) & 1u, y31 = (unsigned)ent.y >> 31;
-                const unsigned rsplit = act & isr & (split ? 1u : 0u);   // atom j ended after the first byte
-                const unsigned rtok1 = rsplit & y30 & y31;
-                const unsigned ok = act & (isr ? (y30 & (unsigned)((ent.y & 0x3FFFFFFF) != 0)) : (unsigned)(ent.y == node));
-                len = rsplit ? 1u : len;
-                mask = rtok1 ? (M)1 : mask;
-                if constexpr (G == 16)
-                    if (rtok1) end_token(j + 1, 1);
-                seq = isr ? seq : seq >> 8;
-                cnt = isr ? cnt : cnt - 1u;
-                t2 = 0;
-                node = isr ? (ent.y & 0x3FFFFFFF) : t;   // read only while ok
-                nb = ent.x & BASE_MASK;
-                const unsigned leaf = ((unsigned)ent.x >> 30) & 1u;
-                const unsigned aend = ok & (unsigned)(cnt == 0);   // atom j+len-1 ends: span j..j+len is a candidate
-                len += aend;
-                const unsigned term = aend & ((unsigned)ent.x >> 31);
-                if constexpr (G == 16) {
-                    mask = (term & (unsigned)(len == 1)) ? (M)1 : mask;
-                    if (term) end_token(j + len, len);
-                } else {
-                    mask |= term ? (M)1 << (len - 1) : (M)0;
-                }
-                const unsigned cont = aend & ((leaf | (unsigned)((info & AInfo<CH>::STOP) != 0) | (unsigned)(len == (unsigned)G)) ^ 1u);
-                {
-                    // the next atom, read by every lane (j + len <= n_atoms: in the window's arrays)
-                    // (reading it a step ahead, before the trie load returns, measured slower: r03z)
-                    const GL &L = *reinterpret_cast<const GL *>(smem + lbase);
-                    unsigned cn = 0;
-                    const unsigned inf = ainfo_get(L, j + len, false);
-                    const uint64_t sq = atom_from_info<CH, WIDE>(L.bytes, inf, raw, cn);
-                    info = cont ? inf : info;
-                    seq = cont ? sq : seq;
-                    cnt = cont ? cn : cnt;
-                }
-                // the walk ends at a failed lookup, at a leaf or a walk-ending atom, or when the
-                // node has no child for the next byte (over without that lookup)
-                const unsigned nochild = (((unsigned)ent.w >> child_bit((unsigned)(seq & 0xFFu))) & 1u) ^ 1u;
-                const unsigned done = act & ((ok ^ 1u) | (aend ? ((cont ^ 1u) | nochild) : (leaf | nochild)));
-                if constexpr (G != 16) {
-                    if (done) {
-                        GL &L = *reinterpret_cast<GL *>(smem + lbase);
-                        L.rec[j].smask = mask;   // G = 16: end masks, set by end_token
-                    }
-                }
-                capm |= (done & (((unsigned)mask & 1u) ^ 1u)) << gsel;
-                active = active && !done;
-            }
-            // the slots whose walk found an atom that is no token by itself
-#pragma unroll
-            for (int g = 0; g < NG; g++)
-                if (ballot((capm >> g) & 1u) && lane == 0) SSr(g).capb = 1;
-        }
-        wave_sync();
-        STAMP(1);
-
-        // ---------------------------------------------------------- B: forward recurrence
-        KREFRESH();
-        bool lane_mode = false;   // B ran per chunk and did C0 and C1 itself (G = 16, capless, no edges)
-        if (DPT_RUN_B) {
-            GL &L = grp(mg);
-            const unsigned na = SSr(mg).n_atoms;
-            unsigned imax = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) imax = max(imax, uni(SSr(g).n_atoms));
-            // Steps past a slot's own n_atoms (up to the wave's imax <= CH) compute garbage that
-            // lands in fin[] entries nobody reads, so the loop body has no per-slot guard.
-            // Recording the edges (f1) and the uncapped DP (f2) are hoisted out as loop versions.
-            // CAPM 0: the reference's capped DP (cost[i] <= i, dp_tokenize.py:28); 1: uncapped with
-            // "inf" (inspect_tokenizer.py:77-86); 2: neither -- exact for both when every atom of
-            // the wave's windows is a token by itself (then cost[i] <= i - ws on a valid path, so
-            // the cap never wins and nothing is unreachable)
-            auto forward = [&](auto EDGES, auto CAPM) {
-                constexpr bool edges = decltype(EDGES)::value;
-                constexpr int capm = decltype(CAPM)::value;
-                // st (lane d, candidate j = i-1-d) = (cost[j]+1) << 16 | invalid[j] << 15 | G[j]
-                constexpr unsigned ST0 = 0x10000u;   // word start: cost 0, reachable, G 0
-                unsigned ws = 0;
-                unsigned st = d == 0 ? ST0 : 0u;
-                unsigned cpj = 0;
-                if constexpr (G == 16) {
-                    // Lane d carries x = rec[j] (its cpos) and its state in key form:
-                    // (cost[j]+1) << 16 | invalid[j] << 15 | (0x7FFF - G[j]), so the candidate key is
-                    // min(st, (st | 0x7FFF) - span); a dead span is one sign-extended bit of the
-                    // inverted end mask of i (read by every lane of the row).
-                    constexpr unsigned SK0 = 0x17FFFu;   // word start in key form
-                    const uint32_t *rec32 = reinterpret_cast<const uint32_t *>(L.rec);
-                    const unsigned sbit = 16u + d;
-                    unsigned sk = d == 0 ? SK0 : 0u;
-                    unsigned x = d == 0 ? rec32[0] : 0xFFFF0000u;
-                    unsigned wsh = 0;                    // word start << 16
-                    uint32_t nx = rec32[1];
-                    // one step; (sk, x) in, (sk', x') out -- called alternately on two register sets
-                    // so the DPP shifts need no copies
-                    auto step = [&](unsigned i, unsigned skI, unsigned xI, unsigned &skO, unsigned &xO) {
-                        const uint32_t cur = nx;
-                        nx = rec32[i + 1];                         // i+1 <= CH+1 < NA: always in bounds
-                        const unsigned span = (cur - xI) & 0x7FFFu;  // cp(j..i); borrows only move up
-                        unsigned kv = (skI | 0x7FFFu) - span;
-                        kv = skI < kv ? skI : kv;
-                        const unsigned key = kv | (unsigned)__builtin_amdgcn_sbfe((int)cur, sbit, 1);
-                        unsigned r = row_min_u32(key);
-                        if constexpr (capm == 0) {
-                            const unsigned capkey = ((i << 16) | 0xFFFFu) - wsh;
-                            r = r < capkey ? r : capkey;
-                        }
-                        const uint64_t gmb = ballot(key == r);
-                        const uint64_t emb = ballot((key ^ r) < 0x8000u);
-                        if (d == 0) {
-                            const unsigned sh = 16u * mg;
-                            const unsigned gs = (unsigned)(gmb >> sh), es = (unsigned)(emb >> sh);
-                            // lowest set bit of the row; bits of other rows only land in fields
-                            // of positions C1 never reads (see Group<16>)
-                            const unsigned dg = ffbl(gs), de = ffbl(es);
-                            L.fin[i].v = (uint8_t)(dg | (de << 4));
-                            L.rec[i].smask = Wfin<G>::pack(r);   // rec[i] was consumed at step i-1
-                            if constexpr (edges)
-                                if (i <= na) a.edges[SSr(mg).sb + SSr(mg).abase + i - 1] = es & 0xFFFFu;
-                        }
-                        const bool wend = (int16_t)cur < 0;     // CP_WS: word starts and the window end
-                        wsh = wend ? (i << 16) : wsh;
-                        unsigned nxt = r + 0x10000u;
-                        if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;   // unreachable: cost stays inf
-                        skO = row_shift_in(skI, wend ? SK0 : nxt);
-                        xO = row_shift_in(xI, cur);
-                    };
-                    unsigned sk2, x2;
-                    unsigned i = 1;
-                    for (; i + 1 <= imax; i += 2) {
-                        step(i, sk, x, sk2, x2);
-                        step(i + 1, sk2, x2, sk, x);
-                    }
-                    if (i <= imax) step(i, sk, x, sk2, x2);
-                } else {
-                    const uint64_t m0 = na > 0 ? L.rec[0].smask : 0ull;
-                    unsigned mlo = d == 0 ? (unsigned)m0 : 0u, mhi = d == 0 ? (unsigned)(m0 >> 32) : 0u;
-                    for (unsigned i = 1; i <= imax; i++) {
-                        const unsigned cur = L.rec[i].cpos;
-                        const uint64_t mi = L.rec[i].smask;
-                        const unsigned cpi = cur & 0x7FFFu;
-                        const unsigned span = cpi - cpj;
-                        const unsigned gj = st & 0x7FFFu;
-                        const unsigned kv = (st | 0x7FFFu) - (gj > span ? gj : span);
-                        const unsigned bit = (d < 32 ? (mlo >> d) : (mhi >> (d - 32))) & 1u;
-                        const unsigned key = bit ? kv : 0xFFFFFFFFu;
-                        unsigned r = wave_min_u32(key);
-                        if constexpr (capm == 0) {
-                            const unsigned capkey = ((i - ws) << 16) | 0xFFFFu;
-                            r = r < capkey ? r : capkey;
-                        }
-                        const uint64_t gmb = ballot(key == r);
-                        const uint64_t emb = ballot((key ^ r) < 0x8000u);
-                        if (lane == 0) {
-                            const unsigned dg = gmb ? (unsigned)__builtin_ctzll(gmb) : 64u;
-                            const unsigned de = emb ? (unsigned)__builtin_ctzll(emb) : 64u;
-                            L.fin[i].d = dg | (de << 8);
-                            L.fin[i].w = Wfin<G>::pack(r);
-                            if constexpr (edges)
-                                if (i <= na) a.edges[SSr(0).sb + SSr(0).abase + i - 1] = emb;
-                        }
-                        const bool wend = (cur & CP_WS) != 0;
-                        ws = wend ? i : ws;
-                        unsigned nxt = (r ^ 0x7FFFu) + 0x10000u;
-                        if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;
-                        const unsigned sin = wend ? ST0 : nxt;
-                        st = wave_shift_in(st, sin);
-                        cpj = wave_shift_in(cpj, cpi);
-                        mlo = wave_shift_in(mlo, (unsigned)mi);
-                        mhi = wave_shift_in(mhi, (unsigned)(mi >> 32));
-                    }
-                }
-            };
-            // Capless windows without edge recording (the common case, G = 16): lanes take
-            // chunks of end positions cut at "cut points" -- boundaries no token span crosses,
-            // through which every tokenization of the word passes -- and run the recurrence
-            // sequentially over their own chunk, one position per iteration for 64 lanes.
-            // A chunk that starts inside a word starts from a local state (cost 0, G 0); a row
-            // scan of the chunks' transfers gives each chunk its incoming state, and a fix-up
-            // corrects the two things that depend on it: the final key of the word that ends
-            // first in the chunk (cost offset, max with the incoming G) and dg at the positions
-            // before that word end (dg = de wherever the incoming G already attains G[i]:
-            // every j in E(i) then ties on max(G[j], cp(span))).  de and E(i) are local.  The first
-            // is one store; the second is a test in the C1 walk, at the ends it visits.
-            auto forward_lanes = [&]() {
-              if constexpr (G == 16) {
-                // LW lanes share a window: a 16-lane row per slot, or (the one-string kernel, SOLO) the whole
-                // wave on slot 0 -- chunks of <= 5 boundaries instead of 17, so the dependent LDS steps of the
-                // recurrence and of the C1 walks are a quarter as many (the per-call floor)
-                constexpr int LW = SOLO ? 64 : 16;
-                constexpr unsigned CMAX = ((unsigned)(CH + LW - 1) / (unsigned)LW) | 1u;   // boundaries per lane, at most
-                const unsigned mg = SOLO ? 0u : lane / 16u;
-                const unsigned d = SOLO ? lane : lane % 16u;
-                GL &L = grp(mg);
-                const unsigned na = SSr(mg).n_atoms;
-                uint32_t *rec32 = reinterpret_cast<uint32_t *>(L.rec);
-                constexpr unsigned FRESH = 31u;   // key16 of a fresh start: cost 0, reachable, G 0
-                // key16 = cost << 6 | invalid << 5 | 31 - G (the Wfin<16> form)
-                auto relax = [](unsigned sj, unsigned span) {   // cost + 1, G = max(G, cp(span)); span <= 16
-                    const unsigned a1 = sj + 64u;
-                    const unsigned a2 = (a1 | 31u) - span;
-                    return a1 < a2 ? a1 : a2;
-                };
-                // ---- cut points: boundary p is one iff min_{i > p} lo_i >= p, lo_i = the first atom
-                //      of the longest token ending at i (i-1 - highest bit of its end mask)
-                // boundaries per lane (na <= 256), odd: lanes stepping through their chunks together
-                // then hit distinct LDS banks (ds_read_b32: 32 banks per 32-lane group; a stride of
-                // 16 dwords put 8 lanes on a bank)
-                const unsigned C = ((na + (unsigned)LW - 1u) / (unsigned)LW) | 1u;   // <= CMAX
-                const unsigned c0 = min(d * C, na), c1 = min(c0 + C, na);
-                // one backward pass over the chunk's ends (c0, c1]: the local suffix min of lo
-                // decides the cuts as far as this chunk's ends go; the later chunks' ends (min S)
-                // then only cap them: p is a cut iff both mins are >= p, i.e. p <= S
-                // (the 512-byte pass's chunks have up to 33 boundaries: a 64-bit cut mask there)
-                using CutM = std::conditional_t<(CMAX > 32u), uint64_t, uint32_t>;
-                unsigned mloc = 0xFFFFu;
-                CutM lcut = 0;
-#pragma unroll 4
-                for (int k = (int)CMAX - 1; k >= 0; k--) {
-                    const unsigned i = c0 + 1u + (unsigned)k;
-                    if (i <= c1) {
-                        const unsigned hb = 31u - (unsigned)__builtin_clz((~rec32[i] >> 16) | 1u);   // bit 0 is set in a capless window
-                        mloc = min(mloc, i - 1u - hb);
-                        if (mloc >= i - 1u) lcut |= (CutM)1 << k;   // boundary p = i-1 = c0+k < c1
-                    }
-                }
-                // min lo over the later lanes of the group (shift left: lane l reads lane l+k)
-                unsigned sm = mloc;
-                sm = min(sm, gshl<LW, 1>(sm, 0xFFFFu));
-                sm = min(sm, gshl<LW, 2>(sm, 0xFFFFu));
-                sm = min(sm, gshl<LW, 4>(sm, 0xFFFFu));
-                sm = min(sm, gshl<LW, 8>(sm, 0xFFFFu));
-                if constexpr (LW == 64) {
-                    sm = min(sm, gshl<LW, 16>(sm, 0xFFFFu));
-                    sm = min(sm, gshl<LW, 32>(sm, 0xFFFFu));
-                }
-                const unsigned S = gshl<LW, 1>(sm, 0xFFFFu);
-                // boundaries c0 + k <= S
-                const CutM cut = S < c0 ? (CutM)0 : (S - c0 >= CMAX - 1u ? lcut : lcut & (((CutM)2 << (S - c0)) - 1u));
-                // rs = the first cut at or after c0 (in this lane's chunk or a later one; na is a cut)
-                unsigned rs = na;
-                if constexpr (CMAX > 32u) rs = cut ? c0 + (unsigned)__builtin_ctzll(cut) : na;
-                else rs = cut ? c0 + ffbl(cut) : na;
-                rs = min(rs, gshl<LW, 1>(rs, na));
-                rs = min(rs, gshl<LW, 2>(rs, na));
-                rs = min(rs, gshl<LW, 4>(rs, na));
-                rs = min(rs, gshl<LW, 8>(rs, na));
-                if constexpr (LW == 64) {
-                    rs = min(rs, gshl<LW, 16>(rs, na));
-                    rs = min(rs, gshl<LW, 32>(rs, na));
-                }
-                if constexpr (NEAR_CUT) {
-                    // the NEAREST cut to c0 instead of the first one after it: snapping up made the longest
-                    // chunk of a wave ~2x the mean on cfg4's long words (a 256-atom window: 36.7 ends
-                    // against C = 17), and the wave steps as long as its longest chunk; nearest-cut
-                    // rounding is monotone in c0, so the chunks still tile (0, na]
-                    unsigned lastc = 0;   // (0 is a cut)
-                    if constexpr (CMAX > 32u) lastc = cut ? c0 + (63u - (unsigned)__builtin_clzll(cut)) : 0u;
-                    else lastc = cut ? c0 + (31u - (unsigned)__builtin_clz((unsigned)cut)) : 0u;
-                    unsigned pm = lastc;   // max over the lanes <= d of the group, then shifted: lanes < d
-                    pm = max(pm, gshr<LW, 1>(pm, 0u));
-                    pm = max(pm, gshr<LW, 2>(pm, 0u));
-                    pm = max(pm, gshr<LW, 4>(pm, 0u));
-                    pm = max(pm, gshr<LW, 8>(pm, 0u));
-                    if constexpr (LW == 64) {
-                        pm = max(pm, gshr<LW, 16>(pm, 0u));
-                        pm = max(pm, gshr<LW, 32>(pm, 0u));
-                    }
-                    const unsigned prevc = gshr<LW, 1>(pm, 0u);
-                    rs = (c0 - prevc < rs - c0) ? prevc : rs;
-                }
-                const unsigned re = gshl<LW, 1>(rs, na);
-                if (DPT_STOP == 25) return;   // diagnostic: cut points only
-
-                // ---- the recurrence over ends (rs, re], one position per iteration
-                unsigned i = rs, ws = rs, sprev = FRESH, pe = 0;
-                unsigned cprev = rec32[rs] & 0x7FFu;
-                unsigned nxt = rec32[rs + 1u];   // rs + 1 <= na + 1 < NA
-                unsigned T = 0;                  // tokens of the chunk: the pieces' costs
-                // (reading the next position's first candidates a step ahead, or two candidates per inner
-                // iteration, measured slower: r03y, r03)
-                while (ballot(i < re)) {
-                    if (i < re) {
-                        i++;
-                        const unsigned r = nxt;
-                        nxt = rec32[i + 1u];
-                        const unsigned cpi = r & 0x7FFu;             // bits 11..14: see below
-                        unsigned best = relax(sprev, cpi - cprev);   // j = i-1: the single atom
-                        unsigned dg = 0, de = 0;
-                        unsigned m = (~r >> 17) & 0x7FFFu;          // longer tokens ending at i: bit d-1
-                        while (m) {
-                            const unsigned dd = ffbl(m) + 1u;
-                            m &= m - 1u;
-                            const unsigned j = i - 1u - dd;          // j >= ws: spans cross no cut
-                            const unsigned rj = rec32[j];
-                            const unsigned sj = j == ws ? FRESH : (rj >> 16);
-                            const unsigned kk = relax(sj, cpi - (rj & 0x7FFu));
-                            // ascending d = descending j: the first strict improvement is the largest j
-                            if ((kk >> 5) < (best >> 5)) de = dd;
-                            if (kk < best) dg = dd;
-                            best = kk < best ? kk : best;
-                        }
-                        // One dword: the key in the mask half (this end's mask was read above), and the
-                        // local G(i) - 1 (G is 1..16 past rs in a capless window) in bits 11..14 of the
-                        // cpos half (code-point prefixes are < 2048 in a window; every reader of a cpos
-                        // in lane mode masks them off).  C1 finds it there -- the mask halves take the
-                        // walks' tokens: at a word end it is the word's L* - 1 (the longest token to
-                        // select), elsewhere what the walk's dg/de rule compares the incoming G with.
-                        rec32[i] = (best << 16) | (r & 0x87FFu) | ((30u - (best & 31u)) << 11);
-                        L.fin[i].v = (uint8_t)(dg | (de << 4));
-                        const bool wend = (r & CP_WS) != 0;
-                        if (wend) {
-                            T += best >> 6;
-                            if (!pe) pe = i;
-                        }
-                        ws = wend ? i : ws;
-                        sprev = wend ? FRESH : best;
-                        cprev = cpi;
-                    }
-                }
-                if (DPT_STOP == 26) return;   // diagnostic: + the recurrence
-                // P1 = the piece walked first in C1 (the one ending at re); p1in: no word start in
-                // (rs, re), so P1 is the chunk's first piece too and starts from the incoming state
-                const bool re_ws = i > rs && sprev == FRESH;   // re is a word start (its word ended)
-                const bool p1in = pe == 0 || pe == re;
-                if (!re_ws) T += sprev >> 6;
-                unsigned gl1 = 31u - ((re_ws ? L.rec[re].smask : sprev) & 31u);   // local G of P1 at re
-                // ---- row scan of the chunk transfers: (reset, value) -- a chunk with a word start
-                //      ignores its input; otherwise out = in (+) local, (+) = costs add, G max
-                unsigned x = (pe ? 0x10000u : 0u) | sprev;
-                auto compose = [&](unsigned y) {   // y (the earlier lanes) then x
-                    const unsigned comb = (y & 0xFFC0u) + (x & 0xFFC0u) + min(y & 31u, x & 31u);
-                    x = (x >> 16) ? x : ((y & 0x10000u) | comb);
-                };
-                compose(gshr<LW, 1>(x, FRESH));
-                compose(gshr<LW, 2>(x, FRESH));
-                compose(gshr<LW, 4>(x, FRESH));
-                compose(gshr<LW, 8>(x, FRESH));
-                if constexpr (LW == 64) {
-                    compose(gshr<LW, 16>(x, FRESH));
-                    compose(gshr<LW, 32>(x, FRESH));
-                }
-                const unsigned in = gshr<LW, 1>(x, FRESH) & 0xFFFFu;
-                const unsigned gin = 31u - (in & 31u);   // G at rs
-                // The incoming state changes two things.  The final key of the word that ends first in
-                // the chunk: composed here, and its L* := gin where gin > G(pe).  And dg at the ends q in
-                // (rs, lim], lim = that word end (re without one): dg = de where gin >= the local G(q).
-                // Only the ends the C1 walk visits need that, so the walk applies it (fgm below) from the
-                // G(q) - 1 the recurrence left in rec[q]; at pe the bits then hold max(gin, G(pe)) - 1,
-                // which gin - 1 reaches exactly when gin >= the local G(pe).
-                if (gin && pe) {
-                    const unsigned kl = L.rec[pe].smask;
-                    L.rec[pe].smask = (uint16_t)((in & 0xFFC0u) + (kl & 0xFFC0u) + min(in & 31u, kl & 31u));
-                    if (gin > 31u - (kl & 31u)) L.rec[pe].cpos = (uint16_t)((L.rec[pe].cpos & 0x87FFu) | ((gin - 1u) << 11));
-                }
-                const unsigned flim = gin ? (pe ? pe : re) : 0u;   // no incoming G: no end is <= 0
-                const unsigned fgm = gin - 1u;                      // (read only where flim != 0)
-                const unsigned gre = p1in ? max(gin, gl1) : gl1;   // G at re of P1's word (its L* if re_ws)
-                if (DPT_STOP == 27) return;   // diagnostic: + the transfer scan and fix-up
-
-                // ---- C1 (replaces C0 + C1 for the wave): the selection walks, one chunk per lane.
-                // Every tokenization passes through the cuts, so a chunk's tokens are the ones its
-                // own walk from re down to rs emits; their count T is fixed (the pieces' costs).
-                // The walk rule is C1's (dg while the longest token so far A is below the word's
-                // L*, de after).  What a chunk needs from the right: P1's L* (a copy scan from
-                // the chunk holding its word end) and whether A has reached L* on entry.  Left of
-                // q (the first cut where G reaches L*: gre < L*) it has -- the L* token lies in the
-                // segment ending at q; right of q, dg == de everywhere (every j in E(i) is at or
-                // after q, so G[j] == L*), so it does not matter; in q's chunk it has iff a chunk
-                // to the right selected an L* token by chance -- the flag scan after the walks,
-                // and that chunk re-walks P1 in de mode.
-                // token base: exclusive prefix sum of T over the row; the window's count to wtok
-                unsigned tb = T;
-                tb += gshr<LW, 1>(tb, 0u);
-                tb += gshr<LW, 2>(tb, 0u);
-                tb += gshr<LW, 4>(tb, 0u);
-                tb += gshr<LW, 8>(tb, 0u);
-                if constexpr (LW == 64) {
-                    tb += gshr<LW, 16>(tb, 0u);
-                    tb += gshr<LW, 32>(tb, 0u);
-                }
-                if (d == (unsigned)LW - 1u) SSr(mg).wtok = tb;
-                tb -= T;
-                // P1's L*: from rec[re] when its word ends at re, else from the right (the first
-                // word end of the next chunk that has one)
-                unsigned lsr = pe ? (0x10000u | (((unsigned)L.rec[pe].cpos >> 11) & 15u)) : 0u;
-                auto copy_r = [&](unsigned y) { lsr = (lsr >> 16) ? lsr : y; };
-                copy_r(gshl<LW, 1>(lsr, 0u));
-                copy_r(gshl<LW, 2>(lsr, 0u));
-                copy_r(gshl<LW, 4>(lsr, 0u));
-                copy_r(gshl<LW, 8>(lsr, 0u));
-                if constexpr (LW == 64) {
-                    copy_r(gshl<LW, 16>(lsr, 0u));
-                    copy_r(gshl<LW, 32>(lsr, 0u));
-                }
-                // (DPP reads outside any branch: a lane masked off in EXEC reads as 0)
-                const unsigned lsn = gshl<LW, 1>(lsr, 0u);
-                const unsigned ls1 = re_ws ? gre : (lsn & 15u) + 1u;
-                const bool walk = !len_only && SSr(mg).status == 0;   // per row (not uniform)
-                const bool left_of_q = gre < ls1;
-                unsigned n1 = 0;   // tokens of P1
-                unsigned afin = 0, lsm = ls1;   // after the walk: A and L* of the last piece
-                {
-                    unsigned ii = re, k = walk ? tb + T : tb, A = left_of_q ? ls1 : 0u, Ls = ls1;
-                    unsigned pend = rec32[re] & 0x7FFu;
-                    bool inp1 = true;
-                    while (ballot(k > tb)) {
-                        if (k > tb) {
-                            const unsigned rr = rec32[ii];
-                            const unsigned cpi = rr & 0x7FFu;
-                            if (ii < re && (rr & CP_WS)) {   // into the word ending at ii
-                                Ls = ((rr >> 11) & 15u) + 1u;
-                                A = 0;
-                                pend = cpi;
-                                inp1 = false;
-                            }
-                            n1 += inp1 ? 1u : 0u;
-                            const unsigned f = L.fin[ii].v;
-                            const unsigned sp = pend - cpi;
-                            A = A > sp ? A : sp;
-                            // de once A has reached L*, and where the incoming G attains the local G(ii)
-                            // (every j in E(ii) then ties on G: the chunk-start rule, see flim)
-                            const bool tie = (ii <= flim) & (((rr >> 11) & 15u) <= fgm);
-                            const unsigned dd = ((A >= Ls) | tie) ? (f >> 4) : (f & 15u);
-                            const unsigned j = ii - 1u - dd;
-                            k--;
-                            L.rec[k].smask = (uint16_t)j;   // k < rs or a position this walk has left
-                            pend = cpi;
-                            ii = j;
-                        }
-                    }
-                    const unsigned sp = pend - (rec32[rs] & 0x7FFu);
-                    afin = A > sp ? A : sp;
-                    lsm = Ls;
-                }
-                // flag scan, right to left: the chunk's last piece reached its L* (sel); a chunk
-                // whose last piece is P1 also passes on what came in; none crosses a word start
-                unsigned fl = ((T > 0 && afin >= lsm) ? 1u : 0u) | ((!p1in || re_ws) ? 2u : 0u);
-                auto flag_r = [&](unsigned y) { fl = (fl & 2u) ? fl : (fl | (y & 3u)); };
-                flag_r(gshl<LW, 1>(fl, 0u));
-                flag_r(gshl<LW, 2>(fl, 0u));
-                flag_r(gshl<LW, 4>(fl, 0u));
-                flag_r(gshl<LW, 8>(fl, 0u));
-                if constexpr (LW == 64) {
-                    flag_r(gshl<LW, 16>(fl, 0u));
-                    flag_r(gshl<LW, 32>(fl, 0u));
-                }
-                const unsigned fln = gshl<LW, 1>(fl, 0u);
-                const bool fin_in = !re_ws && (fln & 1u) != 0;
-                // q's chunk with a chance L* token to the right: P1 again in de mode (A = L*);
-                // P1 starts below L* only from rs with gin < L* or from a word start inside
-                if (walk && fin_in && !left_of_q && (!p1in || gin < ls1)) {
-                    unsigned ii = re, k = tb + T;
-                    for (unsigned c = 0; c < n1; c++) {
-                        const unsigned j = ii - 1u - (unsigned)(L.fin[ii].v >> 4);
-                        k--;
-                        L.rec[k].smask = (uint16_t)j;
-                        ii = j;
-                    }
-                }
-              }
-            };
-            // Capless windows of the 256-byte 64-lane kernel without edge recording (one string per
-            // wave: BLOOM-scale byte-level vocabularies).  The row recurrence is one wave-min per atom,
-            // a dependent chain over the whole window (55 % of that kernel, profiles/r03_phase_diag.txt).
-            // Here each lane takes a chunk of end positions cut at cut points, as forward_lanes does,
-            // and relaxes forward ("push") from every start j of its chunk over j's span mask (phase
-            // A's start masks, rec[j].smask): the token j..i updates i's entry {dg | de << 8 | cp(i)
-            // << 16, key} in fin[].  Starts are taken in ascending order, so "<=" keeps the largest j
-            // of a tie -- the row recurrence's lowest lane (dp_tokenize.py:40-46).  A wave scan of the
-            // chunk transfers and the chunk-start fix-up follow (here a loop over fin[]; forward_lanes
-            // applies it in its own walk); C0/C1 then run as in row mode (they read fin[] only).
-            auto forward_lanes64 = [&]() {
-              if constexpr (G == 64 && !BIG) {
-                if (na == 0) return;
-                constexpr unsigned FRESH = 0x7FFFu;       // key of a fresh start: cost 0, reachable, G 0
-                constexpr unsigned RESET = 0x80000000u;   // transfer flag: a word ends in the chunk
-                uint2 *fin2 = reinterpret_cast<uint2 *>(L.fin);
-                // ---- cut points (bit p of cm[p / 64]): p is one iff max_{j < p} (j + 1 + hb(smask_j))
-                //      <= p -- no token crosses it; 0 and na always are
-                uint64_t cm[(CH + 64) / 64];
-                unsigned carry = 0;
-#pragma unroll
-                for (int r = 0; r < (CH + 64) / 64; r++) {
-                    const unsigned p = 64u * (unsigned)r + lane;
-                    // the end of the longest token from p: p + 1 + (63 - clz)
-                    const unsigned v = p < na ? p + 64u - (unsigned)__builtin_clzll(L.rec[p].smask | 1ull) : 0u;
-                    const unsigned inc = wave_incl_scan_max(v);
-                    const unsigned ex = max(carry, wave_shift_in(inc, 0u));
-                    carry = max(carry, __builtin_amdgcn_readlane(inc, 63));
-                    cm[r] = ballot(p <= na && ex <= p);
-                }
-                // the first cut at or after c (<= na)
-                auto nextcut = [&](unsigned c) -> unsigned {
-                    unsigned res = na;
-#pragma unroll
-                    for (int r = (CH + 64) / 64 - 1; r >= 0; r--) {
-                        const unsigned lo = 64u * (unsigned)r;
-                        const uint64_t keep = c <= lo ? ~0ull : (c >= lo + 64u ? 0ull : (~0ull << (c - lo)));
-                        const uint64_t m = cm[r] & keep;
-                        res = m ? lo + (unsigned)__builtin_ctzll(m) : res;
-                    }
-                    return res;
-                };
-                // the last cut at or before c (0 is a cut)
-                auto prevcut = [&](unsigned c) -> unsigned {
-                    unsigned res = 0;
-#pragma unroll
-                    for (int r = 0; r < (CH + 64) / 64; r++) {
-                        const unsigned lo = 64u * (unsigned)r;
-                        const uint64_t keep = c < lo ? 0ull : (c >= lo + 63u ? ~0ull : (~0ull >> (63u - (c - lo))));
-                        const uint64_t m = cm[r] & keep;
-                        res = m ? lo + 63u - (unsigned)__builtin_clzll(m) : res;
-                    }
-                    return res;
-                };
-                // chunk bounds snapped to the NEAREST cut (as forward_lanes, DPT_NEAR_CUT): monotone in c, so
-                // lane l's end is lane l+1's start
-                auto snap = [&](unsigned c) -> unsigned {
-                    const unsigned nx = nextcut(c);
-                    if constexpr (!NEAR_CUT64) return nx;
-                    const unsigned pv = prevcut(c);
-                    return (c - pv < nx - c) ? pv : nx;
-                };
-                const unsigned C = (na + 63u) >> 6;   // (odd chunk lengths: -0.5 %, r03ad)
-                const unsigned c0 = min(lane * C, na), c1 = min(c0 + C, na);
-                const unsigned rs = snap(c0);
-                // (c1 = the next lane's c0: its start, by wave_shl:1; lane 63 ends at na)
-                const unsigned re = (unsigned)__builtin_amdgcn_update_dpp((int)na, (int)rs, 0x130, 0xF, 0xF, false);
-                (void)c1;
-                if (DPT_STOP == 25) return;   // diagnostic: cut points only
-                // ---- the chunk's entries: no candidate yet, cp(i) in the high half; pe = its first word end
-                unsigned pe = 0;
-                for (unsigned i = rs + 1u; i <= re; i++) {
-                    const unsigned cp = L.rec[i].cpos;
-                    fin2[i] = make_uint2((cp & 0x7FFFu) << 16, 0xFFFFFFFFu);
-                    pe = (!pe && (cp & CP_WS)) ? i : pe;
-                }
-                // ---- push: j ascending; j's key is final once every earlier start of the chunk ran --
-                //      it is the j-1 -> j edge's result (bit 0: capless windows have it at every start),
-                //      carried in a register.  One edge at a time: batches of 2 / 4 edges with their reads
-                //      in flight (r03x) and giving long chunks to the whole wave as a row recurrence (r03ae)
-                //      measured slower -- the push is throughput-bound across the resident waves.
-                unsigned kcarry = FRESH;
-                for (unsigned j = rs; j < re; j++) {
-                    const uint64_t sm = L.rec[j].smask;
-                    const unsigned cj = L.rec[j].cpos;
-                    const unsigned kj = (j == rs || (cj & CP_WS)) ? FRESH : kcarry;
-                    const unsigned a1 = kj + 0x10000u;             // cost + 1
-                    const unsigned a1g = (a1 | 0x7FFFu) + (cj & 0x7FFFu);
-                    auto upd = [&](uint2 &f, unsigned dd) {
-                        const unsigned a2 = a1g - (f.x >> 16);       // G = max(G[j], cp(j..i))
-                        const unsigned kk = a1 < a2 ? a1 : a2;
-                        f.x = ((kk >> 15) <= (f.y >> 15)) ? ((f.x & ~0x7F00u) | (dd << 8)) : f.x;   // de
-                        f.x = (kk <= f.y) ? ((f.x & ~0x7Fu) | dd) : f.x;                            // dg
-                        f.y = kk < f.y ? kk : f.y;
-                    };
-                    if (!raw && L.scf[j]) {
-                        // a word that is one token (phase A's whole-word shortcut): only that edge, whose key
-                        // (cost 1) is final at the word end; its inner positions are never read (C0/C1 read
-                        // word ends, C1 walks from them; no cut lies inside the word).  Sound only because
-                        // (1) every window ends at a word start or the string's end (window_bounds), so the
-                        // BF_STOP the byte-stream walker stopped on is the word's real end, not a window cut
-                        // through it, and (2) that walker never steps past a BF_STOP; a change to either
-                        // must revisit this (tests/test_gpu_parity.py::test_bloom_words_across_windows)
-                        const unsigned dd = 63u - (unsigned)__builtin_clzll(sm);   // the longest token from j
-                        uint2 f = fin2[j + 1u + dd];
-                        upd(f, dd);
-                        fin2[j + 1u + dd] = f;
-                        kcarry = f.y;
-                        j += dd;
-                        continue;
-                    }
-                    {   // the j -> j+1 edge (bit 0): j+1's final key
-                        uint2 f = fin2[j + 1u];
-                        upd(f, 0u);
-                        fin2[j + 1u] = f;
-                        kcarry = f.y;
-                    }
-                    // the span mask as two 32-bit halves: one v_ffbl and 32-bit arithmetic per edge
-                    // (BLOOM 21.5 -> 22.1 GB/s against the 64-bit walk, r04l)
-#pragma unroll
-                    for (int hh = 0; hh < 2; hh++) {
-                        uint32_t m32 = hh == 0 ? ((uint32_t)sm & ~1u) : (uint32_t)(sm >> 32);
-                        while (m32) {
-                            const unsigned dd = ffbl(m32) + 32u * (unsigned)hh;
-                            m32 &= m32 - 1u;
-                            uint2 f = fin2[j + 1u + dd];   // <= re: no token crosses a cut
-                            upd(f, dd);
-                            fin2[j + 1u + dd] = f;
-                        }
-                    }
-                }
-                if (DPT_STOP == 26) return;   // diagnostic: + the recurrence
-                // ---- wave scan of the chunk transfers (forward_lanes' compose, 64 lanes, keys)
-                const bool re_wb = (L.rec[re].cpos & CP_WS) != 0;
-                unsigned x = rs == re ? FRESH : ((pe ? RESET : 0u) | (re_wb ? FRESH : fin2[re].y));
-                auto compose = [&](unsigned y) {   // y (the earlier lanes) then x
-                    const unsigned comb = ((y & 0x7FFF0000u) + (x & 0x7FFF0000u)) | min(y & 0x7FFFu, x & 0x7FFFu);
-                    x = (x & RESET) ? x : ((y & RESET) | comb);
-                };
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x111, 0xF, 0xF, false));   // row_shr:1
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x112, 0xF, 0xF, false));   // row_shr:2
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x114, 0xF, 0xF, false));   // row_shr:4
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x118, 0xF, 0xF, false));   // row_shr:8
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x142, 0xA, 0xF, false));   // row_bcast:15
-                compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x143, 0xC, 0xF, false));   // row_bcast:31
-                const unsigned in = (unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x138, 0xF, 0xF, false) & ~RESET;   // wave_shr:1
-                const unsigned gin = 0x7FFFu - (in & 0x7FFFu);   // G at rs (0: a word starts there, cost 0)
-                if (gin) {
-                    // before the first word end: dg = de wherever the incoming G attains G[q];
-                    // the first word end's key = in (+) local
-                    const unsigned lim = pe ? pe : re;
-                    for (unsigned q = rs + 1u; q <= lim; q++) {
-                        const uint2 f = fin2[q];
-                        if (gin >= 0x7FFFu - (f.y & 0x7FFFu)) fin2[q].x = (f.x & ~0x7Fu) | ((f.x >> 8) & 0x7Fu);
-                    }
-                    if (pe) {
-                        const unsigned kl = fin2[pe].y;
-                        fin2[pe].y = ((in & 0x7FFF0000u) + (kl & 0x7FFF0000u)) | min(in & 0x7FFFu, kl & 0x7FFFu);
-                    }
-                }
-              }
-            };
-            using T_ = std::true_type;
-            using F_ = std::false_type;
-            using C0_ = std::integral_constant<int, 0>;
-            using C1_ = std::integral_constant<int, 1>;
-            using C2_ = std::integral_constant<int, 2>;
-            unsigned capb = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) capb |= uni(SSr(g).capb);
-            if (!PLAIN && a.edges) {
-                if (!capb) forward(T_{}, C2_{}); else if (uncapped) forward(T_{}, C1_{}); else forward(T_{}, C0_{});
-            } else {
-                if (!capb) {
-                    if constexpr (G == 16) {
-                        forward_lanes();
-                        lane_mode = true;
-                    } else if constexpr (!BIG) {
-                        forward_lanes64();
-                        lane_mode = DPT_STOP >= 25 && DPT_STOP <= 27;   // stop builds: no C0/C1 over unfinished fin[]
-                    } else {
-                        forward(F_{}, C2_{});
-                    }
-                } else if (uncapped) forward(F_{}, C1_{}); else forward(F_{}, C0_{});
-            }
-        }
-        wave_sync();
-        STAMP(2);
-
-        // ---------------------------------------------------------- C0: per-window token counts and validity
-        KREFRESH();
-        // (word w ends at atom word_end(w); its final state is in fin[word_end(w)])
-        if (DPT_RUN_B && !lane_mode) {
-            if constexpr (GL::WSLG) {
-                // the word list (word -> first atom, then the window end) from the word-start bits
-#pragma unroll
-                for (int g = 0; g < NG; g++) {
-                    const unsigned na = uni(SSr(g).n_atoms);
-                    if (na == 0) continue;
-                    const GL &L = grp(g);
-                    uint8_t *gw = wsl_of(g);
-                    unsigned wi = 0;
-                    for (unsigned j0 = 0; j0 <= na; j0 += 64u) {
-                        const unsigned j = j0 + lane;
-                        const bool ws = j <= na && (L.rec[j].cpos & CP_WS) != 0;   // atom na: the window end
-                        const uint64_t m = ballot(ws);
-                        if (ws) gw[wi + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (uint8_t)j;
-                        wi += (unsigned)__builtin_popcountll(m);
-                    }
-                }
-            }
-            unsigned pre[NG + 1];
-            pre[0] = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) pre[g + 1] = pre[g] + (uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).n_words) : 0u);
-            const unsigned total = pre[NG];
-            for (unsigned u0 = 0; u0 < total; u0 += 64) {
-                const unsigned u = u0 + lane;
-                unsigned g = 0;
-#pragma unroll
-                for (int k = 1; k < NG; k++) g += u >= pre[k] ? 1u : 0u;
-                unsigned wbase = 0;
-#pragma unroll
-                for (int k = 0; k < NG; k++) wbase = g == (unsigned)k ? pre[k] : wbase;
-                unsigned cost = 0, inv = 0, lng = 0;
-                if (u < total) {
-                    const GL &L = grp(g);
-                    const unsigned we = L.word_end(wsl_of(g), u - wbase);
-                    const typename Wfin<G>::T F = L.wkey(we);
-                    cost = Wfin<G>::cost(F);
-                    inv = Wfin<G>::invalid(F) ? 1u : 0u;
-                    // a vocabulary token longer than G code points could span more than G atoms,
-                    // beyond the walks: such a word is outside the engine's limits (status 3)
-                    if (a.long_span) lng = we - L.word_start(wsl_of(g), u - wbase) > (unsigned)G ? 1u : 0u;
-                }
-                // per-group sums over this chunk: groups own contiguous lane ranges
-#pragma unroll
-                for (int k = 0; k < NG; k++) {
-                    const unsigned lo = pre[k] > u0 ? pre[k] - u0 : 0u, hi = pre[k + 1] > u0 ? pre[k + 1] - u0 : 0u;
-                    if (hi <= lo) continue;
-                    const bool mine = lane >= lo && lane < (hi < 64u ? hi : 64u);
-                    const unsigned cs = wave_incl_scan_add(mine ? cost : 0u);
-                    const unsigned csum = __builtin_amdgcn_readlane(cs, 63);
-                    const unsigned anyinv = (ballot(mine && inv) != 0 ? 1u : 0u) | (ballot(mine && lng) != 0 ? 2u : 0u);
-                    if (lane == 0) { SSr(k).wtok += csum; SSr(k).inval |= anyinv; }
-                }
-            }
-        }
-        wave_sync();
-
-        // ---------------------------------------------------------- C1: selection, one lane per word
-        KREFRESH();
-        if (DPT_RUN_B && !lane_mode) {
-            unsigned pre[NG + 1], tokpre[NG + 1], inv_g[NG];
-            pre[0] = 0; tokpre[0] = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                const unsigned nwg = uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).n_words) : 0u;
-                inv_g[g] = uni(SSr(g).inval) | (uni(SSr(g).status) != 0 ? 1u : 0u);
-                pre[g + 1] = pre[g] + nwg;
-                tokpre[g + 1] = tokpre[g] + (nwg ? uni(SSr(g).wtok) : 0u);
-            }
-            const unsigned total = pre[NG];
-            unsigned carry = 0;
-            for (unsigned u0 = 0; u0 < total; u0 += 64) {
-                const unsigned u = u0 + lane;
-                const bool in = u < total;
-                unsigned g = 0;
-#pragma unroll
-                for (int k = 1; k < NG; k++) g += u >= pre[k] ? 1u : 0u;
-                unsigned wbase = 0, tbase = 0, ginv = 0;
-#pragma unroll
-                for (int k = 0; k < NG; k++)
-                    if (g == (unsigned)k) { wbase = pre[k]; tbase = tokpre[k]; ginv = inv_g[k]; }
-                GL &L = grp(g);
-                const unsigned w = u - wbase;
-                const typename Wfin<G>::T F = in ? L.wkey(L.word_end(wsl_of(g), w)) : (typename Wfin<G>::T)0;
-                const unsigned cost = in ? Wfin<G>::cost(F) : 0u;
-                const unsigned incl = wave_incl_scan_add(cost);
-                const unsigned tok_base = carry + incl - cost - tbase;
-                carry += __builtin_amdgcn_readlane(incl, 63);
-                if (in && !ginv && !len_only) {
-                    // a valid word's walk emits exactly `cost` tokens and ends at its first atom
-                    // (Appendix A), so the token count bounds the loop
-                    unsigned i = L.word_end(wsl_of(g), w);
-                    const unsigned Ls = Wfin<G>::gmax(F);   // G of the word = the longest token to reach
-                    unsigned c = cost, A = 0;
-                    unsigned pend = L.rec[i].cpos & 0x7FFFu;
-                    while (c > 0) {
-                        const typename GR::Fin f = L.fin[i];
-                        const unsigned cpi = L.rec[i].cpos & 0x7FFFu;
-                        const unsigned sp = pend - cpi;
-                        A = A > sp ? A : sp;                 // the token emitted last step ended at pend
-                        const unsigned dd = A < Ls ? GR::dg(f) : GR::de(f);
-                        const unsigned j = i - 1 - dd;
-                        c--;
-                        L.rec[tok_base + c].smask = (M)j;   // span masks are dead after B
-                        pend = cpi;
-                        i = j;
-                    }
-                }
-            }
-        }
-        wave_sync();
-        STAMP(3);
-        // ---------------------------------------------------------- C2: ids (lanes over all slots' tokens)
-        KREFRESH();
-        if (DPT_RUN_C2) {
-            unsigned pre[NG + 1], na_g[NG];
-            uint64_t obase[NG];       // staging element of the window's first token, per slot
-            const bool n16 = SW == 1 || (SW == 0 && a.staging16 != nullptr);   // int16 staging (uniform)
-            // per slot, bit 0: the window starts the string (raw '▁' + first atom); bit 1: a '\u2581'-compressed
-            // PRESPLIT window (its ' ' bytes expand to '\u2581' as raw mode's do)
-            unsigned firstmask = 0;
-            pre[0] = 0;
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                const bool gv = !len_only && uni(SSr(g).inval) == 0 && uni(SSr(g).status) == 0 && uni(SSr(g).n_atoms) > 0;
-                pre[g + 1] = pre[g] + (gv ? uni(SSr(g).wtok) : 0u);
-                na_g[g] = uni(SSr(g).n_atoms);
-                firstmask |= ((raw && uni64(SSr(g).pos) == 0 ? 1u : 0u) | (uni(SSr(g).cpw) ? 2u : 0u)) << (2 * g);
-                const uint64_t e0 = uni64(SSr(g).sb) + uni(SSr(g).ntok);
-                obase[g] = e0;
-            }
-            const unsigned total = pre[NG];
-            // per-slot token range, atom count, first-window flag and staging row, in the slot's
-            // fin[] (dead after C1): a token start reads its slot's record with one LDS load
-            // instead of selecting among NG sets of registers
-            struct C2Slot {
-                uint32_t base, ntk, na, fw;
-                uint64_t ob;   // staging element (an offset, not a pointer: stores through a.staging* stay
-                               // global_store -- a pointer read back from LDS becomes a flat store, whose
-                               // lgkmcnt makes the next LDS wait on the store's completion)
-            };
-            static_assert(sizeof(typename GR::Fin) * GL::NA >= sizeof(C2Slot), "C2Slot fits fin[]");
-            if (lane == 0) {
-#pragma unroll
-                for (int g = 0; g < NG; g++) {
-                    C2Slot &q = *reinterpret_cast<C2Slot *>(&grp(g).fin[0]);
-                    q.base = pre[g]; q.ntk = pre[g + 1] - pre[g]; q.na = na_g[g]; q.fw = (firstmask >> (2 * g)) & 3u; q.ob = obase[g];
-                }
-            }
-            wave_sync();
-            // 16-lane first pass: a bulk pass resolves every token of one or two expanded bytes with
-            // ONE lookup (a one-byte token's root child, a two-byte token's root-table entry: .z = the
-            // id of the node reached) and lists the rest -- word starts ('\u2581'), newlines, tokens of
-            // three or more bytes -- by their token number in the rec[].cpos halves (dead in C2:
-            // entry i in group i / 256's rec[i % 256]).  A short list (< 64 tokens of <= 8 bytes: the
-            // walker would run with idle lanes) joins the wave's pending row, which is walked from
-            // the stored bytes once a round would overflow it (walk_pending); a longer one is walked
-            // below by the refill walker.
-            constexpr bool BULK = G == 16 && !BIG;
-            constexpr unsigned PEND_CAP = 64;   // residual tokens a wave's pending row holds (its scratch row)
-            unsigned wbeg = 0, wend = total;
-            // the list of tokens left for the walkers: in the rec[].cpos halves (dead in C2) -- G = 16:
-            // entry i in group i / 256's rec[i % 256]; G = 64 (one slot): rec[i]
-            auto list_ref = [&](unsigned i) -> uint16_t & {
-                if constexpr (G == 16)
-                    return *reinterpret_cast<uint16_t *>(smem + (i >> 8) * GSTR + (i & 255u) * 4u);
-                else
-                    return grp(0).rec[i].cpos;
-            };
-            // hash pass over n tokens (token number of entry i: src(i)): a token of at most
-            // TOKHASH_MAX_BYTES expanded bytes without a newline atom gets its id from ONE bucket load
-            // of the token hash table (dpt_internal.h); the others are listed, in order, at the front of
-            // the list for the walkers.  Returns their number (n without a table).
-            auto hash_pass = [&](unsigned n, auto src) -> unsigned {
-                const uint8_t *hbase = reinterpret_cast<const uint8_t *>(tv.pair16) + TOKHASH_OFFSET;
-                const TokHashHeader hh = *reinterpret_cast<const TokHashHeader *>(hbase);
-                if (!hh.max_probe) {
-                    for (unsigned i = lane; i < n; i += 64u) list_ref(i) = (uint16_t)src(i);
-                    return n;
-                }
-                const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(
-                    (void *)(hbase + sizeof(TokHashHeader)), (short)0, (int)((hh.mask + 1u) * 16u), 0x00020000);
-                // token rounds of 64 per iteration, their loads before any store (a load waits for every
-                // older store of the wave; 1 or 4 rounds measured slower, r03)
-                constexpr int HP_U = DPT_HP_U;
-                unsigned r2 = 0;
-                for (unsigned i0 = 0; i0 < n; i0 += 64u * HP_U) {
-                    unsigned tt[HP_U], hh2[HP_U], fpv[HP_U];
-                    uint64_t oqv[HP_U];
-                    bool hs[HP_U], inr[HP_U];
-#pragma unroll
-                    for (int u = 0; u < HP_U; u++) {
-                        const unsigned i = i0 + 64u * (unsigned)u + lane;
-                        const bool in = i < n;
-                        const unsigned t = in ? src(i) : 0u;
-                        unsigned g = 0;
-#pragma unroll
-                        for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
-                        const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
-                        const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
-                        const unsigned k = in ? t - q.base : 0u;
-                        const unsigned jj = (unsigned)L.rec[k].smask;
-                        const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
-                        const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                        const unsigned p0 = L.aoff[jj];
-                        const unsigned nbytes = (typename GL::Idx)(L.aoff[j1] - p0);
-                        const unsigned fa = q.fw & 1u & (unsigned)(jj == 0);   // (bit 0: raw mode only)
-                        uint32_t h = 0, fp = 0;
-                        bool hashed;
-                        if constexpr (G == 16) {
-                            uint32_t w[4];
-                            unsigned E = 0;
-                            hashed = in && token_key<CH>(L.bytes, p0, nbytes, raw || (q.fw >> 1) != 0u, fa, w, E);
-                            if (hashed) tokhash(w[0], w[1], w[2], w[3], E, hh.seed, h, fp);
-                        } else {   // 64-lane rows (BLOOM-scale vocabularies): keys of up to 64 bytes
-                            hashed = in && token_hash_long<CH>(L.bytes, p0, nbytes, raw, fa, hh.seed, h, fp);
-                        }
-                        tt[u] = t; hh2[u] = h & hh.mask; fpv[u] = fp; oqv[u] = q.ob + k; hs[u] = hashed; inr[u] = in;
-                    }
-                    int32_t idv[HP_U];
-                    if constexpr (HASH_BOTH) {
-                        // every round's two buckets (the key's two choices) at once, then the stores
-#pragma unroll
-                        for (int u = 0; u < HP_U; u++) {
-                            const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
-                            const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
-                            idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : e[2] == fpv[u] ? (int32_t)e[3] :
-                                     f[0] == fpv[u] ? (int32_t)f[1] : f[2] == fpv[u] ? (int32_t)f[3] : -1;
-                        }
-                    } else {
-                        // every round's home bucket, then the partner buckets of the keys not found there
-                        // (one more load round for the wave, never a chain), then the stores
-#pragma unroll
-                        for (int u = 0; u < HP_U; u++) {
-                            const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
-                            idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : (e[2] == fpv[u] ? (int32_t)e[3] : INT32_MIN);
-                        }
-                        bool miss = false;
-#pragma unroll
-                        for (int u = 0; u < HP_U; u++) miss |= hs[u] && idv[u] == INT32_MIN;
-                        if (ballot(miss)) {
-#pragma unroll
-                            for (int u = 0; u < HP_U; u++) {
-                                if (hs[u] && idv[u] == INT32_MIN) {
-                                    const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
-                                    idv[u] = f[0] == fpv[u] ? (int32_t)f[1] : (f[2] == fpv[u] ? (int32_t)f[3] : -1);
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < HP_U; u++) {
-                        if (hs[u]) {
-                            if (n16) a.staging16[oqv[u]] = (int16_t)idv[u];
-                            else a.staging[oqv[u]] = idv[u];
-                        }
-                    }
-                    // every lane read its entries above (list sources): the compacted rest lands below i0 + 64 * HP_U
-#pragma unroll
-                    for (int u = 0; u < HP_U; u++) {
-                        const bool rest = inr[u] && !hs[u];
-                        const uint64_t m = ballot(rest);
-                        if (rest) list_ref(r2 + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) = (uint16_t)tt[u];
-                        r2 += (unsigned)__builtin_popcountll(m);
-                    }
-                }
-                return r2;
-            };
-            if constexpr (BULK) {
-                const bool i16 = n16;
-                unsigned r = 0;
-                // The bulk pass over every selected token, 4 per lane per round of 256.  int16 ids from the
-                // pair table: all the window-set's lookups first, then all its stores -- a load waits for
-                // every OLDER vector-memory op of the wave, stores included (MI355X_MICROARCH.md: vmcnt
-                // counts loads and stores together, in issue order), so a store between two rounds of
-                // lookups put a store's full latency on every round.  (Every round's lookups before any
-                // store held the ids in registers and spilled: cfg2 -4.1 %, r03.)
-                constexpr int BU = DPT_BULK_U;   // tokens per lane per round
-                auto bulk_round = [&](unsigned t0, int32_t (&ix)[BU], unsigned (&kind)[BU], uint64_t (&oq)[BU]) {
-#pragma unroll
-                    for (int u = 0; u < BU; u++) {
-                        const unsigned t = t0 + 64u * (unsigned)u + lane;
-                        const bool in = t < total;
-                        unsigned g = 0;
-#pragma unroll
-                        for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
-                        const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
-                        const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
-                        const unsigned k = in ? t - q.base : 0u;
-                        const unsigned jj = (unsigned)L.rec[k].smask;
-                        const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
-                        const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                        const unsigned p0 = L.aoff[jj];
-                        const unsigned nbytes = (uint8_t)(L.aoff[j1] - p0);
-                        const uint32_t *w = reinterpret_cast<const uint32_t *>(L.bytes) + (p0 >> 2);
-                        const unsigned two = __builtin_amdgcn_alignbyte(w[1], w[0], p0 & 3u);
-                        const unsigned b0 = two & 0xFFu, b1 = (two >> 8) & 0xFFu;
-                        // raw mode (and '\u2581'-compressed PRESPLIT windows, q.fw bit 1) expands ' ' (a word start),
-                        // '\n' and the string's first atom
-                        const unsigned expd = ((raw ? 1u : 0u) | (q.fw >> 1)) &
-                                              ((unsigned)(b0 == ' ') | (unsigned)(b0 == '\n') | (q.fw & 1u & (unsigned)(jj == 0)) |
-                                               ((unsigned)(nbytes == 2u) & ((unsigned)(b1 == ' ') | (unsigned)(b1 == '\n'))));
-                        const unsigned bulk = (unsigned)in & (unsigned)(nbytes - 1u <= 1u) & (expd ^ 1u);
-                        if constexpr (SW == 1)   // int16 ids: the 128-KB pair table (L1-resident for ASCII)
-                            ix[u] = bulk ? (int32_t)(nbytes == 1u ? 65536u + b0 : (b0 << 8) + b1) : 0;
-                        else
-                            ix[u] = bulk ? (nbytes == 1u ? tv.root_base + (int32_t)b0 : (int32_t)(tv.n_slots + (b0 << 8) + b1)) : 0;
-                        kind[u] = bulk ? nbytes : 0u;
-                        oq[u] = q.ob + k;
-                        const bool res = in && !bulk;
-                        const uint64_t m = ballot(res);
-                        if (res) list_ref(r + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))) = (uint16_t)t;
-                        r += (unsigned)__builtin_popcountll(m);
-                    }
-                };
-                for (unsigned t0 = 0; t0 < total; t0 += 64u * (unsigned)BU) {
-                    int32_t ix[BU];
-                    unsigned kind[BU];   // 0: not here, 1 / 2: a token of that many bytes
-                    uint64_t oq[BU];
-                    bulk_round(t0, ix, kind, oq);
-                    if constexpr (SW == 1) {
-                        int16_t pv[BU];
-#pragma unroll
-                        for (int u = 0; u < BU; u++) pv[u] = tv.pair16[ix[u]];
-#pragma unroll
-                        for (int u = 0; u < BU; u++)
-                            if (kind[u]) a.staging16[oq[u]] = pv[u];
-                        continue;
-                    }
-                    int4 ent[BU];
-#pragma unroll
-                    for (int u = 0; u < BU; u++) ent[u] = trie_slotA(tv, ix[u]);
-#pragma unroll
-                    for (int u = 0; u < BU; u++) {
-                        if (kind[u]) {
-                            // the walker's rule: the id of the node reached when every step's check held
-                            const bool ok = kind[u] == 1u ? ent[u].y == 0 : (ent[u].y & 0x3FFFFFFF) != 0;
-                            const int32_t idv = ok ? ent[u].z : -1;
-                            if (i16) a.staging16[oq[u]] = (int16_t)idv;
-                            else a.staging[oq[u]] = idv;
-                        }
-                    }
-                }
-                wave_sync();
-                STAMP(5);
-                if (DPT_C2STOP == 1) r = 0;   // diagnostic: the bulk pass only
-                if (r > 0) {
-                    r = hash_pass(r, [&](unsigned i) -> unsigned { return list_ref(i); });
-                    wave_sync();
-                }
-                STAMP(6);
-                if (DPT_C2STOP == 2) r = 0;   // diagnostic: + the hash pass
-                wend = r;
-                if (r > 0 && r < (unsigned)PEND_CAP) {
-                    uint4 ent = make_uint4(0u, 0u, 0u, 0u);
-                    bool lng = false;
-                    if (lane < r) {
-                        const unsigned t = list_ref(lane);
-                        unsigned g = 0;
-#pragma unroll
-                        for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
-                        const GL &L = *reinterpret_cast<const GL *>(smem + g * GSTR);
-                        const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
-                        const unsigned k = t - q.base;
-                        const unsigned jj = (unsigned)L.rec[k].smask;
-                        const unsigned nx = (unsigned)L.rec[k + 1].smask;
-                        const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                        const unsigned p0 = L.aoff[jj];
-                        const unsigned len = (uint8_t)(L.aoff[j1] - p0);
-                        const unsigned fi = q.fw & 1u & (unsigned)(jj == 0);
-                        const unsigned rl = (raw ? 1u : 0u) | (q.fw >> 1);   // raw mode's expansions
-                        lng = len > 8u;
-                        const uint64_t by = load_bytes(L.bytes, p0, lng ? 8u : len);
-                        const uint64_t out = q.ob + k;
-                        ent = make_uint4((uint32_t)out, ((uint32_t)(out >> 32) & 0xFFFFu) | (len << 16) | (fi << 24) | (rl << 25),
-                                         (uint32_t)by, (uint32_t)(by >> 32));
-                    }
-                    if (!ballot(lng)) {
-                        if (n_pend + r > (unsigned)PEND_CAP) {
-                            walk_pending(n_pend);
-                            n_pend = 0;
-                        }
-                        if (lane < r) a.pend[(uint64_t)bid * 64u + n_pend + lane] = ent;
-                        n_pend += r;
-                        wend = 0;
-                    }
-                }
-            }
-            if constexpr (!BULK) {   // the walkers take what the hash pass leaves
-                if (total > 0) {
-                    wend = hash_pass(total, [](unsigned i) -> unsigned { return i; });
-                    wave_sync();
-                }
-            }
-            auto tok_at = [&](unsigned i) -> unsigned { return list_ref(i); };
-            // One token walk per lane; a lane whose token is resolved writes the id and takes the
-            // next token (ballot + mbcnt), so each iteration is one trie step for 64 tokens.  A
-            // token's bytes do not depend on the trie, so each iteration issues the trie load
-            // first and does the LDS work of the next byte / atom / token (known before the
-            // load returns: the token ends when its last atom's bytes run out) under it.
-            struct Tok {
-                unsigned jj, j1, cnt, lbase;
-                uint64_t seq;
-                uint64_t out;
-                bool rl;   // raw mode's expansions (raw mode, or a '\u2581'-compressed PRESPLIT window)
-            };
-            auto tstart = [&](unsigned t) -> Tok {
-                Tok T;
-                unsigned g = 0;
-#pragma unroll
-                for (int k = 1; k < NG; k++) g += t >= pre[k] ? 1u : 0u;
-                T.lbase = g * GSTR;
-                const GL &L = *reinterpret_cast<const GL *>(smem + T.lbase);
-                const C2Slot q = *reinterpret_cast<const C2Slot *>(&L.fin[0]);
-                const unsigned k = t - q.base;
-                T.jj = (unsigned)L.rec[k].smask;
-                const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
-                T.j1 = k + 1 < q.ntk ? nx : q.na;
-                T.rl = raw || (q.fw >> 1) != 0u;
-                T.seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[T.jj], L.atom_len(T.jj), 0, q.fw & 1u & (unsigned)(T.jj == 0)), T.rl, T.cnt);
-                T.out = q.ob + k;
-                return T;
-            };
-            // NW token walks per lane (tokens lane, lane + 64, ... first), so that many trie loads are
-            // in flight per lane in every iteration
-            constexpr int NW = 1;
-            bool active[NW];
-            Tok C[NW];
-            int32_t node[NW], nb[NW];
-            bool ok[NW];
-#pragma unroll
-            for (int w = 0; w < NW; w++) {
-                active[w] = wbeg + lane + 64u * w < wend;
-                C[w].jj = C[w].j1 = C[w].cnt = C[w].lbase = 0; C[w].seq = 0; C[w].out = 0; C[w].rl = raw;
-                if (active[w]) C[w] = tstart(tok_at(wbeg + lane + 64u * w));
-                node[w] = 0; nb[w] = tv.root_base; ok[w] = true;
-            }
-            unsigned nxt = wbeg + 64u * NW;
-            for (;;) {
-                bool any = false;
-#pragma unroll
-                for (int w = 0; w < NW; w++) any |= active[w];
-                if (!ballot(any)) break;
-                int32_t sl[NW];
-                int4 ent[NW];
-#pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    sl[w] = nb[w] + (int32_t)(C[w].seq & 0xFFu);
-                    ent[w] = trie_slot4(tv, sl[w]);   // buffer load: inactive walks read harmlessly
-                }
-                // ---- under the loads: the next byte or atom
-                bool done[NW];
-#pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    C[w].seq >>= 8;
-                    C[w].cnt -= 1u;
-                    const unsigned aend = (active[w] ? 1u : 0u) & (unsigned)(C[w].cnt == 0);
-                    const unsigned dn = aend & (unsigned)(C[w].jj + 1 == C[w].j1);
-                    done[w] = dn != 0;
-                    if (aend & (dn ^ 1u)) {
-                        C[w].jj++;
-                        const GL &L = *reinterpret_cast<const GL *>(smem + C[w].lbase);
-                        C[w].seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[C[w].jj], L.atom_len(C[w].jj), 0, 0), C[w].rl, C[w].cnt);
-                    }
-                }
-                // ---- the trie steps; finished walks write their id and take the next token
-#pragma unroll
-                for (int w = 0; w < NW; w++) {
-                    ok[w] &= ent[w].y == node[w];
-                    node[w] = sl[w];
-                    nb[w] = ent[w].x & BASE_MASK;
-                    const uint64_t dm = ballot(done[w]);
-                    if (done[w]) {
-                        const int32_t idv = ok[w] ? ent[w].z : -1;   // the id arrives with the token's last node
-                        if (n16) a.staging16[C[w].out] = (int16_t)idv;
-                        else a.staging[C[w].out] = idv;
-                        const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(dm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)dm, 0u));
-                        active[w] = uu < wend;
-                        if (active[w]) C[w] = tstart(tok_at(uu));
-                        node[w] = 0; nb[w] = tv.root_base; ok[w] = true;
-                    }
-                    nxt += (unsigned)__builtin_popcountll(dm);
-                }
-            }
-        }
-        wave_sync();
-        STAMP(7);
-
-        // ---------------------------------------------------------- advance slots, finish strings
-        KREFRESH();
+    // The last phase of a slot round (tokenize_body): advance the slots past their window, finish the strings that end
+    // with it.  Reads and writes the slot states only; len_only: the call wants no ids.
+    static __device__ __forceinline__ void advance_slots(ConstKernArgs *kp, unsigned lane, bool len_only) {
+        const auto &a = kp->ea;
         if (lane < (unsigned)NG) {
             SlotState &S = SSr(lane);
             if (S.active && S.n_atoms > 0 && S.status == 0 && (S.inval & 2)) {
@@ -2956,30 +1496,1527 @@ __device__ __forceinline__ void tokenize_body(const unsigned bid) {
                 }
             }
         }
-        wave_sync();
-        STAMP(4);
-        STAMP(8);
-        WST_REC(1 + min(wst_it, WST_N - 4), WST_NOW() | ((unsigned long long)busy << 56));
-        wst_it++;
     }
-    if constexpr (G == 16 && !BIG)
-        if (n_pend) {
-            walk_pending(n_pend);
-            n_pend = 0;
-        }
-    if (!BIG && a.solo && lane == 0) {   // the call's only string, the grid's only wave
-        a.id_off[0] = 0;
-        reset_counters(a.retry_count, a.ctr_snap);
-    }
-    STAMP(9);
-    STAMP_FLUSH;
-    WST_REC(WST_N - 1, WST_NOW() | ((unsigned long long)wst_it << 48));
+
+    static __device__ __forceinline__ void body(const unsigned bid) {
+        ConstKernArgs *kp = (ConstKernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+#define a (kp->ea)
+#define tv (tv_of(kp))
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+        const unsigned lane = lane_id();
+        const unsigned mg = lane / G;        // my group
+        const unsigned d = lane % G;         // my back distance - 1
+        const uint64_t n_work = BIG ? (uint64_t)(*a.work_count) : a.n_str;
+        if constexpr (BIG)
+            if (a.hist_zero && bid == 0)
+                for (uint32_t b = lane; b < a.n_hist; b += 64u) a.hist_zero[b] = 0;
+        if (BIG && n_work == 0) return;   // no retries: no counter traffic
+        const uint64_t base_off = a.str_off[0];
+        // (the other instantiations keep the mode a run-time value: folding raw = false into the atoms-mode
+        // 16-lane kernel crashes ROCm 7.2's greedy register allocator)
+        // RAW / MC >= 0: the mode as a compile-time constant (PRESPLIT, ATOMS; the other instantiations read it)
+        const int mode = RAW ? 0 : (MC >= 0 ? MC : (a.mode & DPT_MODE_MASK));
+        const bool raw = mode == 0;
+        const bool uncapped = !PLAIN && (a.mode & DPT_FLAG_UNCAPPED) != 0;   // f2: inspect_tokenizer's inf-initialised DP
+        const bool len_only = !PLAIN && (a.mode & (DPT_FLAG_UNCAPPED | DPT_FLAG_LEN_ONLY)) != 0;
+        // Strings are handed out by npart device counters (each in its own 256-byte line).  Partition p
+        // holds the FIN_BATCH-string chunks p, p + npart, p + 2 npart, ... of the batch, in that order
+        // (part_size / part_string): the partitions advance through the batch side by side, so strings
+        // finish roughly in batch order.  A wave claims as many strings as it has free slots from its current partition (starting on
+        // blockIdx mod npart) and, when a claim reaches the partition's end, marks the partition in a
+        // shared mask and moves to the next unmarked one.  Round 1's single counter (one same-address
+        // atomic per refill) bound the whole kernel: a prep-only build ran 2.91 of the full build's 2.99
+        // ms, every wave queued behind ~5.6k others' atomics (profiles/r02_phase_diag.txt).  No string is
+        // claimed ahead of a free slot: strings held in reserve by one wave left others idle at the end
+        // of multi-window batches (cfg4 4.35 -> 4.56 ms with 4-string claims).
+        const unsigned npart = (BIG || (DPT_DIAG_PREP & 1)) ? 1u : (unsigned)min((uint64_t)NPART, max((uint64_t)1, n_work / 4096u));
+        [[maybe_unused]] uint64_t diag_k = 0;   // DPT_DIAG_PREP & 1: the wave's claims so far
+        unsigned part = BIG ? 0u : bid % npart;
+        bool exhausted = false, claimed_all = false;
+        unsigned n_pend = 0;   // 16-lane first pass: residual tokens waiting in the wave's pending row
+        // one claim of up to req strings (uniform): partition-local [nb, ne) of partition cp, possibly
+        // empty once every partition is used up
 #ifdef DPT_WSTAMPS
-    WST_REC(WST_N - 2, wst_claims);
+        unsigned wst_claims = 0;
+#define WST_CLAIM() (wst_claims++)
+#else
+#define WST_CLAIM()
+#endif
+        auto claim = [&](unsigned req, uint64_t &nb, uint64_t &ne, unsigned &cp) {
+            for (;;) {
+                WST_CLAIM();
+                uint32_t *ctr = BIG ? a.work_next : a.part_ctr + part * PART_STRIDE;
+                const uint64_t hi = BIG ? n_work : part_size((unsigned)n_work, npart, part);
+                unsigned b = 0;
+                if constexpr (!BIG && (DPT_DIAG_PREP & 1)) {   // diagnostic: wave bid's k-th claim, blocks of 4
+                    b = (unsigned)((diag_k * gridDim.x + bid) * 4u);
+                    diag_k++;
+                } else {
+                    if (lane == 0) b = atomicAdd(ctr, req);
+                    if constexpr (!BIG && (DPT_DIAG_PREP & 4)) {   // diagnostic: one more dependent atomic round trip
+                        unsigned x = 0;
+                        asm volatile("" : "+v"(b));
+                        if (lane == 0) x = atomicAdd(ctr + (b >> 31), 0u);
+                        asm volatile("" : "+v"(x));
+                        b |= (x >> 31) << 31;
+                    }
+                }
+                cp = __builtin_amdgcn_readfirstlane(part);
+                nb = (uint32_t)__builtin_amdgcn_readlane(b, 0);
+                ne = nb < hi ? (nb + req < hi ? nb + req : hi) : nb;
+                if (nb + req >= hi) {   // the partition is used up (by this claim or earlier ones)
+                    if (BIG) {
+                        claimed_all = true;
+                    } else {
+                        unsigned m = 0;
+                        if (lane == 0) m = atomicOr(a.part_ctr + (unsigned)NPART * PART_STRIDE, 1u << part);
+                        m = __builtin_amdgcn_readlane(m, 0) | (1u << part);
+                        const unsigned all = (npart >= 32u ? 0u : (1u << npart)) - 1u;
+                        if ((m & all) == all) {
+                            claimed_all = true;
+                        } else {   // the next unmarked partition after this one
+                            const unsigned free = ~m & all;
+                            const unsigned hi_free = free & ~((2u << part) - 1u);
+                            part = (unsigned)__builtin_ctz(hi_free ? hi_free : free);
+                        }
+                    }
+                }
+                if (ne > nb || claimed_all) return;
+            }
+        };
+
+        [[maybe_unused]] Stamps st;
+        WST_REC(0, WST_NOW());
+        [[maybe_unused]] unsigned wst_it = 0;
+
+        if (lane < (unsigned)NG) SSr(lane).active = 0;
+        wave_sync();
+
+        // C0, C2, walk_pending and advance_slots are functions (above); the other phases stay inline here, each for a
+        // resource that moved when it alone was made a function with the same body (the phase table):
+        //   refill and prep, claim: W[NG] below then no longer lives across this loop -- 16 VGPRs fewer, VGPR spills
+        //     9 -> 3, cfg2 1.9 % and cfg5 2.5 % slower; the claim state as a struct stops the 16-lane kernels compiling
+        //   A:  VGPR spills 6 -> 9 (scratch 28 -> 40) in the RAW int16 kernel, 9 -> 10 and 14 -> 15 in the runtime-mode ones
+        //   B:  VGPR spills 6 -> 8 (scratch 28 -> 36) in the RAW kernels, mid_kernel's VGPRs + 1
+        //   C1: SGPR spills + 1 to + 3 in 17 kernels (23 -> 25 in the RAW int16 kernel)
+        for (;;) {
+            KREFRESH();
+            // ---------------------------------------------------------- slots: fetch strings, find windows, prep
+            // Inactive slots are refilled together (one counter atomic, offsets loaded by one lane
+            // per slot), and every slot's window bytes are loaded before any is atomised, so the
+            // HBM round trips of the NG slots overlap.
+            unsigned busy = 0, prepared = 0;
+            for (;;) {
+                unsigned need = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) need |= uni(SSr(g).active) ? 0u : (1u << g);
+                if (need && !exhausted) {
+                    // claims until every free slot has a string or every partition is used up (a claim
+                    // that reaches a partition's end may return fewer strings than asked)
+                    unsigned rem = need;
+                    // partition-local strings [nb, ne) of partition cp into the free slots of rem, in order
+                    auto assign = [&](uint64_t nb, uint64_t ne, unsigned cp) {
+                        const unsigned got = (unsigned)(ne - nb);
+                        if (lane < (unsigned)NG && ((rem >> lane) & 1u)) {
+                            const unsigned k = (unsigned)__builtin_popcount(rem & ((1u << lane) - 1u));
+                            if (k < got) {
+                                const uint64_t idx = nb + k;
+                                const uint64_t s = BIG ? (uint64_t)a.work_list[idx] : part_string(npart, cp, (unsigned)idx);
+                                uint64_t o0, o1;
+                                if constexpr (!BIG && (DPT_DIAG_PREP & 2)) { o0 = s * 256u; o1 = o0 + 256u; }   // diagnostic (cfg2)
+                                else { o0 = a.str_off[s]; o1 = a.str_off[s + 1]; }
+                                SlotState &S = SSr(lane);
+                                S.s = (uint32_t)s; S.sb = o0 - base_off; S.slen = (uint32_t)(o1 - o0); S.pos = 0; S.active = 1;
+                                S.status = o1 == o0 ? 2u : 0u;  // pretokenize_raw('') == [[]] -> IndexError
+                                S.ntok = 0; S.capsum = 0; S.abase = 0;
+                            }
+                        }
+                        for (unsigned q = 0; q < got; q++) rem &= rem - 1u;   // those slots are filled
+                    };
+                    while (rem && !claimed_all) {
+                        const unsigned n_need = (unsigned)__builtin_popcount(rem);
+                        uint64_t nb = 0, ne = 0;
+                        unsigned cp = 0;
+                        claim(n_need, nb, ne, cp);
+                        assign(nb, ne, cp);
+                    }
+                    if (claimed_all) exhausted = true;
+                    wave_sync();
+                }
+                unsigned todo = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) todo |= (uni(SSr(g).active) && !((prepared >> g) & 1u)) ? (1u << g) : 0u;
+                if (!todo) break;
+                WinRegs<CH> W[NG];
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    if (!((todo >> g) & 1u)) continue;
+                    const uint64_t sb = uni64(SSr(g).sb);
+                    load_window<CH>(W[g], a.text + sb, raw ? nullptr : a.cut_mask + sb, uni64(SSr(g).pos), uni64(SSr(g).slen), raw, lane);
+                }
+                bool refill = false;
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    if (!((todo >> g) & 1u)) continue;
+                    GL &L = grp(g);
+                    SlotState &S = SSr(g);
+                    const uint64_t slen = uni64(S.slen), pos = uni64(S.pos);
+                    unsigned status = uni(S.status);
+                    unsigned wlen = 0, na = 0, nw = 0, cpw = 0;
+                    bool ok = status != 2;
+                    if (ok) ok = window_bounds<CH>(W[g], slen, pos, mode, lane, wlen);
+                    if (ok) ok = prep_window<CH, G, WIDE>(L, wsl_of(kp, bid, g), W[g], pos, wlen, mode, lane, na, nw, cpw);
+                    if (ok) {
+                        if (lane == 0) { S.wlen = wlen; S.n_atoms = na; S.n_words = nw; S.wtok = 0; S.inval = 0; S.capb = 0; S.cpw = (uint8_t)cpw; }
+                        prepared |= 1u << g;
+                        busy++;
+                        continue;
+                    }
+                    // the string ends here: empty, or a word (or atom) too long for this pass -- the
+                    // 2048-byte pass retries it, then the unbounded pass (status 3 is overwritten there)
+                    if (status != 2) status = 3;
+                    if (lane == 0) {
+                        const uint64_t s = S.s;
+                        if (status == 3) {
+                            // (the 512-byte pass, mid_kernel: its retry_* fields are the 2048-byte pass's list)
+                            uint32_t *cnt = (BIG && CH > 512) ? a.long_count : a.retry_count;
+                            uint32_t *lst = (BIG && CH > 512) ? a.long_list : a.retry_list;
+                            lst[atomicAdd(cnt, 1u)] = (uint32_t)s;
+                        }
+                        a.status[s] = (int32_t)status;
+                        if (a.capped) a.capped[s] = status == 2 ? 0 : -1;
+                        S.active = 0;
+                        a.counts[s] = 0;
+                    }
+                    refill = true;
+                }
+                wave_sync();
+                if (!refill || exhausted) break;
+            }
+            if (lane < (unsigned)NG && !((prepared >> lane) & 1u)) { SSr(lane).n_atoms = 0; SSr(lane).n_words = 0; SSr(lane).capb = 0; }
+            wave_sync();
+            if (busy == 0) break;
+            STAMP(0);
+
+            // ---------------------------------------------------------- A: match discovery (all slots)
+            KREFRESH();
+            if (DPT_STOP > 1) {
+                // A0 (16-lane rows, raw mode): slots whose window is pure ASCII -- atoms are its bytes --
+                // get every walk's first lookup here, byte-parallel with four loads in flight per lane;
+                // the walks it cannot finish (word starts, the string's first atom, '\n', and walks that
+                // go on past the two-byte root entry: ~6 % in cfg2 with the child filters) are marked
+                // (bit 4g + u of `mark`: atom 4 * lane + u of slot g) and redone by the walker below,
+                // which also takes every atom of the other slots.
+                unsigned a0mask = 0;
+                uint32_t mark = 0;
+                if constexpr (G == 16 && !BIG) {
+                    if (!raw) {   // PRESPLIT: the '\u2581'-compressed windows (prep_window)
+#pragma unroll
+                        for (int g = 0; g < NG; g++)
+                            if (uni(SSr(g).n_atoms) > 0 && uni(SSr(g).cpw)) a0mask |= 1u << g;
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < NG; g++) {
+                            const unsigned wl = uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).wlen) : 0u;
+                            const uint32_t *b32 = reinterpret_cast<const uint32_t *>(grp(g).bytes);
+                            const uint32_t w0 = 4u * lane < wl ? b32[lane] : 0u;
+                            const unsigned nv = wl > 4u * lane ? min(wl - 4u * lane, 4u) : 0u;   // valid bytes in w0
+                            const uint32_t hi = w0 & (nv >= 4u ? 0x80808080u : ((1u << (8u * nv)) - 1u) & 0x80808080u);
+                            if (wl && !ballot(hi != 0)) a0mask |= 1u << g;
+                        }
+                    }
+                }
+                unsigned nstart[NG];   // walker starts per slot: all atoms, or A0's marked ones
+#pragma unroll
+                for (int g = 0; g < NG; g++) nstart[g] = uni(SSr(g).n_atoms);
+                unsigned fwmask = 0;   // slots whose window starts the string (raw: '▁' + first atom)
+#pragma unroll
+                for (int g = 0; g < NG; g++) fwmask |= (raw && uni(SSr(g).pos) == 0 ? 1u : 0u) << g;
+                // One walk per lane.  Walk state: start atom j, the LDS byte offset of its slot's group,
+                // atoms matched so far (len), the trie node, the expanded bytes left of the current atom
+                // (seq, cnt) and its descriptor (info).  Finished walks take the next start (ballot +
+                // mbcnt), so the wave stays busy.
+                unsigned j = 0, lbase = 0, len = 0, cnt = 0, info = 0, t2 = 0, gsel = 0;
+                unsigned capm = 0;   // bit g: slot g's capb (set after the walks)
+                bool split = false;
+                int32_t nb = tv.root_base, node = 0;
+                uint64_t seq = 0;
+                M mask = 0;   // G = 16: bit 0 only (the single-atom span is a token)
+                // G = 16: the span of len atoms ending at end position e is a token: clear bit len-1
+                // of e's inverted end mask (the high half of rec[e]; one LDS atomic, no return)
+                auto end_token = [&](unsigned e, unsigned ln) {
+                    uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + lbase);
+                    __hip_atomic_fetch_and(&r32[e], ~(1u << (15u + ln)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                };
+                auto end_token_at = [&](unsigned lb, unsigned e, unsigned ln) {   // (the group at LDS byte lb)
+                    uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + lb);
+                    __hip_atomic_fetch_and(&r32[e], ~(1u << (15u + ln)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                };
+                auto grp_bytes_at = [&](unsigned lb, unsigned p) -> unsigned {   // window byte p (p < CH + 16) of that group
+                    return reinterpret_cast<const GL *>(smem + lb)->bytes[p];
+                };
+                auto start_gj = [&](unsigned gs, unsigned jj) {
+                    j = jj;
+                    gsel = gs;
+                    lbase = gs * GSTR;
+                    const GL &L = *reinterpret_cast<const GL *>(smem + lbase);
+                    info = ainfo_get(L, j, raw && ((fwmask >> gs) & 1u));
+                    seq = atom_from_info<CH, WIDE>(L.bytes, info, raw, cnt);
+                    nb = tv.root_base; node = 0; len = 0; mask = 0;
+                    // The first two expanded bytes go through one lookup of the two-byte root table
+                    // (TrieView): within atom j, or across its end when the word continues (then
+                    // atom j+1 is loaded now instead of at the first atom end).
+                    const unsigned b0 = (unsigned)(seq & 0xFFu);
+                    if (cnt >= 2) {
+                        t2 = tv.n_slots + (b0 << 8) + (unsigned)((seq >> 8) & 0xFFu);
+                        split = false;
+                        seq >>= 16;
+                        cnt -= 2;
+                    } else if (!(info & AInfo<CH>::STOP)) {
+                        info = ainfo_get(L, j + 1, false);
+                        seq = atom_from_info<CH, WIDE>(L.bytes, info, raw, cnt);
+                        t2 = tv.n_slots + (b0 << 8) + (unsigned)(seq & 0xFFu);
+                        split = true;
+                        seq >>= 8;
+                        cnt -= 1;
+                    } else {
+                        t2 = 0;
+                    }
+                };
+                if constexpr (G == 16 && !BIG) {
+                    if (a0mask) {
+                        constexpr unsigned END = 0x100u;
+#pragma unroll
+                        for (int g = 0; g < NG; g++) {
+                            if (!((a0mask >> g) & 1u)) continue;
+                            // (window bytes in LDS = atoms: raw ASCII windows and '\u2581'-compressed ones alike)
+                            const unsigned wl = uni(SSr(g).n_atoms);
+                            const bool first = raw && uni(SSr(g).pos) == 0;
+                            const unsigned gbase = (unsigned)g * GSTR;
+                            const uint32_t *b32 = reinterpret_cast<const uint32_t *>(grp(g).bytes);
+                            const unsigned k0 = 4u * lane;
+                            if constexpr (A0_SWAR) {
+                                // The lane's four bytes as one 32-bit word (SWAR): every per-byte flag is bit 7 of
+                                // its byte, so one VALU op tests four bytes.  Views: w0 = bytes k0..k0+3 (b), n1w =
+                                // k0+1.. (the next byte), n2w = k0+2.. (the one after).
+                                constexpr uint32_t H = 0x80808080u;
+                                const uint32_t w0 = b32[lane], w1 = b32[lane + 1u];
+                                const uint32_t n1w = __builtin_amdgcn_alignbyte(w1, w0, 1u);
+                                const uint32_t n2w = __builtin_amdgcn_alignbyte(w1, w0, 2u);
+                                // lookups at (b, n1) as read: the table holds (b, '<')'s entry at (b, '\n') too,
+                                // and (b, END)'s flags of b are (b, anything)'s (dpt_api.cpp)
+                                uint2 ent[4];
+#pragma unroll
+                                for (int u = 0; u < 4; u++)
+                                    ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[
+                                        __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)];
+                                // bytes past the window (END): byte q of the 8 is valid while q < nv
+                                const unsigned nv = wl > k0 ? min(wl - k0, 8u) : 0u;
+                                const uint64_t vm = nv >= 8u ? ~0ull : ((1ull << (8u * nv)) - 1ull);
+                                const uint32_t vlo = (uint32_t)vm, vhi = (uint32_t)(vm >> 32);
+                                const uint32_t v0 = vlo & H, v1 = __builtin_amdgcn_alignbyte(vhi, vlo, 1u) & H,
+                                               v2 = __builtin_amdgcn_alignbyte(vhi, vlo, 2u) & H;
+                                auto eq80 = [](uint32_t x, uint32_t c) -> uint32_t {   // bit 7 of each byte of x equal to c's
+                                    const uint32_t t = x ^ c;
+                                    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
+                                };
+                                const uint32_t sp0 = eq80(w0, 0x20202020u), sp1w = eq80(w1, 0x20202020u);
+                                const uint32_t nl0 = eq80(w0, 0x0A0A0A0Au), nl1w = eq80(w1, 0x0A0A0A0Au);
+                                const uint32_t sp1 = __builtin_amdgcn_alignbyte(sp1w, sp0, 1u), sp2 = __builtin_amdgcn_alignbyte(sp1w, sp0, 2u);
+                                const uint32_t nl1 = __builtin_amdgcn_alignbyte(nl1w, nl0, 1u), nl2 = __builtin_amdgcn_alignbyte(nl1w, nl0, 2u);
+                                const uint32_t special = sp0 | nl0 | ((first && lane == 0) ? 0x80u : 0u);   // the walker's
+                                const uint32_t norm = v0 & ~special;
+                                const uint32_t cont = v1 & ~sp1;   // n1 is in the word
+                                // the entries' flag bytes side by side (bit 0 root child, 1 b a token, 2 node b n1,
+                                // 3 it ends a token, 4 it is a leaf) and their child-filter bits for n2
+                                const uint32_t xs = __builtin_amdgcn_perm(ent[1].x, ent[0].x, 0x0C0C0400u) |
+                                                    (__builtin_amdgcn_perm(ent[3].x, ent[2].x, 0x0C0C0400u) << 16);
+                                const uint32_t cb = n2w ^ ((n2w >> 5) & 0x07070707u);   // child_bit(byte) in each byte's low 5 bits
+                                const uint32_t f0 = ent[0].y >> (cb & 31u), f1 = ent[1].y >> ((cb >> 8) & 31u),
+                                               f2 = ent[2].y >> ((cb >> 16) & 31u), f3 = ent[3].y >> ((cb >> 24) & 31u);
+                                const uint32_t fb = (__builtin_amdgcn_perm(f1, f0, 0x0C0C0400u) |
+                                                     (__builtin_amdgcn_perm(f3, f2, 0x0C0C0400u) << 16)) << 7;
+                                const uint32_t tok1 = (xs << 7) & (xs << 6);
+                                const uint32_t has2 = norm & cont & (xs << 5);
+                                // go on past two bytes: n2 in the word with a child for it; '\n' at n1 or n2 ("<0x0A>")
+                                // always (the walker redoes such starts whole)
+                                const uint32_t more = has2 & ~(xs << 3) & (nl1 | (v2 & (nl2 | (~sp2 & fb))));
+                                const uint32_t tk1 = norm & tok1;                  // a one-atom token ends at k0+1+u
+                                const uint32_t tk2 = has2 & ~nl1 & (xs << 4);      // a two-atom token ends at k0+2+u
+                                uint32_t mk = ((v0 & special) | more) & H;   // walker starts
+                                if constexpr (A0_R2) {
+                                    // Third-byte round: a walk that goes on past two plain bytes of the word takes
+                                    // its root-table step (the node after the pair) and its third step here,
+                                    // byte-parallel, and stays for the walker only if it goes on past three
+                                    // (cfg4: ~97 % of these walks end there).  The three-atom token, if any, is
+                                    // recorded here.  Slots with few such walks leave them to the walker.
+                                    const uint32_t r2 = more & ~nl1 & ~nl2 & H;
+                                    if (__builtin_popcountll(ballot(r2 != 0)) >= A0_R2_MIN) {
+                                        const uint32_t v3 = __builtin_amdgcn_alignbyte(vhi, vlo, 3u) & H;
+                                        const uint32_t sp3 = __builtin_amdgcn_alignbyte(sp1w, sp0, 3u);
+                                        const uint32_t nl3 = __builtin_amdgcn_alignbyte(nl1w, nl0, 3u);
+                                        const uint32_t n3w = __builtin_amdgcn_alignbyte(w1, w0, 3u);
+                                        constexpr int32_t OOB = 0x7FFFFFF;   // past the table: the buffer load returns zeros
+                                        int4 e2r[4], e3[4];
+#pragma unroll
+                                        for (int u = 0; u < 4; u++)   // the root table's entry of (b, n1)
+                                            e2r[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ? (int32_t)(tv.n_slots +
+                                                     __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)) : OOB);
+#pragma unroll
+                                        for (int u = 0; u < 4; u++)   // the node after n2
+                                            e3[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ?
+                                                    (int32_t)((e2r[u].x & BASE_MASK) + ((n2w >> (8 * u)) & 0xFFu)) : OOB);
+                                        uint32_t c3 = 0, t3 = 0;
+#pragma unroll
+                                        for (int u = 0; u < 4; u++) {
+                                            const unsigned n3 = (n3w >> (8 * u)) & 0xFFu;
+                                            const unsigned ok3 = ((r2 >> (8 * u + 7)) & 1u) & (unsigned)(e3[u].y == (e2r[u].y & 0x3FFFFFFF));
+                                            const unsigned leaf3 = ((unsigned)e3[u].x >> 30) & 1u;
+                                            const unsigned in3 = ((v3 & ~sp3) >> (8 * u + 7)) & 1u;
+                                            const unsigned ch3 = (((unsigned)e3[u].w >> child_bit(n3)) & 1u) | ((nl3 >> (8 * u + 7)) & 1u);
+                                            t3 |= (ok3 & ((unsigned)e3[u].x >> 31)) << (8 * u + 7);
+                                            c3 |= (ok3 & (leaf3 ^ 1u) & in3 & ch3) << (8 * u + 7);
+                                        }
+                                        mk = ((v0 & special) | (more & ~r2) | c3) & H;
+                                        if (ballot(t3 != 0)) {   // a three-atom token ends at k0+3+u
+                                            uint32_t *q32 = reinterpret_cast<uint32_t *>(smem + gbase);
+#pragma unroll
+                                            for (int u = 0; u < 4; u++)
+                                                __hip_atomic_fetch_and(&q32[k0 + 3u + u],
+                                                                       ~(((t3 >> (8 * u + 7)) & 1u) << 18),
+                                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        }
+                                    }
+                                }
+                                const uint32_t t2e = (tk2 << 8) | wave_shift_in(tk2 >> 24, 0u);
+                                // end k0+1+u: bit 0 of byte u of d a one-atom token, bit 1 a two-atom one
+                                const uint32_t d = ((tk1 & H) >> 7) | ((t2e & H) >> 6);
+                                uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
+                                if (ballot(d != 0)) {
+#pragma unroll
+                                    for (int u = 0; u < 4; u++)
+                                        __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~(((d >> (8 * u)) & 3u) << 16),
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                }
+                                if (ballot((norm & ~tok1) != 0) && lane == 0) SSr(g).capb = 1;
+                                // the slot's marked atoms, in order, into its fin[] (free until phase B)
+                                const unsigned c = (unsigned)__builtin_popcount(mk);
+                                const unsigned incl = wave_incl_scan_add(c);
+                                unsigned o = incl - c;
+                                GL &Lg = grp(g);
+#pragma unroll
+                                for (int u = 0; u < 4; u++)
+                                    if ((mk >> (8 * u + 7)) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
+                                nstart[g] = __builtin_amdgcn_readlane(incl, 63);
+                                continue;
+                            }
+                            // bytes k0 .. k0+7 (past the window: masked by wl below)
+                            const uint64_t w = (uint64_t)b32[lane] | ((uint64_t)b32[lane + 1u] << 32);
+                            auto byte_at = [&](unsigned q) -> unsigned {   // byte k0+q, END past the window
+                                return k0 + q < wl ? (unsigned)((w >> (8u * q)) & 0xFFu) : END;
+                            };
+                            uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
+                            bool nocap = false;
+                            unsigned tk1 = 0, tk2 = 0;
+                            // the packed byte-pair table over (byte, next byte): the flags of the first byte do
+                            // not depend on the second; four lookups in flight per lane
+                            uint2 ent[4];
+#pragma unroll
+                            for (int u = 0; u < 4; u++) {
+                                const unsigned b = byte_at(u), n1 = byte_at(u + 1);
+                                const unsigned e1 = n1 == '\n' ? (unsigned)'<' : n1;
+                                ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[((b & 0xFFu) << 8) | (e1 & 0xFFu)];
+                            }
+                            // Per byte: tk1 bit u = a one-atom token ends at k0+1+u, tk2 bit u = a two-atom
+                            // token ends at k0+2+u (the end masks are written once below)
+                            // (flags as 0/1 integers combined with & and |: short-circuit forms become
+                            // exec-mask branches here)
+#pragma unroll
+                            for (int u = 0; u < 4; u++) {
+                                const unsigned k = k0 + (unsigned)u;
+                                const unsigned b = byte_at(u), n1 = byte_at(u + 1), n2 = byte_at(u + 2);
+                                const auto e = ent[u];
+                                const unsigned valid = (unsigned)(b != END);
+                                const unsigned special = (unsigned)(b == ' ') | (unsigned)(b == '\n') | ((unsigned)first & (unsigned)(k == 0));   // the walker's
+                                const unsigned norm = valid & (special ^ 1u);
+                                // n1 ends the word: the lookup was the atom's own root slot
+                                const unsigned wend = (unsigned)(n1 == END) | (unsigned)(n1 == ' ');
+                                const unsigned xterm = ((unsigned)e.x >> 3) & 1u, xleaf = ((unsigned)e.x >> 4) & 1u;
+                                const unsigned tok1 = (unsigned)e.x & ((unsigned)e.x >> 1) & 1u;
+                                const unsigned node2 = ((unsigned)e.x >> 2) & 1u;
+                                const unsigned filt = (unsigned)e.y;
+                                nocap |= (norm & (tok1 ^ 1u)) != 0;
+                                // a node after two bytes: n1 = '\n' leaves the walk inside "<0x0A>" after
+                                // its '<'; otherwise atom k+1 is consumed (the span k .. k+2)
+                                const unsigned has2 = norm & (wend ^ 1u) & node2;
+                                const unsigned nl1 = (unsigned)(n1 == '\n');
+                                const unsigned e2 = nl1 ? (unsigned)'0' : (n2 == '\n' ? (unsigned)'<' : n2);
+                                const unsigned more = has2 & (xleaf ^ 1u) & (nl1 | ((unsigned)(n2 != END) & (unsigned)(n2 != ' '))) &
+                                                      ((filt >> child_bit(e2)) & 1u);
+                                tk1 |= (norm & tok1) << u;
+                                tk2 |= (has2 & (nl1 ^ 1u) & xterm) << u;
+                                mark |= ((valid & special) | more) << (4 * g + u);
+                            }
+                            // end k0+1+u: tk1 bit u, and tk2 bit u-1 (u = 0: the previous lane's bit 3)
+                            const unsigned t2e = ((tk2 << 1) & 0xEu) | wave_shift_in((tk2 >> 3) & 1u, 0u);
+                            if (ballot((tk1 | t2e) != 0)) {
+                                // (lane l's dwords are 4l+1 .. 4l+4: lanes l, l+8, l+16, l+24 of a 32-lane group hit
+                                // one bank; a rotated order (r03) and a transposed one -- round q's lane l taking
+                                // end 64q+l+1, its bits gathered by ds_bpermute (r04) -- cost VGPR spills instead)
+#pragma unroll
+                                for (int u = 0; u < 4; u++)
+                                    __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~((((tk1 >> u) & 1u) << 16) | (((t2e >> u) & 1u) << 17)),
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
+                            if (ballot(nocap) && lane == 0) SSr(g).capb = 1;
+                            // the slot's marked atoms, in order, into its fin[] (free until phase B)
+                            const unsigned mg = (mark >> (4 * g)) & 15u;
+                            const unsigned c = (unsigned)__builtin_popcount(mg);
+                            const unsigned incl = wave_incl_scan_add(c);
+                            unsigned o = incl - c;
+                            GL &Lg = grp(g);
+#pragma unroll
+                            for (int u = 0; u < 4; u++)
+                                if ((mg >> u) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
+                            nstart[g] = __builtin_amdgcn_readlane(incl, 63);
+                        }
+                    }
+                }
+                // ASCII walker: the marked starts of A0 slots (pure-ASCII raw windows: an atom is one byte, a
+                // word start ' ' is '\u2581' = the trie node ws_node, '\n' is "<0x0A>", the string's first
+                // atom '\u2581' + its byte) walked byte by byte without the generic walker's atom
+                // descriptors.  A "more" start (a plain byte whose walk goes past A0's two-byte lookup, its one-
+                // and two-atom tokens already recorded by A0) repeats that lookup in the root table and goes on
+                // from the node after two bytes.  The generic walker below takes the other slots.
+                if constexpr (G == 16 && !BIG) {
+                    if (a0mask) {
+                        unsigned fpre[NG + 1];
+                        fpre[0] = 0;
+#pragma unroll
+                        for (int g = 0; g < NG; g++) {
+                            fpre[g + 1] = fpre[g] + (((a0mask >> g) & 1u) ? nstart[g] : 0u);
+                            if ((a0mask >> g) & 1u) nstart[g] = 0;
+                        }
+                        const unsigned ftotal = fpre[NG];
+                        const int32_t wsn = a.ws_node, wsb = a.ws_base;
+                        const unsigned wst = a.ws_id >= 0 ? 1u : 0u;   // '\u2581' alone is a token
+                        const int32_t rb = tv.root_base;
+                        const unsigned nsl = tv.n_slots;
+                        // "<0x0A>" after its '<': with pc bytes left the next is byte 5 - pc of "0x0A>" (a 32-bit
+                        // constant and '>' instead of a 64-bit register pair of the bytes still to come)
+                        auto nl_byte = [](unsigned pc) -> unsigned { return pc >= 2u ? (0x41307830u >> (8u * (5u - pc))) & 0xFFu : 0x3Eu; };
+                        unsigned fj = 0, flen = 0, fp = 0, fwl = 0, cur = 0, pc = 0, fgs = 0, fl = 0, isr = 0, one = 0;
+                        // (the walker's "capb" flags, per lane and slot, written once after the walk)
+                        int32_t fnode = 0, fnb = 0, ft2 = 0;
+                        bool act = false;
+                        // a start: (walk state, or over at once -- the '\u2581' node missing / the word ends)
+                        auto fstart = [&](unsigned uu) -> bool {
+                            unsigned gs = 0;
+#pragma unroll
+                            for (int g = 1; g < NG; g++) gs += uu >= fpre[g] ? 1u : 0u;
+                            unsigned base = 0;
+#pragma unroll
+                            for (int g = 0; g < NG; g++) base = (gs == (unsigned)g) ? fpre[g] : base;
+                            fgs = gs;
+                            fl = gs * GSTR;
+                            const GL &L = *reinterpret_cast<const GL *>(smem + fl);
+                            const unsigned jj = L.fin[uu - base].v;
+                            fj = jj;
+                            fwl = SSr(gs).n_atoms;   // (= the LDS bytes: one per atom)
+                            const unsigned b0 = L.bytes[jj];
+                            isr = 0; one = 0; pc = 0;
+                            if (((fwmask >> gs) & 1u) && jj == 0) {   // '\u2581' + b0: one atom
+                                fnode = wsn; fnb = wsb; cur = b0; fp = 1; flen = 0;
+                                return wsn >= 0;
+                            }
+                            if (b0 == '\n') {
+                                fnode = 0; fnb = rb; cur = '<'; pc = 5; fp = jj + 1; flen = 0;
+                                return true;
+                            }
+                            if (b0 != ' ') {   // a "more" start: the root table over (b0, next byte)
+                                const unsigned n1 = L.bytes[jj + 1];
+                                isr = 1; one = 1;
+                                if (n1 == '\n') {   // inside atom jj+1's "<0x0A>" after its '<'
+                                    ft2 = (int32_t)(nsl + (b0 << 8) + (unsigned)'<');
+                                    flen = 1; cur = '0'; pc = 4; fp = jj + 2;
+                                } else {             // two atoms; A0 saw a third that is no word start
+                                    ft2 = (int32_t)(nsl + (b0 << 8) + n1);
+                                    const unsigned n2 = L.bytes[jj + 2];
+                                    flen = 2; fp = jj + 3;
+                                    if (n2 == '\n') { cur = '<'; pc = 5; }
+                                    else cur = n2;
+                                }
+                                return true;
+                            }
+                            // a word start: the atom '\u2581' is the node ws_node
+                            if (wsn < 0) return false;
+                            fnode = wsn; fnb = wsb; flen = 1; one = wst;
+                            if (wst) end_token_at(fl, jj + 1, 1);
+                            if (jj + 1 >= fwl) return false;
+                            const unsigned n1 = L.bytes[jj + 1];
+                            if (n1 == ' ') return false;
+                            fp = jj + 2;
+                            if (n1 == '\n') { cur = '<'; pc = 5; }
+                            else cur = n1;
+                            return true;
+                        };
+                        unsigned nxt = DPT_STOP == 21 ? ftotal : 0u;   // diagnostic: A0 only
+                        for (;;) {
+                            {
+                                const uint64_t im = ballot(!act);
+                                const unsigned nidle = (unsigned)__builtin_popcountll(im);
+                                if (nxt < ftotal && (nidle >= A_REFILL || ftotal - nxt <= nidle)) {
+                                    if (!act) {
+                                        const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
+                                        if (uu < ftotal) {
+                                            act = fstart(uu);
+                                            capm |= (unsigned)(!act && !one) << fgs;   // the start atom is no token
+                                        }
+                                    }
+                                    nxt += nidle;
+                                }
+                            }
+                            // (a start can be over at once, so a refill may leave every lane idle with starts left:
+                            // the step then runs with no lane active and changes nothing -- one back edge, so
+                            // the walk state stays in its registers across it)
+                            if (!ballot(act) && nxt >= ftotal) break;
+                            // the next raw byte, read before the trie load returns (masked off past the window)
+                            // (kept ahead of the load by a scheduling barrier: else its address register may
+                            // reuse the load's dead .z and wait for it)
+                            const unsigned nbv = grp_bytes_at(fl, fp);
+                            __builtin_amdgcn_sched_barrier(0);
+                            const int32_t t = isr ? ft2 : fnb + (int32_t)cur;
+                            const int4 ent = trie_slotA(tv, t);
+                            const unsigned y = (unsigned)ent.y;
+                            const unsigned av = act ? 1u : 0u;
+                            // (both lookups' tests as 0/1 integers: a ?: over them became an exec-mask diamond)
+                            const unsigned okr = ((y >> 30) & 1u) & (unsigned)((y & 0x3FFFFFFFu) != 0);
+                            const unsigned okp = (unsigned)(ent.y == fnode);
+                            const unsigned ok = av & ((isr & okr) | ((isr ^ 1u) & okp));
+                            fnode = isr ? (int32_t)(y & 0x3FFFFFFFu) : t;
+                            fnb = ent.x & BASE_MASK;
+                            const unsigned leaf = ((unsigned)ent.x >> 30) & 1u;
+                            // plain step: cur consumed; the atom ends unless its expansion has bytes left
+                            const unsigned aend = ok & (isr ^ 1u) & (unsigned)(pc == 0);
+                            const unsigned inexp = (isr ^ 1u) & (unsigned)(pc != 0);
+                            cur = inexp ? nl_byte(pc) : cur;
+                            pc = inexp ? pc - 1u : pc;
+                            isr = 0;
+                            flen += aend;
+                            const unsigned term = aend & ((unsigned)ent.x >> 31);
+                            one |= term & (unsigned)(flen == 1);
+                            if (term) end_token_at(fl, fj + flen, flen);
+                            // the next atom (after an atom end): a byte of the word, "<0x0A>", or the end
+                            const unsigned past = (unsigned)(fp >= fwl) | (unsigned)(flen == 16u) | (unsigned)(nbv == ' ');
+                            const unsigned stop = aend & past;
+                            const unsigned nxa = aend & (past ^ 1u);
+                            const unsigned isnl = (unsigned)(nbv == '\n');
+                            cur = nxa ? (isnl ? (unsigned)'<' : nbv) : cur;
+                            pc = (nxa & isnl) ? 5u : pc;
+                            fp += nxa;
+                            const unsigned nochild = (((unsigned)ent.w >> child_bit(cur)) & 1u) ^ 1u;
+                            const unsigned done = av & ((ok ^ 1u) | leaf | stop | nochild);
+                            capm |= (done & (one ^ 1u)) << fgs;
+                            act = act && !done;
+                        }
+                    }
+                }
+                // Byte-stream walker (the 64-lane 256-byte kernel, non-raw modes -- BLOOM-scale byte-level
+                // vocabularies): no expansions, so a walk from atom j consumes the window's bytes from
+                // aoff[j] on, and one u16 of bf[] per step says which byte comes next and whether an atom
+                // ends (or the word) before it.  The first two bytes go through the root table; each later
+                // step is one 8-byte trie load plus that one LDS read under it (the generic walker below reads
+                // the next atom's descriptor and bytes -- four LDS reads and the expansion logic -- per step).
+                // Whole-word shortcut (not when edges are an output): a word that is ONE vocabulary token has
+                // cost 1 and that token as its only shortest tokenization (every other split costs >= 2:
+                // dp_tokenize.py:24-47 then selects it); the walk from its first atom reaching the word's end
+                // on a token marks it (scf[]) and B pushes only that edge (forward_lanes64).  (Walking the word
+                // starts first, to skip the other atoms of such words, left the 64 lanes idle behind the
+                // longest walks: BLOOM 4.90 -> 5.45 ms, r05f; and so did one pass over a word-starts-first list that
+                // skips the starts inside words already known to be one token: +2 %, r05k.)
+                if constexpr (GL::BSTREAM && !BIG) {
+                    if (!raw && nstart[0] > 0) {
+                        const unsigned na_ = nstart[0];
+                        nstart[0] = 0;   // (the generic walker gets nothing)
+                        GL &L = grp(0);
+                        const bool wsc = PLAIN || a.edges == nullptr;
+                        const int32_t rb = tv.root_base;
+                        const unsigned nsl = tv.n_slots;
+                        for (unsigned jj = lane; jj < na_; jj += 64u) L.scf[jj] = 0;
+                        {
+                            const unsigned tot = na_;
+                            unsigned bj = 0, bp = 0, blen = 0, bcur = 0;
+                            int32_t bnode = 0, bnb = 0;
+                            bool bisr = false, bact = false, bws = false;
+                            uint64_t bmask = 0;
+                            // a start: p = aoff[j]; two bytes of the word: the root table, else one root step
+                            auto bstart = [&](unsigned jj) {
+                                bj = jj;
+                                const unsigned p = L.aoff[jj];
+                                const unsigned f1 = L.bf[p + 1u];   // p + 1 <= wlen
+                                const unsigned f0 = L.bf[p];
+                                const unsigned b0 = f0 & 0xFFu;
+                                bws = wsc && (f0 & BF_STOP) != 0;   // a word's first atom
+                                bisr = (f1 & BF_STOP) == 0;         // the word has a second byte
+                                bcur = bisr ? (nsl + (b0 << 8) + (f1 & 0xFFu)) : (unsigned)rb + b0;
+                                bp = p;
+                                bnode = 0; bnb = rb; blen = 0; bmask = 0;
+                            };
+                            unsigned nxt2 = DPT_STOP == 21 ? tot : 0u;
+                            for (;;) {
+                                {
+                                    const uint64_t im = ballot(!bact);
+                                    const unsigned nidle = (unsigned)__builtin_popcountll(im);
+                                    if (nxt2 < tot && (nidle >= A_REFILL64 || tot - nxt2 <= nidle)) {
+                                        if (!bact) {
+                                            const unsigned uu = nxt2 + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
+                                            if (uu < tot) { bact = true; bstart(uu); }
+                                        }
+                                        nxt2 += nidle;
+                                    }
+                                }
+                                if (!ballot(bact)) break;
+                                const int2 e2 = trie_slot(tv, (int32_t)bcur);
+                                // under the load: the flags (and byte) after this step's last byte
+                                const unsigned q = bp + (bisr ? 2u : 1u);   // <= wlen
+                                const unsigned fq = L.bf[q];
+                                const unsigned fq1 = bisr ? (unsigned)L.bf[bp + 1u] : 0u;
+                                const unsigned av = bact ? 1u : 0u;
+                                const unsigned y = (unsigned)e2.y;
+                                unsigned ok;
+                                if (bisr) {
+                                    // root table: .y = node after two bytes | first byte exists << 30 | it ends a token << 31
+                                    const unsigned tok1 = av & (unsigned)((fq1 & BF_ATOM) != 0) & (y >> 30) & (y >> 31);
+                                    bmask |= (uint64_t)tok1;
+                                    blen = (fq1 & BF_ATOM) ? 1u : 0u;
+                                    ok = av & (y >> 30) & (unsigned)((y & 0x3FFFFFFFu) != 0);
+                                    bnode = (int32_t)(y & 0x3FFFFFFFu);
+                                } else {
+                                    ok = av & (unsigned)(e2.y == bnode);
+                                    bnode = (int32_t)bcur;
+                                }
+                                bnb = e2.x & BASE_MASK;
+                                const unsigned leaf = ((unsigned)e2.x >> 30) & 1u;
+                                const unsigned aend = ok & (unsigned)((fq & BF_ATOM) != 0);
+                                blen += aend;
+                                const unsigned term = aend & ((unsigned)e2.x >> 31);
+                                bmask |= term ? 1ull << (blen - 1u) : 0ull;
+                                const unsigned stop = aend & (unsigned)((fq & BF_STOP) != 0);
+                                const unsigned done = av & ((ok ^ 1u) | leaf | stop | (unsigned)(blen == (unsigned)G));
+                                bcur = (unsigned)bnb + (fq & 0xFFu);
+                                bp = q;
+                                bisr = false;
+                                if (done) {
+                                    L.rec[bj].smask = bmask;
+                                    if (bws && (stop & term)) L.scf[bj] = 1;   // the word is one token
+                                }
+                                capm |= done & (((unsigned)bmask & 1u) ^ 1u);
+                                bact = bact && !done;
+                            }
+                        }
+                    }
+                }
+                unsigned pre[NG + 1];
+                pre[0] = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) pre[g + 1] = pre[g] + nstart[g];
+                const unsigned total = pre[NG];
+                auto start = [&](unsigned uu) {
+                    unsigned gs = 0;
+#pragma unroll
+                    for (int g = 1; g < NG; g++) gs += uu >= pre[g] ? 1u : 0u;
+                    unsigned base = 0;
+#pragma unroll
+                    for (int g = 0; g < NG; g++) base = (gs == (unsigned)g) ? pre[g] : base;
+                    unsigned jj = uu - base;
+                    if constexpr (G == 16 && !BIG)
+                        if ((a0mask >> gs) & 1u) jj = grp(gs).fin[jj].v;   // A0 slot: its marked list
+                    start_gj(gs, jj);
+                };
+                // Refills are batched: idle lanes take new starts only once A_REFILL of them are idle
+                // (or the remaining starts fit), so the refill code runs on a fraction of the steps.
+                bool active = false;
+                unsigned nxt = DPT_STOP == 21 ? total : 0u;   // diagnostic: A0 only
+                for (;;) {
+                    {
+                        const uint64_t im = ballot(!active);
+                        const unsigned nidle = (unsigned)__builtin_popcountll(im);
+                        if (nxt < total && (nidle >= (G == 64 ? A_REFILL64 : A_REFILL) || total - nxt <= nidle)) {
+                            if (!active) {
+                                const unsigned uu = nxt + __builtin_amdgcn_mbcnt_hi((unsigned)(im >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)im, 0u));
+                                if (uu < total) { active = true; start(uu); }
+                            }
+                            nxt += nidle;
+                        }
+                    }
+                    if (!ballot(active)) break;
+                    const int32_t t = t2 ? (int32_t)t2 : nb + (int32_t)(seq & 0xFFu);
+                    // (the 64-lane kernels' walks read the 8-byte slots -- no child filter: half the footprint
+                    // of a BLOOM-scale trie, one more failing lookup per walk)
+                    int4 ent;
+                    if constexpr (G == 64) {
+                        const int2 e2 = trie_slot(tv, t);
+                        ent = make_int4(e2.x, e2.y, 0, -1);
+                    } else {
+                        ent = trie_slotA(tv, t);   // buffer load: inactive lanes read harmlessly
+                    }
+                    // The step as selects (few exec-mask branches: their scalar bookkeeping costs issue
+                    // slots like the vector work does).  Root-table entry (t2): .y = node after two
+                    // bytes (0: none) | first byte exists << 30 | first byte ends a token << 31; .x =
+                    // that node's base word.  Plain step: the slot is the child iff its check is node.
+                    // (flags as 0/1 integers: && / || chains become exec-mask branches here)
+                    const unsigned act = active ? 1u : 0u;
+                    const unsigned isr = (unsigned)(t2 != 0);
+                    const unsigned y30 = ((unsigned)ent.y >> 30) & 1u, y31 = (unsigned)ent.y >> 31;
+                    const unsigned rsplit = act & isr & (split ? 1u : 0u);   // atom j ended after the first byte
+                    const unsigned rtok1 = rsplit & y30 & y31;
+                    const unsigned ok = act & (isr ? (y30 & (unsigned)((ent.y & 0x3FFFFFFF) != 0)) : (unsigned)(ent.y == node));
+                    len = rsplit ? 1u : len;
+                    mask = rtok1 ? (M)1 : mask;
+                    if constexpr (G == 16)
+                        if (rtok1) end_token(j + 1, 1);
+                    seq = isr ? seq : seq >> 8;
+                    cnt = isr ? cnt : cnt - 1u;
+                    t2 = 0;
+                    node = isr ? (ent.y & 0x3FFFFFFF) : t;   // read only while ok
+                    nb = ent.x & BASE_MASK;
+                    const unsigned leaf = ((unsigned)ent.x >> 30) & 1u;
+                    const unsigned aend = ok & (unsigned)(cnt == 0);   // atom j+len-1 ends: span j..j+len is a candidate
+                    len += aend;
+                    const unsigned term = aend & ((unsigned)ent.x >> 31);
+                    if constexpr (G == 16) {
+                        mask = (term & (unsigned)(len == 1)) ? (M)1 : mask;
+                        if (term) end_token(j + len, len);
+                    } else {
+                        mask |= term ? (M)1 << (len - 1) : (M)0;
+                    }
+                    const unsigned cont = aend & ((leaf | (unsigned)((info & AInfo<CH>::STOP) != 0) | (unsigned)(len == (unsigned)G)) ^ 1u);
+                    {
+                        // the next atom, read by every lane (j + len <= n_atoms: in the window's arrays)
+                        // (reading it a step ahead, before the trie load returns, measured slower: r03z)
+                        const GL &L = *reinterpret_cast<const GL *>(smem + lbase);
+                        unsigned cn = 0;
+                        const unsigned inf = ainfo_get(L, j + len, false);
+                        const uint64_t sq = atom_from_info<CH, WIDE>(L.bytes, inf, raw, cn);
+                        info = cont ? inf : info;
+                        seq = cont ? sq : seq;
+                        cnt = cont ? cn : cnt;
+                    }
+                    // the walk ends at a failed lookup, at a leaf or a walk-ending atom, or when the
+                    // node has no child for the next byte (over without that lookup)
+                    const unsigned nochild = (((unsigned)ent.w >> child_bit((unsigned)(seq & 0xFFu))) & 1u) ^ 1u;
+                    const unsigned done = act & ((ok ^ 1u) | (aend ? ((cont ^ 1u) | nochild) : (leaf | nochild)));
+                    if constexpr (G != 16) {
+                        if (done) {
+                            GL &L = *reinterpret_cast<GL *>(smem + lbase);
+                            L.rec[j].smask = mask;   // G = 16: end masks, set by end_token
+                        }
+                    }
+                    capm |= (done & (((unsigned)mask & 1u) ^ 1u)) << gsel;
+                    active = active && !done;
+                }
+                // the slots whose walk found an atom that is no token by itself
+#pragma unroll
+                for (int g = 0; g < NG; g++)
+                    if (ballot((capm >> g) & 1u) && lane == 0) SSr(g).capb = 1;
+            }
+            wave_sync();
+            STAMP(1);
+
+            // ---------------------------------------------------------- B: forward recurrence
+            KREFRESH();
+            bool lane_mode = false;   // B ran per chunk and did C0 and C1 itself (G = 16, capless, no edges)
+            if (DPT_RUN_B) {
+                GL &L = grp(mg);
+                const unsigned na = SSr(mg).n_atoms;
+                unsigned imax = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) imax = max(imax, uni(SSr(g).n_atoms));
+                // Steps past a slot's own n_atoms (up to the wave's imax <= CH) compute garbage that
+                // lands in fin[] entries nobody reads, so the loop body has no per-slot guard.
+                // Recording the edges (f1) and the uncapped DP (f2) are hoisted out as loop versions.
+                // CAPM 0: the reference's capped DP (cost[i] <= i, dp_tokenize.py:28); 1: uncapped with
+                // "inf" (inspect_tokenizer.py:77-86); 2: neither -- exact for both when every atom of
+                // the wave's windows is a token by itself (then cost[i] <= i - ws on a valid path, so
+                // the cap never wins and nothing is unreachable)
+                auto forward = [&](auto EDGES, auto CAPM) {
+                    constexpr bool edges = decltype(EDGES)::value;
+                    constexpr int capm = decltype(CAPM)::value;
+                    // st (lane d, candidate j = i-1-d) = (cost[j]+1) << 16 | invalid[j] << 15 | G[j]
+                    constexpr unsigned ST0 = 0x10000u;   // word start: cost 0, reachable, G 0
+                    unsigned ws = 0;
+                    unsigned st = d == 0 ? ST0 : 0u;
+                    unsigned cpj = 0;
+                    if constexpr (G == 16) {
+                        // Lane d carries x = rec[j] (its cpos) and its state in key form:
+                        // (cost[j]+1) << 16 | invalid[j] << 15 | (0x7FFF - G[j]), so the candidate key is
+                        // min(st, (st | 0x7FFF) - span); a dead span is one sign-extended bit of the
+                        // inverted end mask of i (read by every lane of the row).
+                        constexpr unsigned SK0 = 0x17FFFu;   // word start in key form
+                        const uint32_t *rec32 = reinterpret_cast<const uint32_t *>(L.rec);
+                        const unsigned sbit = 16u + d;
+                        unsigned sk = d == 0 ? SK0 : 0u;
+                        unsigned x = d == 0 ? rec32[0] : 0xFFFF0000u;
+                        unsigned wsh = 0;                    // word start << 16
+                        uint32_t nx = rec32[1];
+                        // one step; (sk, x) in, (sk', x') out -- called alternately on two register sets
+                        // so the DPP shifts need no copies
+                        auto step = [&](unsigned i, unsigned skI, unsigned xI, unsigned &skO, unsigned &xO) {
+                            const uint32_t cur = nx;
+                            nx = rec32[i + 1];                         // i+1 <= CH+1 < NA: always in bounds
+                            const unsigned span = (cur - xI) & 0x7FFFu;  // cp(j..i); borrows only move up
+                            unsigned kv = (skI | 0x7FFFu) - span;
+                            kv = skI < kv ? skI : kv;
+                            const unsigned key = kv | (unsigned)__builtin_amdgcn_sbfe((int)cur, sbit, 1);
+                            unsigned r = row_min_u32(key);
+                            if constexpr (capm == 0) {
+                                const unsigned capkey = ((i << 16) | 0xFFFFu) - wsh;
+                                r = r < capkey ? r : capkey;
+                            }
+                            const uint64_t gmb = ballot(key == r);
+                            const uint64_t emb = ballot((key ^ r) < 0x8000u);
+                            if (d == 0) {
+                                const unsigned sh = 16u * mg;
+                                const unsigned gs = (unsigned)(gmb >> sh), es = (unsigned)(emb >> sh);
+                                // lowest set bit of the row; bits of other rows only land in fields
+                                // of positions C1 never reads (see Group<16>)
+                                const unsigned dg = ffbl(gs), de = ffbl(es);
+                                L.fin[i].v = (uint8_t)(dg | (de << 4));
+                                L.rec[i].smask = Wfin<G>::pack(r);   // rec[i] was consumed at step i-1
+                                if constexpr (edges)
+                                    if (i <= na) a.edges[SSr(mg).sb + SSr(mg).abase + i - 1] = es & 0xFFFFu;
+                            }
+                            const bool wend = (int16_t)cur < 0;     // CP_WS: word starts and the window end
+                            wsh = wend ? (i << 16) : wsh;
+                            unsigned nxt = r + 0x10000u;
+                            if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;   // unreachable: cost stays inf
+                            skO = row_shift_in(skI, wend ? SK0 : nxt);
+                            xO = row_shift_in(xI, cur);
+                        };
+                        unsigned sk2, x2;
+                        unsigned i = 1;
+                        for (; i + 1 <= imax; i += 2) {
+                            step(i, sk, x, sk2, x2);
+                            step(i + 1, sk2, x2, sk, x);
+                        }
+                        if (i <= imax) step(i, sk, x, sk2, x2);
+                    } else {
+                        const uint64_t m0 = na > 0 ? L.rec[0].smask : 0ull;
+                        unsigned mlo = d == 0 ? (unsigned)m0 : 0u, mhi = d == 0 ? (unsigned)(m0 >> 32) : 0u;
+                        for (unsigned i = 1; i <= imax; i++) {
+                            const unsigned cur = L.rec[i].cpos;
+                            const uint64_t mi = L.rec[i].smask;
+                            const unsigned cpi = cur & 0x7FFFu;
+                            const unsigned span = cpi - cpj;
+                            const unsigned gj = st & 0x7FFFu;
+                            const unsigned kv = (st | 0x7FFFu) - (gj > span ? gj : span);
+                            const unsigned bit = (d < 32 ? (mlo >> d) : (mhi >> (d - 32))) & 1u;
+                            const unsigned key = bit ? kv : 0xFFFFFFFFu;
+                            unsigned r = wave_min_u32(key);
+                            if constexpr (capm == 0) {
+                                const unsigned capkey = ((i - ws) << 16) | 0xFFFFu;
+                                r = r < capkey ? r : capkey;
+                            }
+                            const uint64_t gmb = ballot(key == r);
+                            const uint64_t emb = ballot((key ^ r) < 0x8000u);
+                            if (lane == 0) {
+                                const unsigned dg = gmb ? (unsigned)__builtin_ctzll(gmb) : 64u;
+                                const unsigned de = emb ? (unsigned)__builtin_ctzll(emb) : 64u;
+                                L.fin[i].d = dg | (de << 8);
+                                L.fin[i].w = Wfin<G>::pack(r);
+                                if constexpr (edges)
+                                    if (i <= na) a.edges[SSr(0).sb + SSr(0).abase + i - 1] = emb;
+                            }
+                            const bool wend = (cur & CP_WS) != 0;
+                            ws = wend ? i : ws;
+                            unsigned nxt = (r ^ 0x7FFFu) + 0x10000u;
+                            if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;
+                            const unsigned sin = wend ? ST0 : nxt;
+                            st = wave_shift_in(st, sin);
+                            cpj = wave_shift_in(cpj, cpi);
+                            mlo = wave_shift_in(mlo, (unsigned)mi);
+                            mhi = wave_shift_in(mhi, (unsigned)(mi >> 32));
+                        }
+                    }
+                };
+                // Capless windows without edge recording (the common case, G = 16): lanes take
+                // chunks of end positions cut at "cut points" -- boundaries no token span crosses,
+                // through which every tokenization of the word passes -- and run the recurrence
+                // sequentially over their own chunk, one position per iteration for 64 lanes.
+                // A chunk that starts inside a word starts from a local state (cost 0, G 0); a row
+                // scan of the chunks' transfers gives each chunk its incoming state, and a fix-up
+                // corrects the two things that depend on it: the final key of the word that ends
+                // first in the chunk (cost offset, max with the incoming G) and dg at the positions
+                // before that word end (dg = de wherever the incoming G already attains G[i]:
+                // every j in E(i) then ties on max(G[j], cp(span))).  de and E(i) are local.  The first
+                // is one store; the second is a test in the C1 walk, at the ends it visits.
+                auto forward_lanes = [&]() {
+                  if constexpr (G == 16) {
+                    // LW lanes share a window: a 16-lane row per slot, or (the one-string kernel, SOLO) the whole
+                    // wave on slot 0 -- chunks of <= 5 boundaries instead of 17, so the dependent LDS steps of the
+                    // recurrence and of the C1 walks are a quarter as many (the per-call floor)
+                    constexpr int LW = SOLO ? 64 : 16;
+                    constexpr unsigned CMAX = ((unsigned)(CH + LW - 1) / (unsigned)LW) | 1u;   // boundaries per lane, at most
+                    const unsigned mg = SOLO ? 0u : lane / 16u;
+                    const unsigned d = SOLO ? lane : lane % 16u;
+                    GL &L = grp(mg);
+                    const unsigned na = SSr(mg).n_atoms;
+                    uint32_t *rec32 = reinterpret_cast<uint32_t *>(L.rec);
+                    constexpr unsigned FRESH = 31u;   // key16 of a fresh start: cost 0, reachable, G 0
+                    // key16 = cost << 6 | invalid << 5 | 31 - G (the Wfin<16> form)
+                    auto relax = [](unsigned sj, unsigned span) {   // cost + 1, G = max(G, cp(span)); span <= 16
+                        const unsigned a1 = sj + 64u;
+                        const unsigned a2 = (a1 | 31u) - span;
+                        return a1 < a2 ? a1 : a2;
+                    };
+                    // ---- cut points: boundary p is one iff min_{i > p} lo_i >= p, lo_i = the first atom
+                    //      of the longest token ending at i (i-1 - highest bit of its end mask)
+                    // boundaries per lane (na <= 256), odd: lanes stepping through their chunks together
+                    // then hit distinct LDS banks (ds_read_b32: 32 banks per 32-lane group; a stride of
+                    // 16 dwords put 8 lanes on a bank)
+                    const unsigned C = ((na + (unsigned)LW - 1u) / (unsigned)LW) | 1u;   // <= CMAX
+                    const unsigned c0 = min(d * C, na), c1 = min(c0 + C, na);
+                    // one backward pass over the chunk's ends (c0, c1]: the local suffix min of lo
+                    // decides the cuts as far as this chunk's ends go; the later chunks' ends (min S)
+                    // then only cap them: p is a cut iff both mins are >= p, i.e. p <= S
+                    // (the 512-byte pass's chunks have up to 33 boundaries: a 64-bit cut mask there)
+                    using CutM = std::conditional_t<(CMAX > 32u), uint64_t, uint32_t>;
+                    unsigned mloc = 0xFFFFu;
+                    CutM lcut = 0;
+#pragma unroll 4
+                    for (int k = (int)CMAX - 1; k >= 0; k--) {
+                        const unsigned i = c0 + 1u + (unsigned)k;
+                        if (i <= c1) {
+                            const unsigned hb = 31u - (unsigned)__builtin_clz((~rec32[i] >> 16) | 1u);   // bit 0 is set in a capless window
+                            mloc = min(mloc, i - 1u - hb);
+                            if (mloc >= i - 1u) lcut |= (CutM)1 << k;   // boundary p = i-1 = c0+k < c1
+                        }
+                    }
+                    // min lo over the later lanes of the group (shift left: lane l reads lane l+k)
+                    unsigned sm = mloc;
+                    sm = min(sm, gshl<LW, 1>(sm, 0xFFFFu));
+                    sm = min(sm, gshl<LW, 2>(sm, 0xFFFFu));
+                    sm = min(sm, gshl<LW, 4>(sm, 0xFFFFu));
+                    sm = min(sm, gshl<LW, 8>(sm, 0xFFFFu));
+                    if constexpr (LW == 64) {
+                        sm = min(sm, gshl<LW, 16>(sm, 0xFFFFu));
+                        sm = min(sm, gshl<LW, 32>(sm, 0xFFFFu));
+                    }
+                    const unsigned S = gshl<LW, 1>(sm, 0xFFFFu);
+                    // boundaries c0 + k <= S
+                    const CutM cut = S < c0 ? (CutM)0 : (S - c0 >= CMAX - 1u ? lcut : lcut & (((CutM)2 << (S - c0)) - 1u));
+                    // rs = the first cut at or after c0 (in this lane's chunk or a later one; na is a cut)
+                    unsigned rs = na;
+                    if constexpr (CMAX > 32u) rs = cut ? c0 + (unsigned)__builtin_ctzll(cut) : na;
+                    else rs = cut ? c0 + ffbl(cut) : na;
+                    rs = min(rs, gshl<LW, 1>(rs, na));
+                    rs = min(rs, gshl<LW, 2>(rs, na));
+                    rs = min(rs, gshl<LW, 4>(rs, na));
+                    rs = min(rs, gshl<LW, 8>(rs, na));
+                    if constexpr (LW == 64) {
+                        rs = min(rs, gshl<LW, 16>(rs, na));
+                        rs = min(rs, gshl<LW, 32>(rs, na));
+                    }
+                    if constexpr (NEAR_CUT) {
+                        // the NEAREST cut to c0 instead of the first one after it: snapping up made the longest
+                        // chunk of a wave ~2x the mean on cfg4's long words (a 256-atom window: 36.7 ends
+                        // against C = 17), and the wave steps as long as its longest chunk; nearest-cut
+                        // rounding is monotone in c0, so the chunks still tile (0, na]
+                        unsigned lastc = 0;   // (0 is a cut)
+                        if constexpr (CMAX > 32u) lastc = cut ? c0 + (63u - (unsigned)__builtin_clzll(cut)) : 0u;
+                        else lastc = cut ? c0 + (31u - (unsigned)__builtin_clz((unsigned)cut)) : 0u;
+                        unsigned pm = lastc;   // max over the lanes <= d of the group, then shifted: lanes < d
+                        pm = max(pm, gshr<LW, 1>(pm, 0u));
+                        pm = max(pm, gshr<LW, 2>(pm, 0u));
+                        pm = max(pm, gshr<LW, 4>(pm, 0u));
+                        pm = max(pm, gshr<LW, 8>(pm, 0u));
+                        if constexpr (LW == 64) {
+                            pm = max(pm, gshr<LW, 16>(pm, 0u));
+                            pm = max(pm, gshr<LW, 32>(pm, 0u));
+                        }
+                        const unsigned prevc = gshr<LW, 1>(pm, 0u);
+                        rs = (c0 - prevc < rs - c0) ? prevc : rs;
+                    }
+                    const unsigned re = gshl<LW, 1>(rs, na);
+                    if (DPT_STOP == 25) return;   // diagnostic: cut points only
+
+                    // ---- the recurrence over ends (rs, re], one position per iteration
+                    unsigned i = rs, ws = rs, sprev = FRESH, pe = 0;
+                    unsigned cprev = rec32[rs] & 0x7FFu;
+                    unsigned nxt = rec32[rs + 1u];   // rs + 1 <= na + 1 < NA
+                    unsigned T = 0;                  // tokens of the chunk: the pieces' costs
+                    // (reading the next position's first candidates a step ahead, or two candidates per inner
+                    // iteration, measured slower: r03y, r03)
+                    while (ballot(i < re)) {
+                        if (i < re) {
+                            i++;
+                            const unsigned r = nxt;
+                            nxt = rec32[i + 1u];
+                            const unsigned cpi = r & 0x7FFu;             // bits 11..14: see below
+                            unsigned best = relax(sprev, cpi - cprev);   // j = i-1: the single atom
+                            unsigned dg = 0, de = 0;
+                            unsigned m = (~r >> 17) & 0x7FFFu;          // longer tokens ending at i: bit d-1
+                            while (m) {
+                                const unsigned dd = ffbl(m) + 1u;
+                                m &= m - 1u;
+                                const unsigned j = i - 1u - dd;          // j >= ws: spans cross no cut
+                                const unsigned rj = rec32[j];
+                                const unsigned sj = j == ws ? FRESH : (rj >> 16);
+                                const unsigned kk = relax(sj, cpi - (rj & 0x7FFu));
+                                // ascending d = descending j: the first strict improvement is the largest j
+                                if ((kk >> 5) < (best >> 5)) de = dd;
+                                if (kk < best) dg = dd;
+                                best = kk < best ? kk : best;
+                            }
+                            // One dword: the key in the mask half (this end's mask was read above), and the
+                            // local G(i) - 1 (G is 1..16 past rs in a capless window) in bits 11..14 of the
+                            // cpos half (code-point prefixes are < 2048 in a window; every reader of a cpos
+                            // in lane mode masks them off).  C1 finds it there -- the mask halves take the
+                            // walks' tokens: at a word end it is the word's L* - 1 (the longest token to
+                            // select), elsewhere what the walk's dg/de rule compares the incoming G with.
+                            rec32[i] = (best << 16) | (r & 0x87FFu) | ((30u - (best & 31u)) << 11);
+                            L.fin[i].v = (uint8_t)(dg | (de << 4));
+                            const bool wend = (r & CP_WS) != 0;
+                            if (wend) {
+                                T += best >> 6;
+                                if (!pe) pe = i;
+                            }
+                            ws = wend ? i : ws;
+                            sprev = wend ? FRESH : best;
+                            cprev = cpi;
+                        }
+                    }
+                    if (DPT_STOP == 26) return;   // diagnostic: + the recurrence
+                    // P1 = the piece walked first in C1 (the one ending at re); p1in: no word start in
+                    // (rs, re), so P1 is the chunk's first piece too and starts from the incoming state
+                    const bool re_ws = i > rs && sprev == FRESH;   // re is a word start (its word ended)
+                    const bool p1in = pe == 0 || pe == re;
+                    if (!re_ws) T += sprev >> 6;
+                    unsigned gl1 = 31u - ((re_ws ? L.rec[re].smask : sprev) & 31u);   // local G of P1 at re
+                    // ---- row scan of the chunk transfers: (reset, value) -- a chunk with a word start
+                    //      ignores its input; otherwise out = in (+) local, (+) = costs add, G max
+                    unsigned x = (pe ? 0x10000u : 0u) | sprev;
+                    auto compose = [&](unsigned y) {   // y (the earlier lanes) then x
+                        const unsigned comb = (y & 0xFFC0u) + (x & 0xFFC0u) + min(y & 31u, x & 31u);
+                        x = (x >> 16) ? x : ((y & 0x10000u) | comb);
+                    };
+                    compose(gshr<LW, 1>(x, FRESH));
+                    compose(gshr<LW, 2>(x, FRESH));
+                    compose(gshr<LW, 4>(x, FRESH));
+                    compose(gshr<LW, 8>(x, FRESH));
+                    if constexpr (LW == 64) {
+                        compose(gshr<LW, 16>(x, FRESH));
+                        compose(gshr<LW, 32>(x, FRESH));
+                    }
+                    const unsigned in = gshr<LW, 1>(x, FRESH) & 0xFFFFu;
+                    const unsigned gin = 31u - (in & 31u);   // G at rs
+                    // The incoming state changes two things.  The final key of the word that ends first in
+                    // the chunk: composed here, and its L* := gin where gin > G(pe).  And dg at the ends q in
+                    // (rs, lim], lim = that word end (re without one): dg = de where gin >= the local G(q).
+                    // Only the ends the C1 walk visits need that, so the walk applies it (fgm below) from the
+                    // G(q) - 1 the recurrence left in rec[q]; at pe the bits then hold max(gin, G(pe)) - 1,
+                    // which gin - 1 reaches exactly when gin >= the local G(pe).
+                    if (gin && pe) {
+                        const unsigned kl = L.rec[pe].smask;
+                        L.rec[pe].smask = (uint16_t)((in & 0xFFC0u) + (kl & 0xFFC0u) + min(in & 31u, kl & 31u));
+                        if (gin > 31u - (kl & 31u)) L.rec[pe].cpos = (uint16_t)((L.rec[pe].cpos & 0x87FFu) | ((gin - 1u) << 11));
+                    }
+                    const unsigned flim = gin ? (pe ? pe : re) : 0u;   // no incoming G: no end is <= 0
+                    const unsigned fgm = gin - 1u;                      // (read only where flim != 0)
+                    const unsigned gre = p1in ? max(gin, gl1) : gl1;   // G at re of P1's word (its L* if re_ws)
+                    if (DPT_STOP == 27) return;   // diagnostic: + the transfer scan and fix-up
+
+                    // ---- C1 (replaces C0 + C1 for the wave): the selection walks, one chunk per lane.
+                    // Every tokenization passes through the cuts, so a chunk's tokens are the ones its
+                    // own walk from re down to rs emits; their count T is fixed (the pieces' costs).
+                    // The walk rule is C1's (dg while the longest token so far A is below the word's
+                    // L*, de after).  What a chunk needs from the right: P1's L* (a copy scan from
+                    // the chunk holding its word end) and whether A has reached L* on entry.  Left of
+                    // q (the first cut where G reaches L*: gre < L*) it has -- the L* token lies in the
+                    // segment ending at q; right of q, dg == de everywhere (every j in E(i) is at or
+                    // after q, so G[j] == L*), so it does not matter; in q's chunk it has iff a chunk
+                    // to the right selected an L* token by chance -- the flag scan after the walks,
+                    // and that chunk re-walks P1 in de mode.
+                    // token base: exclusive prefix sum of T over the row; the window's count to wtok
+                    unsigned tb = T;
+                    tb += gshr<LW, 1>(tb, 0u);
+                    tb += gshr<LW, 2>(tb, 0u);
+                    tb += gshr<LW, 4>(tb, 0u);
+                    tb += gshr<LW, 8>(tb, 0u);
+                    if constexpr (LW == 64) {
+                        tb += gshr<LW, 16>(tb, 0u);
+                        tb += gshr<LW, 32>(tb, 0u);
+                    }
+                    if (d == (unsigned)LW - 1u) SSr(mg).wtok = tb;
+                    tb -= T;
+                    // P1's L*: from rec[re] when its word ends at re, else from the right (the first
+                    // word end of the next chunk that has one)
+                    unsigned lsr = pe ? (0x10000u | (((unsigned)L.rec[pe].cpos >> 11) & 15u)) : 0u;
+                    auto copy_r = [&](unsigned y) { lsr = (lsr >> 16) ? lsr : y; };
+                    copy_r(gshl<LW, 1>(lsr, 0u));
+                    copy_r(gshl<LW, 2>(lsr, 0u));
+                    copy_r(gshl<LW, 4>(lsr, 0u));
+                    copy_r(gshl<LW, 8>(lsr, 0u));
+                    if constexpr (LW == 64) {
+                        copy_r(gshl<LW, 16>(lsr, 0u));
+                        copy_r(gshl<LW, 32>(lsr, 0u));
+                    }
+                    // (DPP reads outside any branch: a lane masked off in EXEC reads as 0)
+                    const unsigned lsn = gshl<LW, 1>(lsr, 0u);
+                    const unsigned ls1 = re_ws ? gre : (lsn & 15u) + 1u;
+                    const bool walk = !len_only && SSr(mg).status == 0;   // per row (not uniform)
+                    const bool left_of_q = gre < ls1;
+                    unsigned n1 = 0;   // tokens of P1
+                    unsigned afin = 0, lsm = ls1;   // after the walk: A and L* of the last piece
+                    {
+                        unsigned ii = re, k = walk ? tb + T : tb, A = left_of_q ? ls1 : 0u, Ls = ls1;
+                        unsigned pend = rec32[re] & 0x7FFu;
+                        bool inp1 = true;
+                        while (ballot(k > tb)) {
+                            if (k > tb) {
+                                const unsigned rr = rec32[ii];
+                                const unsigned cpi = rr & 0x7FFu;
+                                if (ii < re && (rr & CP_WS)) {   // into the word ending at ii
+                                    Ls = ((rr >> 11) & 15u) + 1u;
+                                    A = 0;
+                                    pend = cpi;
+                                    inp1 = false;
+                                }
+                                n1 += inp1 ? 1u : 0u;
+                                const unsigned f = L.fin[ii].v;
+                                const unsigned sp = pend - cpi;
+                                A = A > sp ? A : sp;
+                                // de once A has reached L*, and where the incoming G attains the local G(ii)
+                                // (every j in E(ii) then ties on G: the chunk-start rule, see flim)
+                                const bool tie = (ii <= flim) & (((rr >> 11) & 15u) <= fgm);
+                                const unsigned dd = ((A >= Ls) | tie) ? (f >> 4) : (f & 15u);
+                                const unsigned j = ii - 1u - dd;
+                                k--;
+                                L.rec[k].smask = (uint16_t)j;   // k < rs or a position this walk has left
+                                pend = cpi;
+                                ii = j;
+                            }
+                        }
+                        const unsigned sp = pend - (rec32[rs] & 0x7FFu);
+                        afin = A > sp ? A : sp;
+                        lsm = Ls;
+                    }
+                    // flag scan, right to left: the chunk's last piece reached its L* (sel); a chunk
+                    // whose last piece is P1 also passes on what came in; none crosses a word start
+                    unsigned fl = ((T > 0 && afin >= lsm) ? 1u : 0u) | ((!p1in || re_ws) ? 2u : 0u);
+                    auto flag_r = [&](unsigned y) { fl = (fl & 2u) ? fl : (fl | (y & 3u)); };
+                    flag_r(gshl<LW, 1>(fl, 0u));
+                    flag_r(gshl<LW, 2>(fl, 0u));
+                    flag_r(gshl<LW, 4>(fl, 0u));
+                    flag_r(gshl<LW, 8>(fl, 0u));
+                    if constexpr (LW == 64) {
+                        flag_r(gshl<LW, 16>(fl, 0u));
+                        flag_r(gshl<LW, 32>(fl, 0u));
+                    }
+                    const unsigned fln = gshl<LW, 1>(fl, 0u);
+                    const bool fin_in = !re_ws && (fln & 1u) != 0;
+                    // q's chunk with a chance L* token to the right: P1 again in de mode (A = L*);
+                    // P1 starts below L* only from rs with gin < L* or from a word start inside
+                    if (walk && fin_in && !left_of_q && (!p1in || gin < ls1)) {
+                        unsigned ii = re, k = tb + T;
+                        for (unsigned c = 0; c < n1; c++) {
+                            const unsigned j = ii - 1u - (unsigned)(L.fin[ii].v >> 4);
+                            k--;
+                            L.rec[k].smask = (uint16_t)j;
+                            ii = j;
+                        }
+                    }
+                  }
+                };
+                // Capless windows of the 256-byte 64-lane kernel without edge recording (one string per
+                // wave: BLOOM-scale byte-level vocabularies).  The row recurrence is one wave-min per atom,
+                // a dependent chain over the whole window (55 % of that kernel, profiles/r03_phase_diag.txt).
+                // Here each lane takes a chunk of end positions cut at cut points, as forward_lanes does,
+                // and relaxes forward ("push") from every start j of its chunk over j's span mask (phase
+                // A's start masks, rec[j].smask): the token j..i updates i's entry {dg | de << 8 | cp(i)
+                // << 16, key} in fin[].  Starts are taken in ascending order, so "<=" keeps the largest j
+                // of a tie -- the row recurrence's lowest lane (dp_tokenize.py:40-46).  A wave scan of the
+                // chunk transfers and the chunk-start fix-up follow (here a loop over fin[]; forward_lanes
+                // applies it in its own walk); C0/C1 then run as in row mode (they read fin[] only).
+                auto forward_lanes64 = [&]() {
+                  if constexpr (G == 64 && !BIG) {
+                    if (na == 0) return;
+                    constexpr unsigned FRESH = 0x7FFFu;       // key of a fresh start: cost 0, reachable, G 0
+                    constexpr unsigned RESET = 0x80000000u;   // transfer flag: a word ends in the chunk
+                    uint2 *fin2 = reinterpret_cast<uint2 *>(L.fin);
+                    // ---- cut points (bit p of cm[p / 64]): p is one iff max_{j < p} (j + 1 + hb(smask_j))
+                    //      <= p -- no token crosses it; 0 and na always are
+                    uint64_t cm[(CH + 64) / 64];
+                    unsigned carry = 0;
+#pragma unroll
+                    for (int r = 0; r < (CH + 64) / 64; r++) {
+                        const unsigned p = 64u * (unsigned)r + lane;
+                        // the end of the longest token from p: p + 1 + (63 - clz)
+                        const unsigned v = p < na ? p + 64u - (unsigned)__builtin_clzll(L.rec[p].smask | 1ull) : 0u;
+                        const unsigned inc = wave_incl_scan_max(v);
+                        const unsigned ex = max(carry, wave_shift_in(inc, 0u));
+                        carry = max(carry, __builtin_amdgcn_readlane(inc, 63));
+                        cm[r] = ballot(p <= na && ex <= p);
+                    }
+                    // the first cut at or after c (<= na)
+                    auto nextcut = [&](unsigned c) -> unsigned {
+                        unsigned res = na;
+#pragma unroll
+                        for (int r = (CH + 64) / 64 - 1; r >= 0; r--) {
+                            const unsigned lo = 64u * (unsigned)r;
+                            const uint64_t keep = c <= lo ? ~0ull : (c >= lo + 64u ? 0ull : (~0ull << (c - lo)));
+                            const uint64_t m = cm[r] & keep;
+                            res = m ? lo + (unsigned)__builtin_ctzll(m) : res;
+                        }
+                        return res;
+                    };
+                    // the last cut at or before c (0 is a cut)
+                    auto prevcut = [&](unsigned c) -> unsigned {
+                        unsigned res = 0;
+#pragma unroll
+                        for (int r = 0; r < (CH + 64) / 64; r++) {
+                            const unsigned lo = 64u * (unsigned)r;
+                            const uint64_t keep = c < lo ? 0ull : (c >= lo + 63u ? ~0ull : (~0ull >> (63u - (c - lo))));
+                            const uint64_t m = cm[r] & keep;
+                            res = m ? lo + 63u - (unsigned)__builtin_clzll(m) : res;
+                        }
+                        return res;
+                    };
+                    // chunk bounds snapped to the NEAREST cut (as forward_lanes, DPT_NEAR_CUT): monotone in c, so
+                    // lane l's end is lane l+1's start
+                    auto snap = [&](unsigned c) -> unsigned {
+                        const unsigned nx = nextcut(c);
+                        if constexpr (!NEAR_CUT64) return nx;
+                        const unsigned pv = prevcut(c);
+                        return (c - pv < nx - c) ? pv : nx;
+                    };
+                    const unsigned C = (na + 63u) >> 6;   // (odd chunk lengths: -0.5 %, r03ad)
+                    const unsigned c0 = min(lane * C, na), c1 = min(c0 + C, na);
+                    const unsigned rs = snap(c0);
+                    // (c1 = the next lane's c0: its start, by wave_shl:1; lane 63 ends at na)
+                    const unsigned re = (unsigned)__builtin_amdgcn_update_dpp((int)na, (int)rs, 0x130, 0xF, 0xF, false);
+                    (void)c1;
+                    if (DPT_STOP == 25) return;   // diagnostic: cut points only
+                    // ---- the chunk's entries: no candidate yet, cp(i) in the high half; pe = its first word end
+                    unsigned pe = 0;
+                    for (unsigned i = rs + 1u; i <= re; i++) {
+                        const unsigned cp = L.rec[i].cpos;
+                        fin2[i] = make_uint2((cp & 0x7FFFu) << 16, 0xFFFFFFFFu);
+                        pe = (!pe && (cp & CP_WS)) ? i : pe;
+                    }
+                    // ---- push: j ascending; j's key is final once every earlier start of the chunk ran --
+                    //      it is the j-1 -> j edge's result (bit 0: capless windows have it at every start),
+                    //      carried in a register.  One edge at a time: batches of 2 / 4 edges with their reads
+                    //      in flight (r03x) and giving long chunks to the whole wave as a row recurrence (r03ae)
+                    //      measured slower -- the push is throughput-bound across the resident waves.
+                    unsigned kcarry = FRESH;
+                    for (unsigned j = rs; j < re; j++) {
+                        const uint64_t sm = L.rec[j].smask;
+                        const unsigned cj = L.rec[j].cpos;
+                        const unsigned kj = (j == rs || (cj & CP_WS)) ? FRESH : kcarry;
+                        const unsigned a1 = kj + 0x10000u;             // cost + 1
+                        const unsigned a1g = (a1 | 0x7FFFu) + (cj & 0x7FFFu);
+                        auto upd = [&](uint2 &f, unsigned dd) {
+                            const unsigned a2 = a1g - (f.x >> 16);       // G = max(G[j], cp(j..i))
+                            const unsigned kk = a1 < a2 ? a1 : a2;
+                            f.x = ((kk >> 15) <= (f.y >> 15)) ? ((f.x & ~0x7F00u) | (dd << 8)) : f.x;   // de
+                            f.x = (kk <= f.y) ? ((f.x & ~0x7Fu) | dd) : f.x;                            // dg
+                            f.y = kk < f.y ? kk : f.y;
+                        };
+                        if (!raw && L.scf[j]) {
+                            // a word that is one token (phase A's whole-word shortcut): only that edge, whose key
+                            // (cost 1) is final at the word end; its inner positions are never read (C0/C1 read
+                            // word ends, C1 walks from them; no cut lies inside the word).  Sound only because
+                            // (1) every window ends at a word start or the string's end (window_bounds), so the
+                            // BF_STOP the byte-stream walker stopped on is the word's real end, not a window cut
+                            // through it, and (2) that walker never steps past a BF_STOP; a change to either
+                            // must revisit this (tests/test_gpu_parity.py::test_bloom_words_across_windows)
+                            const unsigned dd = 63u - (unsigned)__builtin_clzll(sm);   // the longest token from j
+                            uint2 f = fin2[j + 1u + dd];
+                            upd(f, dd);
+                            fin2[j + 1u + dd] = f;
+                            kcarry = f.y;
+                            j += dd;
+                            continue;
+                        }
+                        {   // the j -> j+1 edge (bit 0): j+1's final key
+                            uint2 f = fin2[j + 1u];
+                            upd(f, 0u);
+                            fin2[j + 1u] = f;
+                            kcarry = f.y;
+                        }
+                        // the span mask as two 32-bit halves: one v_ffbl and 32-bit arithmetic per edge
+                        // (BLOOM 21.5 -> 22.1 GB/s against the 64-bit walk, r04l)
+#pragma unroll
+                        for (int hh = 0; hh < 2; hh++) {
+                            uint32_t m32 = hh == 0 ? ((uint32_t)sm & ~1u) : (uint32_t)(sm >> 32);
+                            while (m32) {
+                                const unsigned dd = ffbl(m32) + 32u * (unsigned)hh;
+                                m32 &= m32 - 1u;
+                                uint2 f = fin2[j + 1u + dd];   // <= re: no token crosses a cut
+                                upd(f, dd);
+                                fin2[j + 1u + dd] = f;
+                            }
+                        }
+                    }
+                    if (DPT_STOP == 26) return;   // diagnostic: + the recurrence
+                    // ---- wave scan of the chunk transfers (forward_lanes' compose, 64 lanes, keys)
+                    const bool re_wb = (L.rec[re].cpos & CP_WS) != 0;
+                    unsigned x = rs == re ? FRESH : ((pe ? RESET : 0u) | (re_wb ? FRESH : fin2[re].y));
+                    auto compose = [&](unsigned y) {   // y (the earlier lanes) then x
+                        const unsigned comb = ((y & 0x7FFF0000u) + (x & 0x7FFF0000u)) | min(y & 0x7FFFu, x & 0x7FFFu);
+                        x = (x & RESET) ? x : ((y & RESET) | comb);
+                    };
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x111, 0xF, 0xF, false));   // row_shr:1
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x112, 0xF, 0xF, false));   // row_shr:2
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x114, 0xF, 0xF, false));   // row_shr:4
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x118, 0xF, 0xF, false));   // row_shr:8
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x142, 0xA, 0xF, false));   // row_bcast:15
+                    compose((unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x143, 0xC, 0xF, false));   // row_bcast:31
+                    const unsigned in = (unsigned)__builtin_amdgcn_update_dpp((int)FRESH, (int)x, 0x138, 0xF, 0xF, false) & ~RESET;   // wave_shr:1
+                    const unsigned gin = 0x7FFFu - (in & 0x7FFFu);   // G at rs (0: a word starts there, cost 0)
+                    if (gin) {
+                        // before the first word end: dg = de wherever the incoming G attains G[q];
+                        // the first word end's key = in (+) local
+                        const unsigned lim = pe ? pe : re;
+                        for (unsigned q = rs + 1u; q <= lim; q++) {
+                            const uint2 f = fin2[q];
+                            if (gin >= 0x7FFFu - (f.y & 0x7FFFu)) fin2[q].x = (f.x & ~0x7Fu) | ((f.x >> 8) & 0x7Fu);
+                        }
+                        if (pe) {
+                            const unsigned kl = fin2[pe].y;
+                            fin2[pe].y = ((in & 0x7FFF0000u) + (kl & 0x7FFF0000u)) | min(in & 0x7FFFu, kl & 0x7FFFu);
+                        }
+                    }
+                  }
+                };
+                using T_ = std::true_type;
+                using F_ = std::false_type;
+                using C0_ = std::integral_constant<int, 0>;
+                using C1_ = std::integral_constant<int, 1>;
+                using C2_ = std::integral_constant<int, 2>;
+                unsigned capb = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) capb |= uni(SSr(g).capb);
+                if (!PLAIN && a.edges) {
+                    if (!capb) forward(T_{}, C2_{}); else if (uncapped) forward(T_{}, C1_{}); else forward(T_{}, C0_{});
+                } else {
+                    if (!capb) {
+                        if constexpr (G == 16) {
+                            forward_lanes();
+                            lane_mode = true;
+                        } else if constexpr (!BIG) {
+                            forward_lanes64();
+                            lane_mode = DPT_STOP >= 25 && DPT_STOP <= 27;   // stop builds: no C0/C1 over unfinished fin[]
+                        } else {
+                            forward(F_{}, C2_{});
+                        }
+                    } else if (uncapped) forward(F_{}, C1_{}); else forward(F_{}, C0_{});
+                }
+            }
+            wave_sync();
+            STAMP(2);
+
+            // ---------------------------------------------------------- C0: per-window token counts and validity
+            KREFRESH();
+            // (word w ends at atom word_end(w); its final state is in fin[word_end(w)])
+            if (DPT_RUN_B && !lane_mode) phase_c0(kp, bid, lane);
+            wave_sync();
+
+            // ---------------------------------------------------------- C1: selection, one lane per word
+            KREFRESH();
+            if (DPT_RUN_B && !lane_mode) {
+                unsigned pre[NG + 1], tokpre[NG + 1], inv_g[NG];
+                pre[0] = 0; tokpre[0] = 0;
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    const unsigned nwg = uni(SSr(g).n_atoms) > 0 ? uni(SSr(g).n_words) : 0u;
+                    inv_g[g] = uni(SSr(g).inval) | (uni(SSr(g).status) != 0 ? 1u : 0u);
+                    pre[g + 1] = pre[g] + nwg;
+                    tokpre[g + 1] = tokpre[g] + (nwg ? uni(SSr(g).wtok) : 0u);
+                }
+                const unsigned total = pre[NG];
+                unsigned carry = 0;
+                for (unsigned u0 = 0; u0 < total; u0 += 64) {
+                    const unsigned u = u0 + lane;
+                    const bool in = u < total;
+                    unsigned g = 0;
+#pragma unroll
+                    for (int k = 1; k < NG; k++) g += u >= pre[k] ? 1u : 0u;
+                    unsigned wbase = 0, tbase = 0, ginv = 0;
+#pragma unroll
+                    for (int k = 0; k < NG; k++)
+                        if (g == (unsigned)k) { wbase = pre[k]; tbase = tokpre[k]; ginv = inv_g[k]; }
+                    GL &L = grp(g);
+                    const unsigned w = u - wbase;
+                    const typename Wfin<G>::T F = in ? L.wkey(L.word_end(wsl_of(kp, bid, g), w)) : (typename Wfin<G>::T)0;
+                    const unsigned cost = in ? Wfin<G>::cost(F) : 0u;
+                    const unsigned incl = wave_incl_scan_add(cost);
+                    const unsigned tok_base = carry + incl - cost - tbase;
+                    carry += __builtin_amdgcn_readlane(incl, 63);
+                    if (in && !ginv && !len_only) {
+                        // a valid word's walk emits exactly `cost` tokens and ends at its first atom
+                        // (Appendix A), so the token count bounds the loop
+                        unsigned i = L.word_end(wsl_of(kp, bid, g), w);
+                        const unsigned Ls = Wfin<G>::gmax(F);   // G of the word = the longest token to reach
+                        unsigned c = cost, A = 0;
+                        unsigned pend = L.rec[i].cpos & 0x7FFFu;
+                        while (c > 0) {
+                            const typename GR::Fin f = L.fin[i];
+                            const unsigned cpi = L.rec[i].cpos & 0x7FFFu;
+                            const unsigned sp = pend - cpi;
+                            A = A > sp ? A : sp;                 // the token emitted last step ended at pend
+                            const unsigned dd = A < Ls ? GR::dg(f) : GR::de(f);
+                            const unsigned j = i - 1 - dd;
+                            c--;
+                            L.rec[tok_base + c].smask = (M)j;   // span masks are dead after B
+                            pend = cpi;
+                            i = j;
+                        }
+                    }
+                }
+            }
+            wave_sync();
+            STAMP(3);
+            // ---------------------------------------------------------- C2: ids (lanes over all slots' tokens)
+            KREFRESH();
+            if (DPT_RUN_C2) phase_c2(kp, bid, lane, raw, len_only, n_pend, st);
+            wave_sync();
+            STAMP(7);
+
+            // ---------------------------------------------------------- advance slots, finish strings
+            KREFRESH();
+            advance_slots(kp, lane, len_only);
+            wave_sync();
+            STAMP(4);
+            STAMP(8);
+            WST_REC(1 + min(wst_it, WST_N - 4), WST_NOW() | ((unsigned long long)busy << 56));
+            wst_it++;
+        }
+        if constexpr (G == 16 && !BIG)
+            if (n_pend) {
+                walk_pending(kp, bid, lane, n_pend);
+                n_pend = 0;
+            }
+        if (!BIG && a.solo && lane == 0) {   // the call's only string, the grid's only wave
+            a.id_off[0] = 0;
+            reset_counters(a.retry_count, a.ctr_snap);
+        }
+        STAMP(9);
+        STAMP_FLUSH;
+        WST_REC(WST_N - 1, WST_NOW() | ((unsigned long long)wst_it << 48));
+#ifdef DPT_WSTAMPS
+        WST_REC(WST_N - 2, wst_claims);
 #endif
 #undef a
 #undef tv
-}
+    }
+};
+
+// The body of tokenize_kernel (and of fallback_kernel's 2048-byte blocks); bid: the block's index among the blocks running it
+template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
+__device__ __forceinline__ void tokenize_body(const unsigned bid) { TokPass<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>::body(bid); }
 
 template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
 // (the one-string kernel, SOLO, is one wave: no occupancy to keep, so no VGPR cap and no spills)

@@ -39,23 +39,10 @@
 #include <stdint.h>
 
 #include "dpt_internal.h"
+#include "dpt_wave.h"
 
 namespace dpt {
 namespace lng {
-
-__device__ __forceinline__ unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ unsigned uni(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
-
-__device__ __forceinline__ unsigned incl_scan_add(unsigned v) {
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, true);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xF, 0xF, true);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xF, 0xF, true);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xF, 0xF, true);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false); // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false); // row_bcast:31
-    return v;
-}
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, unsigned m) {
     const int src = (int)((lane_id() ^ m) << 2);
@@ -73,14 +60,10 @@ __device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
     return ((uint64_t)uni((unsigned)(v >> 32)) << 32) | uni((unsigned)v);
 }
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) { return __builtin_amdgcn_readlane(incl_scan_add(v), 63); }
+__device__ __forceinline__ unsigned wave_sum(unsigned v) { return __builtin_amdgcn_readlane(wave_incl_scan_add(v), 63); }
 
-// lane l receives x[l-1]; lane 0 receives `in` (wave_shr:1)
-__device__ __forceinline__ unsigned shift_in(unsigned x, unsigned in) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)in, (int)x, 0x138, 0xF, 0xF, false);
-}
 __device__ __forceinline__ uint64_t shift_in64(uint64_t x, uint64_t in) {
-    return ((uint64_t)shift_in((unsigned)(x >> 32), (unsigned)(in >> 32)) << 32) | shift_in((unsigned)x, (unsigned)in);
+    return ((uint64_t)wave_shift_in((unsigned)(x >> 32), (unsigned)(in >> 32)) << 32) | wave_shift_in((unsigned)x, (unsigned)in);
 }
 
 // global-memory ordering between the phases of one wave (the scratch is written and read back
@@ -263,7 +246,7 @@ __device__ __forceinline__ void long_body(const Args &a) {
                 cs += cl[u];
             }
             const unsigned v = an | (cs << 9);   // atoms <= 256 per chunk, code points <= 1536
-            const unsigned incl = incl_scan_add(v);
+            const unsigned incl = wave_incl_scan_add(v);
             const unsigned tot = __builtin_amdgcn_readlane(incl, 63);
             unsigned ai = na + ((incl - v) & 0x1FFu);
             unsigned cpi = cp + ((incl - v) >> 9);
@@ -445,9 +428,9 @@ __device__ __forceinline__ void long_body(const Args &a) {
                     S.rec[i].w = (unsigned)st_i;   // rec[i].w (mask hi of start i) is in `cur` already
                 }
                 sk = shift_in64(sk, st_i);
-                cpj = shift_in(cpj, cpi);
-                mlo = shift_in(mlo, cur.z);
-                mhi = shift_in(mhi, cur.w);
+                cpj = wave_shift_in(cpj, cpi);
+                mlo = wave_shift_in(mlo, cur.z);
+                mhi = wave_shift_in(mhi, cur.w);
                 prev = cur;
             }
         }
@@ -488,7 +471,7 @@ __device__ __forceinline__ void long_body(const Args &a) {
                 const bool mine = e <= na && S.wstart(e);
                 const uint64_t k = mine ? word_key(e) : 0ull;
                 const unsigned cost = mine ? (unsigned)(k >> 32) : 0u;
-                const unsigned incl = incl_scan_add(cost);
+                const unsigned incl = wave_incl_scan_add(cost);
                 const unsigned kbase = carry + incl - cost;   // tokens of the words before this one
                 carry += __builtin_amdgcn_readlane(incl, 63);
                 if (mine) {

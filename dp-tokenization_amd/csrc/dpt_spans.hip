@@ -20,30 +20,14 @@
 #include <stdint.h>
 
 #include "dpt_internal.h"
+#include "dpt_wave.h"
 
 namespace dpt {
 namespace spn {
 
 constexpr unsigned WAVES = 4;   // strings per block of 256 threads
 
-__device__ __forceinline__ unsigned lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ bool any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-__device__ __forceinline__ unsigned uni(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
-
-__device__ __forceinline__ unsigned incl_scan_add(unsigned v) {
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, true);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x112, 0xF, 0xF, true);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x114, 0xF, 0xF, true);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x118, 0xF, 0xF, true);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false); // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false); // row_bcast:31
-    return v;
-}
-
-// lane l receives x[l-1]; lane 0 receives `in` (wave_shr:1)
-__device__ __forceinline__ unsigned shift_in(unsigned x, unsigned in) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)in, (int)x, 0x138, 0xF, 0xF, false);
-}
 
 // the value of lane `src` (< 64, per lane)
 __device__ __forceinline__ unsigned lane_read(unsigned v, unsigned src) {
@@ -78,8 +62,8 @@ __device__ __forceinline__ void text_chunk(unsigned b, uint32_t len, uint64_t tb
             ws = q != 0 && (MODE == DPT_MODE_PRESPLIT ? b != 0u : (b & 1u) != 0u);
         }
     }
-    xi = incl_scan_add(w);
-    ci = cbase + incl_scan_add(ws);
+    xi = wave_incl_scan_add(w);
+    ci = cbase + wave_incl_scan_add(ws);
 }
 
 // The id of token k0 + lane (0 past the string's last token: nothing is loaded), and its byte length: 0
@@ -135,7 +119,7 @@ __global__ void __launch_bounds__(WAVES * 64) spans_kernel(SpansLaunch a) {
                 bad = true;
                 break;
             }
-            const uint32_t ei = incl_scan_add(tl);   // (64 tokens of at most 65535 bytes)
+            const uint32_t ei = wave_incl_scan_add(tl);   // (64 tokens of at most 65535 bytes)
             const uint64_t e = ebase + ei;
             ebase += (uint32_t)__builtin_amdgcn_readlane((int)ei, 63);
             bool pend = act;
@@ -176,7 +160,7 @@ __global__ void __launch_bounds__(WAVES * 64) spans_kernel(SpansLaunch a) {
                 pend = pend && !can;
             }
             if (bad) break;
-            const uint32_t word = shift_in(wend, wcarry);   // the word starts up to the token's start
+            const uint32_t word = wave_shift_in(wend, wcarry);   // the word starts up to the token's start
             if (act) {
                 a.tok_end[ib + k] = endp;
                 if (a.tok_word) a.tok_word[ib + k] = word;
