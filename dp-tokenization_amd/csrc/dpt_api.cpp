@@ -1,6 +1,7 @@
 // dpt_api.cpp -- the C-ABI declared in include/dpt.h.
 //
-// Owns: the device copy of the vocabulary (dpt_vocab: the upload of dpt_vocab.cpp's build_vocab_tables),
+// Owns: the device copy of the vocabulary (dpt_vocab: the upload of dpt_vocab.cpp's build_vocab_tables) and of
+// a decode table (dpt_detok: dpt_detok.cpp's build_detok_tables),
 // per-stream workspaces (dpt_ctx), argument checking, the host-buffer convenience paths and their staging,
 // and the event-based kernel timing used by bench.py.  No C++ exception crosses the ABI.
 #include <hip/hip_runtime.h>
@@ -23,6 +24,15 @@ struct dpt_vocab : dpt::VocabScalars {
     // dpt_token_spans: byte length per id - id_min (0: no token has this id); null when the ids are too
     // sparse for a dense table or two tokens of different length share an id (the spans calls: DPT_E_VOCAB)
     uint16_t *d_tok_len = nullptr;
+};
+
+// The device copy of a decode table (dpt_detok.cpp build_detok_tables).
+struct dpt_detok {
+    int device = 0;
+    uint2 *d_tab = nullptr;     // {offset in the blob, length | dpt::DETOK_NONE} per id - id_min
+    uint8_t *d_blob = nullptr;  // the decoded pieces (never null: an empty blob is one byte)
+    int32_t id_min = 0;
+    uint32_t n_tab = 0;
 };
 
 static uint64_t flag_words(uint64_t cap_batches) { return cap_batches * (2 * dpt::BS_LINE + 1); }
@@ -256,6 +266,28 @@ struct SpansLayout {
         in_idoff = 8 * (n_str + 1); in_ids = 2 * in_idoff; in_st = in_ids + al8(4 * n_tok + 4);
         in_text = in_st + al8(4 * n_str); in_cut = in_text + al8(n_bytes + 1); in_bytes = in_cut + (cut ? al8(n_bytes + 1) : 0);
         word = al8(4 * n_tok + 4); ss = with_word ? 2 * word : word; out_bytes = ss + al8(4 * n_str);
+    }
+};
+
+// The decode host path's (id_off sits at 0; the sizes pass has out_len alone in the out buffer, the decode
+// pass dec_status and the bytes):
+struct DecodeLayout {
+    uint64_t in_outoff, in_ids, in_st, in_bytes;   // in:  id_off rebased to 0 | out_off | ids | status
+    uint64_t len_bytes, bytes;                     // out: out_len (sizes pass); dec_status | the decoded bytes (decode pass)
+    DecodeLayout(uint64_t n_str, uint64_t n_tok) {
+        in_outoff = 8 * (n_str + 1); in_ids = 2 * in_outoff; in_st = in_ids + al8(4 * n_tok + 4);
+        in_bytes = in_st + al8(4 * n_str + 4);
+        len_bytes = 8 * n_str; bytes = al8(4 * n_str + 4);
+    }
+};
+// The round trip's (id_off and rt sit at 0):
+struct RoundtripLayout {
+    uint64_t in_stroff, in_ids, in_st, in_text, in_bytes;   // in:  id_off and str_off rebased to 0 | ids | status | text
+    uint64_t fd, out_bytes;                                 // out: rt | first_diff
+    RoundtripLayout(uint64_t n_bytes, uint64_t n_str, uint64_t n_tok) {
+        in_stroff = 8 * (n_str + 1); in_ids = 2 * in_stroff; in_st = in_ids + al8(4 * n_tok + 4);
+        in_text = in_st + al8(4 * n_str + 4); in_bytes = in_text + al8(n_bytes + 1);
+        fd = al8(4 * n_str + 4); out_bytes = 2 * fd;
     }
 };
 
@@ -861,6 +893,198 @@ int dpt_token_spans_host(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_t
     if (n_tok) memcpy(tok_end, c->p_out, 4 * n_tok);
     if (n_tok && tok_word) memcpy(tok_word, c->p_out + L.word, 4 * n_tok);
     memcpy(span_status, c->p_out + L.ss, 4 * n_str);
+    return DPT_OK;
+}
+
+int dpt_detok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok, int rule,
+                     const int32_t *skip_ids, uint32_t n_skip, int device, dpt_detok **out) {
+    if (!out || !tok_off || (!utf8_blob && n_tok && tok_off[n_tok] != tok_off[0]) || (n_skip && !skip_ids))
+        return fail(DPT_E_ARG, "null argument");
+    *out = nullptr;
+    if (rule < DPT_DETOK_PIECES || rule > DPT_DETOK_BYTELEVEL) return fail(DPT_E_ARG, "no such decode rule");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(DPT_E_NODEV, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(DPT_E_ARG, "bad device index");
+    for (uint32_t t = 0; t < n_tok; t++)
+        if (tok_off[t + 1] < tok_off[t]) return fail(DPT_E_ARG, "tok_off not monotone");
+    dpt::DetokTables t;
+    if (const char *err = dpt::build_detok_tables(utf8_blob, tok_off, ids, n_tok, rule, skip_ids, n_skip, &t)) return fail(DPT_E_VOCAB, err);
+    if (t.blob.empty()) t.blob.push_back(0);
+    DeviceGuard g(device);
+    dpt_detok *d = new (std::nothrow) dpt_detok();
+    if (!d) return fail(DPT_E_ARG, "out of host memory");
+    d->device = device; d->id_min = t.id_min; d->n_tab = t.n_tab;
+    hipError_t e = upload(&d->d_tab, t.tab);
+    if (e == hipSuccess) e = upload(&d->d_blob, t.blob);
+    if (e != hipSuccess) {
+        dpt_detok_destroy(d);
+        return hip_fail(e, "decode table upload");
+    }
+    *out = d;
+    return DPT_OK;
+}
+
+int dpt_detok_destroy(dpt_detok *d) {
+    if (!d) return DPT_OK;
+    DeviceGuard g(d->device);
+    (void)hipFree(d->d_tab);
+    (void)hipFree(d->d_blob);
+    delete d;
+    return DPT_OK;
+}
+
+// Argument checks shared by the decode entry points (no device is touched, d is not dereferenced before every
+// pointer has been checked), and the table's part of a launch.
+static int decode_check(dpt::DecodeLaunch *p, const dpt_detok *d, int flags) {
+    if (!d) return fail(DPT_E_ARG, "null detok");
+    if (!p->id_off) return fail(DPT_E_ARG, "null id_off");
+    if (flags & ~DPT_DECODE_STRIP_SPACE) return fail(DPT_E_ARG, "bad decode flags");
+    if (p->kind == dpt::DECODE_SIZES && !p->out_len) return fail(DPT_E_ARG, "null out_len");
+    if (p->kind == dpt::DECODE_BYTES && !p->out_off) return fail(DPT_E_ARG, "null out_off");
+    if (p->kind == dpt::DECODE_BYTES && !p->result) return fail(DPT_E_ARG, "null dec_status");
+    if (p->kind == dpt::DECODE_ROUNDTRIP && !p->str_off) return fail(DPT_E_ARG, "null str_off");
+    if (p->kind == dpt::DECODE_ROUNDTRIP && !p->result) return fail(DPT_E_ARG, "null rt");
+    p->flags = flags; p->tab = d->d_tab; p->blob = d->d_blob; p->id_min = d->id_min; p->n_tab = d->n_tab;
+    return DPT_OK;
+}
+
+static int decode_launch(const dpt::DecodeLaunch &p, const dpt_detok *d, void *hip_stream) {
+    DeviceGuard g(d->device);
+    const hipError_t e = dpt::launch_decode(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "decode launch");
+    return DPT_OK;
+}
+
+int dpt_decode_sizes(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint64_t n_str,
+                     int flags, uint64_t *out_len, void *hip_stream) {
+    dpt::DecodeLaunch p{};
+    p.kind = dpt::DECODE_SIZES; p.ids = ids; p.id_off = id_off; p.status = status; p.n_str = n_str; p.out_len = out_len;
+    if (const int rc = decode_check(&p, d, flags)) return rc;
+    return decode_launch(p, d, hip_stream);
+}
+
+int dpt_decode(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint64_t n_str,
+               int flags, uint8_t *out, const uint64_t *out_off, int32_t *dec_status, void *hip_stream) {
+    dpt::DecodeLaunch p{};
+    p.kind = dpt::DECODE_BYTES; p.ids = ids; p.id_off = id_off; p.status = status; p.n_str = n_str;
+    p.out = out; p.out_off = out_off; p.result = dec_status;
+    if (const int rc = decode_check(&p, d, flags)) return rc;
+    return decode_launch(p, d, hip_stream);
+}
+
+int dpt_roundtrip(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                  const uint8_t *text, const uint64_t *str_off, uint64_t n_str, int flags, int32_t *rt,
+                  uint32_t *first_diff, void *hip_stream) {
+    dpt::DecodeLaunch p{};
+    p.kind = dpt::DECODE_ROUNDTRIP; p.ids = ids; p.id_off = id_off; p.status = status; p.n_str = n_str;
+    p.text = text; p.str_off = str_off; p.result = rt; p.first_diff = first_diff;
+    if (const int rc = decode_check(&p, d, flags)) return rc;
+    return decode_launch(p, d, hip_stream);
+}
+
+// the decode host paths' offsets (nullable str_off): monotone
+static int check_decode_off(const uint64_t *id_off, const uint64_t *str_off, uint64_t n_str) {
+    for (uint64_t i = 0; i < n_str; i++) {
+        if (id_off[i + 1] < id_off[i]) return fail(DPT_E_ARG, "id_off not monotone");
+        if (str_off && str_off[i + 1] < str_off[i]) return fail(DPT_E_ARG, "str_off not monotone");
+        if (str_off && str_off[i + 1] - str_off[i] >= (1ull << 32)) return fail(DPT_E_ARG, "a string of 4 GiB or more");
+    }
+    return DPT_OK;
+}
+
+int dpt_decode_host(dpt_ctx *c, const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                    uint64_t n_str, int flags, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *dec_status) {
+    // host arguments first (checkable without a device)
+    dpt::DecodeLaunch p{};
+    p.kind = dpt::DECODE_BYTES; p.ids = ids; p.id_off = id_off; p.status = status; p.n_str = n_str;
+    p.out = out; p.out_off = out_off; p.result = dec_status;
+    int rc = decode_check(&p, d, flags);
+    if (rc) return rc;
+    if (!c) return fail(DPT_E_ARG, "null ctx");
+    if ((rc = check_decode_off(id_off, nullptr, n_str))) return rc;
+    const uint64_t n_tok = id_off[n_str] - id_off[0];
+    if ((n_tok && !ids) || (out_cap && !out)) return fail(DPT_E_ARG, "null argument");
+    if (c->device != d->device) return fail(DPT_E_ARG, "ctx and detok on different devices");
+    out_off[0] = 0;
+    if (n_str == 0) return DPT_OK;
+    DeviceGuard g(c->device);
+    hipError_t e;
+    const DecodeLayout L(n_str, n_tok);
+    if ((rc = stage_host(c, L.in_bytes, L.len_bytes))) return rc;
+    uint64_t *io = at<uint64_t>(c->p_in, 0);
+    for (uint64_t i = 0; i <= n_str; i++) io[i] = id_off[i] - id_off[0];
+    if (n_tok) memcpy(c->p_in + L.in_ids, ids, 4 * n_tok);
+    if (status) memcpy(c->p_in + L.in_st, status, 4 * n_str);
+    // the sizes, then their prefix sum on the host
+    p.kind = dpt::DECODE_SIZES;
+    p.ids = at<const int32_t>(c->d_in, L.in_ids); p.id_off = at<const uint64_t>(c->d_in, 0);
+    p.status = status ? at<const int32_t>(c->d_in, L.in_st) : nullptr; p.out_len = at<uint64_t>(c->d_out, 0);
+    const hipStream_t st = 0;
+    if ((e = hipMemcpyAsync(c->d_in, c->p_in, L.in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D");
+    if ((e = dpt::launch_decode(p, st)) != hipSuccess) return hip_fail(e, "decode sizes launch");
+    if ((e = hipMemcpyAsync(c->p_out, c->d_out, L.len_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+    const uint64_t *len = at<const uint64_t>(c->p_out, 0);
+    for (uint64_t i = 0; i < n_str; i++) out_off[i + 1] = out_off[i] + len[i];
+    const uint64_t decoded = out_off[n_str];
+    if (decoded > out_cap) return fail(DPT_E_CAP, "decoded bytes do not fit out_cap (the need is out_off[n_str])");
+    // the bytes (the in buffer keeps its size, so it stays where it is; the out buffer may move)
+    if ((rc = stage_host(c, L.in_bytes, L.bytes + al8(decoded + 1)))) return rc;
+    uint64_t *oo = at<uint64_t>(c->p_in, L.in_outoff);
+    memcpy(oo, out_off, 8 * (n_str + 1));
+    p.kind = dpt::DECODE_BYTES;
+    p.out = c->d_out + L.bytes; p.out_off = at<const uint64_t>(c->d_in, L.in_outoff); p.result = at<int32_t>(c->d_out, 0);
+    if ((e = hipMemcpyAsync(c->d_in + L.in_outoff, oo, 8 * (n_str + 1), hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D");
+    if ((e = dpt::launch_decode(p, st)) != hipSuccess) return hip_fail(e, "decode launch");
+    if ((e = hipMemcpyAsync(c->p_out, c->d_out, L.bytes + decoded, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+    memcpy(dec_status, c->p_out, 4 * n_str);
+    if (decoded) memcpy(out, c->p_out + L.bytes, decoded);
+    return DPT_OK;
+}
+
+int dpt_roundtrip_host(dpt_ctx *c, const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                       const uint8_t *text, const uint64_t *str_off, uint64_t n_str, int flags, int32_t *rt,
+                       uint32_t *first_diff) {
+    dpt::DecodeLaunch p{};
+    p.kind = dpt::DECODE_ROUNDTRIP; p.ids = ids; p.id_off = id_off; p.status = status; p.n_str = n_str;
+    p.text = text; p.str_off = str_off; p.result = rt; p.first_diff = first_diff;
+    int rc = decode_check(&p, d, flags);
+    if (rc) return rc;
+    if (!c) return fail(DPT_E_ARG, "null ctx");
+    if ((rc = check_decode_off(id_off, str_off, n_str))) return rc;
+    const uint64_t n_tok = id_off[n_str] - id_off[0], n_bytes = str_off[n_str] - str_off[0];
+    if ((n_tok && !ids) || (n_bytes && !text)) return fail(DPT_E_ARG, "null argument");
+    if (c->device != d->device) return fail(DPT_E_ARG, "ctx and detok on different devices");
+    if (n_str == 0) return DPT_OK;
+    DeviceGuard g(c->device);
+    hipError_t e;
+    const RoundtripLayout L(n_bytes, n_str, n_tok);
+    if ((rc = stage_host(c, L.in_bytes, L.out_bytes))) return rc;
+    uint64_t *io = at<uint64_t>(c->p_in, 0), *so = at<uint64_t>(c->p_in, L.in_stroff);
+    for (uint64_t i = 0; i <= n_str; i++) {
+        io[i] = id_off[i] - id_off[0];
+        so[i] = str_off[i] - str_off[0];
+    }
+    if (n_tok) memcpy(c->p_in + L.in_ids, ids, 4 * n_tok);
+    if (status) memcpy(c->p_in + L.in_st, status, 4 * n_str);
+    if (n_bytes) memcpy(c->p_in + L.in_text, text, n_bytes);
+    // the same call on the device buffers
+    p.ids = at<const int32_t>(c->d_in, L.in_ids); p.id_off = at<const uint64_t>(c->d_in, 0);
+    p.status = status ? at<const int32_t>(c->d_in, L.in_st) : nullptr;
+    p.text = c->d_in + L.in_text; p.str_off = at<const uint64_t>(c->d_in, L.in_stroff);
+    p.result = at<int32_t>(c->d_out, 0); p.first_diff = at<uint32_t>(c->d_out, L.fd);
+    const hipStream_t st = 0;
+    if ((e = hipMemcpyAsync(c->d_in, c->p_in, L.in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D");
+    if ((e = dpt::launch_decode(p, st)) != hipSuccess) return hip_fail(e, "roundtrip launch");
+    if ((e = hipMemcpyAsync(c->p_out, c->d_out, L.out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "sync");
+    memcpy(rt, c->p_out, 4 * n_str);
+    if (first_diff) {   // (written only where the verdict is DPT_RT_DIFFERS, as the device call does)
+        const uint32_t *fd = at<const uint32_t>(c->p_out, L.fd);
+        for (uint64_t i = 0; i < n_str; i++)
+            if (rt[i] == DPT_RT_DIFFERS) first_diff[i] = fd[i];
+    }
     return DPT_OK;
 }
 

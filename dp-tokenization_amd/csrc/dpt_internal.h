@@ -1,5 +1,5 @@
-// Internal interface between the C-ABI (dpt_api.cpp), the host table builder (dpt_vocab.cpp) and the
-// kernels (dpt_kernels.hip, dpt_spans.hip).
+// Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp)
+// and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -245,6 +245,52 @@ struct SpansLaunch {
 };
 hipError_t launch_spans(const SpansLaunch &p, hipStream_t stream);
 hipError_t kernel_init();
+
+// Decode table of a vocabulary (dpt_detok.cpp build_detok_tables; include/dpt.h dpt_detok_create): what
+// every id decodes to under one rule, as host bytes exactly as dpt_detok_create uploads them.
+//   tab[id - id_min] = {.x = the piece's offset in blob, .y = its length in bytes (0: a skipped id or a
+//   piece that decodes to nothing), or DETOK_NONE for an id no token has (.x = 0)}
+//   blob = the pieces in id order, back to back
+constexpr uint32_t DETOK_NONE = 0x80000000u;
+struct DetokTables {
+    std::vector<uint2> tab;
+    std::vector<uint8_t> blob;
+    int32_t id_min = 0;
+    uint32_t n_tab = 0;
+    uint32_t longest = 0;   // the longest decoded piece, bytes
+};
+// returns 0 or an error message; calls no HIP function
+const char *build_detok_tables(const uint8_t *blob, const uint64_t *off, const int32_t *ids, uint32_t n, int rule,
+                               const int32_t *skip_ids, uint32_t n_skip, DetokTables *out);
+
+// One launch of the decode kernels (dpt_decode.hip; include/dpt.h dpt_decode_sizes, dpt_decode, dpt_roundtrip):
+// every pointer a device pointer.
+enum DecodeKind { DECODE_SIZES = 0, DECODE_BYTES = 1, DECODE_ROUNDTRIP = 2 };
+struct DecodeLaunch {
+    int kind;                  // DecodeKind
+    int flags;                 // DPT_DECODE_*
+    const int32_t *ids;
+    const uint64_t *id_off;
+    const int32_t *status;     // nullable: all 0
+    uint64_t n_str;
+    // the table
+    const uint2 *tab;
+    const uint8_t *blob;
+    int32_t id_min;
+    uint32_t n_tab;
+    // DECODE_SIZES
+    uint64_t *out_len;
+    // DECODE_BYTES
+    uint8_t *out;
+    const uint64_t *out_off;
+    // DECODE_ROUNDTRIP
+    const uint8_t *text;
+    const uint64_t *str_off;
+    uint32_t *first_diff;      // nullable
+    // DECODE_BYTES: dec_status, DECODE_ROUNDTRIP: rt
+    int32_t *result;
+};
+hipError_t launch_decode(const DecodeLaunch &p, hipStream_t stream);
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

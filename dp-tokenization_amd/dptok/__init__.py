@@ -2,15 +2,16 @@
 
 Public surface:
     Vocab, Encoder          batch engine (engine.py)
+    Detok                   ids back to bytes and the round-trip check (engine.py)
     dp_tokenize_batch       List[str] -> List[List[int]] for a t2i vocabulary
     synth                   synthetic vocabularies/corpora of the BASELINE configs
 The reference-compatible names (dp_tokenize_llama, compute_shortest_tokenizations, ...)
 live in the sibling ``packages`` / ``inspect_tokenizer`` modules of this directory.
 """
-from ._lib import DptError, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
-from .engine import Encoder, TokenSpans, Vocab, pack_strings, raise_for_status
+from ._lib import DptError, RT_DIFFERS, RT_EQUAL, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
+from .engine import Detok, Encoder, TokenSpans, Vocab, pack_strings, raise_for_status
 
-__all__ = ["Vocab", "Encoder", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
+__all__ = ["Vocab", "Encoder", "Detok", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
            "STATUS_OK", "STATUS_NO_TOKENIZATION", "STATUS_EMPTY_WORD", "STATUS_TOO_LONG", "STATUS_INTERNAL"]
 
 

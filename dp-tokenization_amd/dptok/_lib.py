@@ -22,6 +22,9 @@ DPT_MODE_ATOMS = 2
 DPT_FLAG_UNCAPPED = 0x10
 DPT_FLAG_LEN_ONLY = 0x20
 STATUS_OK, STATUS_NO_TOKENIZATION, STATUS_EMPTY_WORD, STATUS_TOO_LONG, STATUS_INTERNAL = range(5)
+DPT_DETOK_PIECES, DPT_DETOK_SP, DPT_DETOK_BYTELEVEL = range(3)
+DPT_DECODE_STRIP_SPACE = 1
+RT_EQUAL, RT_DIFFERS = 0, 5
 
 
 class DptError(RuntimeError):
@@ -38,6 +41,19 @@ _lib = None
 P = ctypes.c_void_p
 U64 = ctypes.c_uint64
 I32 = ctypes.c_int
+U32 = ctypes.c_uint32
+
+# include/dpt.h, "Decode": name -> argument types
+DECODE_CALLS = {
+    "dpt_detok_create": [P, P, P, U32, I32, P, U32, I32, ctypes.POINTER(P)],
+    "dpt_detok_destroy": [P],
+    "dpt_decode_sizes": [P, P, P, P, U64, I32, P, P],
+    "dpt_decode": [P, P, P, P, U64, I32, P, P, P, P],
+    "dpt_roundtrip": [P, P, P, P, P, P, U64, I32, P, P, P],
+    "dpt_decode_host": [P, P, P, P, P, U64, I32, P, U64, P, P],
+    "dpt_roundtrip_host": [P, P, P, P, P, P, P, U64, I32, P, P],
+    "dpt_debug_detok_table": [P, P, P, U32, I32, P, U32, I32, P, U64, ctypes.POINTER(U64)],
+}
 
 
 def lib():
@@ -75,6 +91,12 @@ def lib():
     L.dpt_token_histogram.argtypes = [P, P, U64, P, ctypes.c_uint32, P]
     L.dpt_token_spans.argtypes = [P, I32, P, U64, P, P, U64, P, P, P, P, P, P, P]
     L.dpt_token_spans_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P, P, P, P]
+    # the decode calls came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still
+    # encodes; ``Detok`` then raises (has_decode)
+    for name, argtypes in DECODE_CALLS.items():
+        if hasattr(L, name):
+            getattr(L, name).argtypes = argtypes
+            getattr(L, name).restype = I32
     L.dpt_ctx_set_histogram.argtypes = [P, P, ctypes.c_uint32]
     L.dpt_ctx_set_histogram_ex.argtypes = [P, P, ctypes.c_uint32, I32]
     L.dpt_ctx_profile.argtypes = [P, I32]
@@ -95,6 +117,12 @@ def lib():
     return L
 
 
+def has_decode() -> bool:
+    """The loaded library exports the decode calls (a libdpt.so built before them does not)."""
+    L = lib()
+    return all(hasattr(L, name) for name in DECODE_CALLS)
+
+
 def check(rc: int, what: str = "") -> None:
     if rc != DPT_OK:
         msg = lib().dpt_last_error().decode("utf-8", "replace")
@@ -108,4 +136,5 @@ EXPORTED = ["dpt_last_error", "dpt_abi_version", "dpt_vocab_create", "dpt_vocab_
             "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram", "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex",
             "dpt_token_spans", "dpt_token_spans_host",
             "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias", "dpt_debug_launch_plan",
-            "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"]
+            "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"] + \
+    list(DECODE_CALLS)

@@ -547,3 +547,147 @@ class Encoder:
         n = ctypes.c_uint64()
         check(_lib.lib().dpt_ctx_profile_read(self.handle, ms, ctypes.byref(n)), "dpt_ctx_profile_read")
         return [ms[0], ms[1], ms[2]], n.value
+
+
+DETOK_RULES = {"pieces": _lib.DPT_DETOK_PIECES, "sp": _lib.DPT_DETOK_SP, "bytelevel": _lib.DPT_DETOK_BYTELEVEL}
+
+
+class Detok:
+    """Device-resident decode table of ``t2i`` under one rule (include/dpt.h dpt_detok_create): ids back to
+    bytes, and the round-trip check of an encoded batch -- the tokenizer's own ``decode`` of the reference's
+    second closure (packages/tokenizer_utils.py:82-84, :176-179) and its caller's assert
+    (main_analyze_s2orc.py:84-87) for a whole batch in one launch.
+
+    ``rule``: "pieces" (the tokens' bytes), "sp" (SentencePiece: U+2581 -> ' ', ``<0xNN>`` -> the byte) or
+    "bytelevel" (the GPT-2 / ByteLevel alphabet back to bytes); ``skip_ids`` decode to nothing (BOS).
+    ``strip_space`` drops a string's first decoded byte when it is ' '.  The output is bytes: nothing is
+    validated or repaired as UTF-8."""
+
+    def __init__(self, t2i: Dict[str, int], rule: str = "sp", skip_ids: Iterable[int] = (), device: int = 0):
+        L = _lib.lib()
+        if not _lib.has_decode():
+            raise DptError(f"{_lib.LIB_PATH} was built before the decode calls (no dpt_detok_create): rebuild it")
+        toks = list(t2i.keys())
+        enc = [encode_utf8(t) for t in toks]
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        if enc:
+            off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
+        ids = np.array([t2i[t] for t in toks], dtype=np.int32)
+        skip = np.array(list(skip_ids), dtype=np.int32)
+        h = ctypes.c_void_p()
+        check(L.dpt_detok_create(_ptr(blob), _ptr(off), _ptr(ids), len(toks), DETOK_RULES[rule],
+                                 _ptr(skip) if len(skip) else None, len(skip), device, ctypes.byref(h)), "dpt_detok_create")
+        self.handle = h
+        self.device = device
+        self.rule = rule
+        self.ctx = None   # the host paths' staging, made on first use
+
+    def __del__(self):
+        L = _lib._lib
+        if L is None:
+            return
+        c, h = getattr(self, "ctx", None), getattr(self, "handle", None)
+        if c:
+            L.dpt_ctx_destroy(c)
+            self.ctx = None
+        if h:
+            L.dpt_detok_destroy(h)
+            self.handle = None
+
+    def _ctx(self):
+        if self.ctx is None:
+            c = ctypes.c_void_p()
+            check(_lib.lib().dpt_ctx_create(self.device, ctypes.byref(c)), "dpt_ctx_create")
+            self.ctx = c
+        return self.ctx
+
+    @staticmethod
+    def _csr(ids, id_off, status):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        id_off = np.ascontiguousarray(id_off, dtype=np.uint64)
+        if len(id_off) < 1:
+            raise ValueError("id_off needs n + 1 entries")
+        n = len(id_off) - 1
+        if status is not None:
+            status = np.ascontiguousarray(status, dtype=np.int32)
+            if len(status) < n:
+                raise ValueError("status shorter than the batch")
+        if len(ids) < int(id_off[-1]):
+            raise ValueError("ids shorter than id_off[-1]")
+        return ids[int(id_off[0]):], id_off, status, n
+
+    # ---------------------------------------------------------------- host buffers
+    def decode_csr(self, ids: np.ndarray, id_off: np.ndarray, status: Optional[np.ndarray] = None,
+                   strip_space: bool = False):
+        """CSR ids in -> (bytes u8[], out_off u64[n+1], dec_status int32[n]): string s decodes to
+        bytes[out_off[s]:out_off[s+1]]; dec_status[s] is status[s], or 4 when an id of s has no token (its
+        bytes are then unspecified)."""
+        ids, id_off, status, n = self._csr(ids, id_off, status)
+        flags = _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        dec_status = np.zeros(max(n, 1), dtype=np.int32)
+        cap = 4 * len(ids) + 64   # (most pieces are shorter; a longer decode answers DPT_E_CAP with its need)
+        L = _lib.lib()
+        while True:
+            out = np.empty(max(cap, 1), dtype=np.uint8)
+            rc = L.dpt_decode_host(self._ctx(), self.handle, _ptr(ids), _ptr(id_off), _ptr(status), n, flags, _ptr(out), cap,
+                                   _ptr(out_off), _ptr(dec_status))
+            if rc == _lib.DPT_E_CAP and int(out_off[-1]) > cap:
+                cap = int(out_off[-1])
+                continue
+            check(rc, "dpt_decode_host")
+            return out[: int(out_off[-1])], out_off, dec_status[:n]
+
+    def roundtrip_csr(self, text: np.ndarray, offs: np.ndarray, ids: np.ndarray, id_off: np.ndarray,
+                      status: Optional[np.ndarray] = None, strip_space: bool = False):
+        """The decode of every string against text[offs[s]:offs[s+1]] without writing it -> (rt int32[n],
+        first_diff int64[n]): rt[s] is status[s] when that is not 0, else RT_EQUAL, RT_DIFFERS or 4 (an id
+        without a token); first_diff[s] the first differing byte offset (the shorter length when one side is
+        a prefix of the other), -1 where rt[s] != RT_DIFFERS."""
+        ids, id_off, status, n = self._csr(ids, id_off, status)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if len(offs) != n + 1:
+            raise ValueError("offs and id_off differ in length")
+        if len(text) < int(offs[-1]):
+            raise ValueError("text shorter than offs[-1]")
+        rt = np.zeros(max(n, 1), dtype=np.int32)
+        fd = np.zeros(max(n, 1), dtype=np.uint32)
+        base = int(offs[0])
+        check(_lib.lib().dpt_roundtrip_host(self._ctx(), self.handle, _ptr(ids), _ptr(id_off), _ptr(status),
+                                            _ptr(text[base:] if base else text), _ptr(offs), n,
+                                            _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, _ptr(rt), _ptr(fd)),
+              "dpt_roundtrip_host")
+        rt = rt[:n]
+        return rt, np.where(rt == _lib.RT_DIFFERS, fd[:n].astype(np.int64), -1)
+
+    # ---------------------------------------------------------------- device buffers
+    def sizes_device(self, ids_ptr: int, idoff_ptr: int, n_str: int, out_len_ptr: int, status_ptr: int = 0,
+                     strip_space: bool = False, stream: int = 0) -> None:
+        """dpt_decode_sizes: out_len (uint64 per string) = the decoded bytes of each string.  Device
+        addresses, stream-ordered, no sync, no workspace."""
+        check(_lib.lib().dpt_decode_sizes(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
+                                          ctypes.c_void_p(status_ptr or None), n_str,
+                                          _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, ctypes.c_void_p(out_len_ptr),
+                                          ctypes.c_void_p(stream or None)), "dpt_decode_sizes")
+
+    def decode_device(self, ids_ptr: int, idoff_ptr: int, n_str: int, out_ptr: int, out_off_ptr: int, dec_status_ptr: int,
+                      status_ptr: int = 0, strip_space: bool = False, stream: int = 0) -> None:
+        """dpt_decode: string s's bytes at out + out_off[s] - out_off[0] (out_off: uint64[n_str + 1], the
+        prefix sum of ``sizes_device``'s lengths from any start), dec_status int32 per string."""
+        check(_lib.lib().dpt_decode(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
+                                    ctypes.c_void_p(status_ptr or None), n_str,
+                                    _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, ctypes.c_void_p(out_ptr or None),
+                                    ctypes.c_void_p(out_off_ptr), ctypes.c_void_p(dec_status_ptr),
+                                    ctypes.c_void_p(stream or None)), "dpt_decode")
+
+    def roundtrip_device(self, ids_ptr: int, idoff_ptr: int, text_ptr: int, off_ptr: int, n_str: int, rt_ptr: int,
+                         first_diff_ptr: int = 0, status_ptr: int = 0, strip_space: bool = False, stream: int = 0) -> None:
+        """dpt_roundtrip: rt (int32 per string) and first_diff (uint32 per string, 0: not wanted; written
+        only where rt is RT_DIFFERS) of the decode against text / offsets (the encode's own)."""
+        check(_lib.lib().dpt_roundtrip(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
+                                       ctypes.c_void_p(status_ptr or None), ctypes.c_void_p(text_ptr or None),
+                                       ctypes.c_void_p(off_ptr), n_str, _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0,
+                                       ctypes.c_void_p(rt_ptr), ctypes.c_void_p(first_diff_ptr or None),
+                                       ctypes.c_void_p(stream or None)), "dpt_roundtrip")

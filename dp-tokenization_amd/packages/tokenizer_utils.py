@@ -21,6 +21,10 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   the (start, end) of token k in characters of ``text``, ``word_ids[k]`` the 0-based word it lies in
   (what the probe at reference main_analyze_s2orc.py:275-290 re-tokenizes every word to learn).  Same
   exceptions as ``batch``.
+* ``decode_dp_tokenization.batch(List[List[int]]) -> List[str]`` and ``dp_tokenize.batch_roundtrip(List[str])
+  -> List[Optional[int]]``: the tokenizer's own decode of a batch, and the caller's round-trip assert
+  (reference main_analyze_s2orc.py:84-87), each in one GPU launch; ``decode_dp_tokenization`` itself stays
+  the tokenizer object's ``decode``.
 * ``merge_tokens``, ``pretokenize_with_llama``, ``pretokenize_raw``: the reference's host-side
   string utilities with identical behaviour (pre-tokenization, not the DP).
 """
@@ -28,13 +32,15 @@ from __future__ import annotations
 
 import os
 import sys
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _HERE not in sys.path:
     sys.path.insert(0, _HERE)
 
-from dptok import DptError, Encoder, Vocab, raise_for_status  # noqa: E402
+from dptok import Detok, DptError, Encoder, Vocab, raise_for_status  # noqa: E402
 from dptok import _lib as _dpt  # noqa: E402
 from dptok.engine import (PieceTable, TokenSpans, csr_token_spans, pack_presplit_words, pack_strings,  # noqa: E402
                           pack_word_atoms)
@@ -164,6 +170,78 @@ def _batch_spans(engine, texts, text, offs, mode, cut=None, none=None, fix_statu
     return out
 
 
+_DECODE_BATCH_DOC = """``decode_dp_tokenization.batch(list of id lists) -> List[str]``: every list decoded on the
+GPU in one launch, the bytes read as UTF-8 with ``errors="replace"``.  This is %s own decode of the ids.  A
+``transformers`` tokenizer's ``decode`` -- what ``decode_dp_tokenization`` itself calls -- may render special
+tokens and spacing differently: on the recorded llama-mode cases 83 of 565 differ for the ``transformers``
+tokenizer, none for the SentencePiece one."""
+
+_ROUNDTRIP_DOC = """``dp_tokenize.batch_roundtrip(texts) -> List[Optional[int]]``: the encode exactly as ``batch`` (same
+exceptions, in the same order), then ONE round-trip launch against the original texts -- the caller's
+``decode_dp_tokenization(dp_tokenize(x)) == x`` (reference main_analyze_s2orc.py:84-87) for the batch.  Per
+string None when the decode equals the text, else the first differing byte offset of its UTF-8."""
+
+
+def _bos_id(tokenizer) -> Optional[int]:
+    """The tokenizer's BOS id when it has one: its ``bos_token_id``, else the one id it puts in front of
+    the empty string (the SentencePiece wrappers without that attribute)."""
+    bos = getattr(tokenizer, "bos_token_id", None)
+    if bos is None:
+        try:
+            e = list(tokenizer.encode(""))
+        except Exception:
+            return None
+        bos = e[0] if len(e) == 1 else None
+    return None if bos is None else int(bos)
+
+
+def _pack_id_lists(id_lists):
+    """List of id lists -> (ids int32[], id_off u64[n+1])."""
+    import itertools
+    cnt = np.fromiter((len(x) for x in id_lists), dtype=np.int64, count=len(id_lists))
+    ids = np.fromiter(itertools.chain.from_iterable(id_lists), dtype=np.int64, count=int(cnt.sum()))
+    if len(ids) and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):
+        raise DptError("decode: an id outside int32")
+    id_off = np.zeros(len(id_lists) + 1, dtype=np.uint64)
+    if len(cnt):
+        id_off[1:] = np.cumsum(cnt, dtype=np.uint64)
+    return ids.astype(np.int32), id_off
+
+
+def _decode_surface(make_detok, strip, encode_many):
+    """The batch calls over one lazily built ``Detok`` (the table is built and uploaded at the first call):
+    ``decode_batch(list of id lists) -> List[str]`` and ``batch_roundtrip(texts) -> List[Optional[int]]``."""
+    box = []
+
+    def detok():
+        if not box:
+            box.append(make_detok())
+        return box[0]
+
+    def decode_batch(id_lists) -> List[str]:
+        id_lists = list(id_lists)
+        ids, id_off = _pack_id_lists(id_lists)
+        raw, out_off, st = detok().decode_csr(ids, id_off, strip_space=strip)
+        bad = np.flatnonzero(st)
+        if len(bad):
+            raise DptError("decode: string %d has an id outside the vocabulary" % int(bad[0]))
+        blob, o = raw.tobytes(), out_off.tolist()
+        return [blob[o[s]:o[s + 1]].decode("utf-8", "replace") for s in range(len(id_lists))]
+
+    def batch_roundtrip(texts) -> List[Optional[int]]:
+        texts = list(texts)
+        id_lists = encode_many(texts)   # the encode exactly as ``batch`` does it, with its exceptions
+        ids, id_off = _pack_id_lists(id_lists)
+        text, offs = pack_strings(texts)
+        rt, fd = detok().roundtrip_csr(text, offs, ids, id_off, strip_space=strip)
+        bad = np.flatnonzero((rt != _dpt.RT_EQUAL) & (rt != _dpt.RT_DIFFERS))
+        if len(bad):
+            raise DptError("round trip: string %d has an id outside the vocabulary (status %d)" % (int(bad[0]), int(rt[bad[0]])))
+        return [None if v == _dpt.RT_EQUAL else d for v, d in zip(rt.tolist(), fd.tolist())]
+
+    return decode_batch, batch_roundtrip
+
+
 def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
     t2i: Dict[str, int] = dict(llama_tokenizer.get_vocab())
     vocab_bidict = _InverseDict(t2i)
@@ -234,6 +312,14 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
         # reference tokenizer_utils.py:82-84: drop the 4-character "<s> " prefix
         return llama_tokenizer.decode(encoding)[4:]
 
+    # SentencePiece's own decode for a batch in one launch: BOS decodes to nothing, the dummy-prefix space
+    # is dropped.  The round trip compares with the ORIGINAL text in both modes.
+    decode_batch, batch_roundtrip = _decode_surface(
+        lambda: Detok(t2i, "sp", [b for b in [_bos_id(llama_tokenizer)] if b is not None], _device()), True, encode_many)
+    decode_batch.__doc__ = _DECODE_BATCH_DOC % "SentencePiece's"
+    batch_roundtrip.__doc__ = _ROUNDTRIP_DOC
+    decode_dp_tokenization.batch = decode_batch
+    dp_tokenize.batch_roundtrip = batch_roundtrip
     dp_tokenize.batch = encode_many
     dp_tokenize.batch_spans = spans_many
     dp_tokenize.engine = engine
@@ -301,6 +387,14 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
     def decode_dp_tokenization(encoding: List[int]):
         return bloom_tokenizer.decode(encoding)   # reference :179-181
 
+    # ByteLevel's own decode (the alphabet back to bytes, nothing stripped); the round trip compares with
+    # the UTF-8 of the input
+    decode_batch, batch_roundtrip = _decode_surface(lambda: Detok(dict(vocab_to_index), "bytelevel", (), _device()), False,
+                                                    encode_many)
+    decode_batch.__doc__ = _DECODE_BATCH_DOC % "ByteLevel's"
+    batch_roundtrip.__doc__ = _ROUNDTRIP_DOC
+    decode_dp_tokenization.batch = decode_batch
+    dp_tokenize.batch_roundtrip = batch_roundtrip
     dp_tokenize.batch = encode_many
     dp_tokenize.batch_spans = spans_many
     dp_tokenize.engine = engine

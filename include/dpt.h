@@ -20,6 +20,8 @@
  *                        reference main_analyze_s2orc.py:269-297 (len(dp_tokenize(x)))
  *   dpt_token_spans    <- the probe's per-word comparison, reference main_analyze_s2orc.py:275-290
  *                        (dp_tokenize on every pre-token, to tell which words the DP shortened)
+ *   dpt_decode, dpt_roundtrip <- the decode_dp_tokenization closure, reference packages/tokenizer_utils.py:82-84,
+ *                        :176-179, and the caller's round-trip assert, main_analyze_s2orc.py:84-87
  *   dpt_hist_allreduce <- SURVEY.md §8(b)/(e): the one collective of a sharded corpus (the
  *                        reference is single-process, llama_s2orc.sh:10; no call site there)
  *
@@ -240,6 +242,85 @@ int dpt_token_spans_host(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_t
                          const uint64_t *str_off, const uint8_t *cut_mask, uint64_t n_str, const int32_t *ids,
                          const uint64_t *id_off, const int32_t *status, uint32_t *tok_end, uint32_t *tok_word,
                          int32_t *span_status);
+
+/*
+ * Decode: ids back to bytes, and the round-trip check of an encoded batch -- the second closure of the
+ * reference's factories, decode_dp_tokenization (reference packages/tokenizer_utils.py:82-84, :176-179: the
+ * tokenizer's own decode), and the assert its caller runs on every example, decode_dp_tokenization(
+ * dp_tokenize(abstract)) == abstract (reference main_analyze_s2orc.py:84-87).  Added within ABI 6
+ * (DPT_ABI_VERSION unchanged): a binding that may meet an older libdpt.so probes for the symbols.
+ *
+ * A dpt_detok is the decode table of a vocabulary under one rule: what every id decodes to.  It is built
+ * from dpt_vocab_create's first four arguments (later duplicates win, empty strings are ignored, as there;
+ * of two tokens on one id the later one wins), a rule and the ids that decode to nothing:
+ *   DPT_DETOK_PIECES     the token's bytes as they are: a string's decode is its atom-expanded text, for
+ *                        PRESPLIT / ATOMS ids exactly the text that was encoded
+ *   DPT_DETOK_SP         SentencePiece's decode: every U+2581 (E2 96 81) becomes ' '; a token that is exactly
+ *                        <0xNN> (6 bytes, two upper-case hex digits) becomes the byte NN.  The output is
+ *                        bytes: no UTF-8 validation or repair
+ *   DPT_DETOK_BYTELEVEL  every code point of the token goes back through the GPT-2 / ByteLevel
+ *                        bytes-to-unicode alphabet (256 code points: the printable Latin-1 bytes 21..7E,
+ *                        A1..AC, AE..FF stand for themselves, the other 68 bytes are U+0100.. in byte
+ *                        order); a token with a code point outside the alphabet keeps its UTF-8 bytes
+ *   skip_ids[0..n_skip)  decode to nothing under every rule (BOS and the like)
+ * DPT_E_VOCAB when the ids (skip ids included) are spread over more than 8 * n_tokens + 65536 values: the
+ * table is dense, one 8-byte entry per id.  Immutable after creation; may be shared by threads and streams.
+ *
+ * ids, id_off and status are what dpt_encode wrote (or any ids in that layout): token k of string s is
+ * ids[id_off[s] - id_off[0] + k]; id_off[0] need not be 0.  status is nullable: all 0.  A string with
+ * status[s] != 0 has no ids: it decodes to nothing, and the only thing written for it is that status
+ * (dec_status[s], rt[s]; out_len[s] = 0).  flags: DPT_DECODE_STRIP_SPACE drops the string's first decoded
+ * byte when it is ' ' (SentencePiece's dummy prefix, the word mark of RAW mode's first character).
+ *   dpt_decode_sizes  out_len[s] = the decoded bytes of string s (the caller's prefix sum gives out_off)
+ *   dpt_decode        the bytes of string s at out[out_off[s] - out_off[0] ..]; out_off[0] need not be 0, no
+ *                     alignment is assumed.  dec_status[s] = 0, or DPT_STATUS_INTERNAL when an id of s lies
+ *                     outside the table or no token has it, or when the decode does not fill
+ *                     [out_off[s], out_off[s+1]) exactly; such a string's bytes (and its out_len) are
+ *                     unspecified, every other string is exact, and every store stays inside the string's own
+ *                     output range whatever the ids hold
+ *   dpt_roundtrip     compares the decode of string s with text[str_off[s] - str_off[0] ..) without writing
+ *                     it: rt[s] = DPT_RT_EQUAL or DPT_RT_DIFFERS, and first_diff[s] (nullable; written only
+ *                     when rt[s] = DPT_RT_DIFFERS) = the first differing byte offset -- the shorter length
+ *                     when one side is a prefix of the other.  An id without a token gives
+ *                     DPT_STATUS_INTERNAL unless the bytes decoded before it already differ
+ * DEVICE pointers on the table's device; stream-ordered on hip_stream, never synchronise, allocate nothing
+ * and need no dpt_ctx: any number of calls may be in flight on one dpt_detok.  Strings and their decodes
+ * < 4 GiB; id_off, str_off and out_off monotone (the device calls cannot check device-resident offsets).
+ */
+typedef struct dpt_detok dpt_detok;
+#define DPT_DETOK_PIECES 0
+#define DPT_DETOK_SP 1
+#define DPT_DETOK_BYTELEVEL 2
+#define DPT_DECODE_STRIP_SPACE 1
+#define DPT_RT_EQUAL 0
+#define DPT_RT_DIFFERS 5
+int dpt_detok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok, int rule,
+                     const int32_t *skip_ids, uint32_t n_skip, int device, dpt_detok **out);
+int dpt_detok_destroy(dpt_detok *d);
+int dpt_decode_sizes(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint64_t n_str,
+                     int flags, uint64_t *out_len, void *hip_stream);
+int dpt_decode(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint64_t n_str,
+               int flags, uint8_t *out, const uint64_t *out_off, int32_t *dec_status, void *hip_stream);
+int dpt_roundtrip(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                  const uint8_t *text, const uint64_t *str_off, uint64_t n_str, int flags, int32_t *rt,
+                  uint32_t *first_diff, void *hip_stream);
+/* Same with HOST pointers: copy in through the ctx's host-path staging (grows on demand), run, copy out,
+ * synchronise; both check that the offset arrays are monotone (DPT_E_ARG).  dpt_decode_host runs the sizes,
+ * fills out_off[0..n_str] with their prefix sum from 0 -- always -- and, when out_off[n_str] > out_cap,
+ * returns DPT_E_CAP having written no bytes: the caller reads the need from out_off and calls again. */
+int dpt_decode_host(dpt_ctx *c, const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                    uint64_t n_str, int flags, uint8_t *out, uint64_t out_cap, uint64_t *out_off, int32_t *dec_status);
+int dpt_roundtrip_host(dpt_ctx *c, const dpt_detok *d, const int32_t *ids, const uint64_t *id_off, const int32_t *status,
+                       const uint8_t *text, const uint64_t *str_off, uint64_t n_str, int flags, int32_t *rt,
+                       uint32_t *first_diff);
+/* TEST-ONLY, needs no device.  The bytes dpt_detok_create would upload for these arguments, built on the host
+ * (tests/decode_ref.py holds a model of the format).  which: 0 the entries (n_tab pairs of uint32: the piece's
+ * offset in the blob, its length -- 0 for a skipped id -- or 0x80000000 for an id no token has), 1 the blob
+ * (the decoded pieces in id order), 2 DPT_DETOK_SCALAR_INTS int64: id_min, n_tab, blob bytes, longest decoded
+ * piece.  *size = the table's bytes, always; it is copied to out (nullable) when cap >= *size, else DPT_E_CAP. */
+#define DPT_DETOK_SCALAR_INTS 4
+int dpt_debug_detok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok, int rule,
+                          const int32_t *skip_ids, uint32_t n_skip, int which, void *out, uint64_t cap, uint64_t *size);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
