@@ -1,0 +1,142 @@
+// dpt_objects.h -- what the two halves of the C-ABI share: the objects behind its handles, error reporting, and
+// the one encode call both run (dpt_api.cpp: the objects, the workspace and the device-pointer calls;
+// dpt_host.cpp: the host-buffer calls and their staging).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "dpt_internal.h"
+
+struct dpt_vocab : dpt::VocabScalars {
+    int device = 0;
+    int2 *d_slots = nullptr;
+    int32_t *d_ids = nullptr;
+    int16_t *d_pair16 = nullptr;      // C2's pair-id table (dpt::PAIR16_N int16), then phase A0's byte-pair table (65536 uint2), then the token hash
+    int4 *d_slots4 = nullptr;         // {base | TERM, check, id, child filter} for the lane kernel
+    // dpt_token_spans: byte length per id - id_min (0: no token has this id); null when the ids are too
+    // sparse for a dense table or two tokens of different length share an id (the spans calls: DPT_E_VOCAB)
+    uint16_t *d_tok_len = nullptr;
+};
+
+// The device copy of a decode table (dpt_detok.cpp build_detok_tables).
+struct dpt_detok {
+    int device = 0;
+    uint2 *d_tab = nullptr;     // {offset in the blob, length | dpt::DETOK_NONE} per id - id_min
+    uint8_t *d_blob = nullptr;  // the decoded pieces (never null: an empty blob is one byte)
+    int32_t id_min = 0;
+    uint32_t n_tab = 0;
+};
+
+struct dpt_ctx {
+    int device = 0;
+    // workspace of the device path (ensure_workspace)
+    int32_t *staging32 = nullptr;     // ids staged as int32 (vocabularies with an id outside 0..32767)
+    uint64_t cap32 = 0;
+    int16_t *staging16 = nullptr;     // ids staged as int16 (vocabularies with ids16)
+    uint64_t cap16 = 0;
+    uint8_t *arena = nullptr;         // the unbounded pass's scratch, 20 bytes per input byte it holds
+    uint64_t arena_cap = 0;           // input bytes
+    bool arena_reserved = false;      // dpt_ctx_reserve_vocab set it: the encode path does not resize it
+    uint64_t *counts = nullptr;
+    uint32_t *retry_list = nullptr;
+    uint64_t cap_str = 0;
+    dpt::CounterBlock *ctr = nullptr; // the counter block (dpt::CTR_ALLOC_BYTES)
+    uint8_t *wsl_scratch = nullptr;   // word lists of the 256-byte pass (dpt::wsl_scratch_bytes)
+    uint4 *pend = nullptr;            // pending residual tokens of the 256-byte pass (dpt::pend_scratch_bytes)
+    // two parity regions R0, R1 of batch lines (dpt::BS_LINE u64 per 256-string batch: its sum in the
+    // first), then the batch prefixes of the scan path (cap_batches u64): the call of parity P uses R_P
+    // and -- fold calls -- zeroes R_(1-P) for the next one (the parity flips); between calls R_parity
+    // is all zero.  See dpt_internal.h fin_fold and BS_LINE.
+    unsigned long long *flags = nullptr;
+    uint64_t cap_batches = 0;
+    int flag_parity = 0;
+    unsigned max_blocks = 0;
+    // host paths (dpt_host.cpp Stager alone touches them): one device buffer in and one out (dpt_host_layout.h), each
+    // mirrored by a pinned host buffer so every copy is one async DMA
+    uint8_t *d_in = nullptr, *p_in = nullptr, *d_out = nullptr, *p_out = nullptr;
+    uint8_t *pd_in = nullptr, *pd_out = nullptr;   // p_in / p_out as the device addresses them (zero-copy calls), or null
+    uint64_t cap_in = 0, cap_pin_in = 0, cap_out = 0, cap_pin_out = 0;
+    // dpt_ctx_set_histogram: folded into the next encode's finish pass
+    int64_t *hist = nullptr;
+    uint32_t hist_bins = 0;
+    bool hist_overwrite = false;
+    // profiling
+    bool profile = false;
+    std::vector<hipEvent_t> events;   // groups of 4 per call
+    uint64_t launches = 0;
+    // test-only (dpt_ctx_debug_counter_bias): every call starts the unbounded pass's arena counter and the
+    // far-pair counter at this value, the arena and far pointers passed down shifted by it
+    uint64_t counter_bias = 0;
+};
+
+namespace dpt {
+
+// (the thread's message itself lives in dpt_api.cpp: set_last_error)
+inline int fail(int code, const std::string &msg) { return set_last_error(msg), code; }
+inline int hip_fail(hipError_t e, const char *what) { return fail(DPT_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// Device buffer of at least `need` elements: exact on first allocation, +25 % when it grows.  A buffer that
+// already holds `need` is left where it is.
+template <typename T>
+hipError_t grow(T **p, uint64_t *cap, uint64_t need) {
+    if (need <= *cap && *p) return hipSuccess;
+    uint64_t n = need < 64 ? 64 : need;
+    if (*cap) n += n / 4;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
+    if (e == hipSuccess) *cap = n;
+    return e;
+}
+
+// What an encode call and a host-path call both name (a member left at its default is absent): the argument
+// list the five encode entry points share, the rest by name.
+struct CsrCall {
+    int mode_flags = DPT_MODE_RAW;   // DPT_MODE_* | DPT_FLAG_*
+    const uint8_t *text = nullptr, *cut_mask = nullptr;
+    const uint64_t *str_off = nullptr;
+    uint64_t n_bytes = 0, n_str = 0, ids_cap = 0, far_cap = 0;
+    int32_t *ids = nullptr, *status = nullptr, *capped_len = nullptr;
+    uint64_t *id_off = nullptr, *edges = nullptr, *far = nullptr;   // dpt_dp_host*: the per-atom-end masks, far_cap far edge pairs
+    void set(int mode_flags_, const uint8_t *text_, uint64_t n_bytes_, const uint64_t *str_off_, const uint8_t *cut_mask_,
+             uint64_t n_str_, int32_t *status_, int32_t *capped_len_, int32_t *ids_ = nullptr, uint64_t ids_cap_ = 0) {
+        mode_flags = mode_flags_; text = text_; n_bytes = n_bytes_; str_off = str_off_; cut_mask = cut_mask_; n_str = n_str_;
+        status = status_; capped_len = capped_len_; ids = ids_; ids_cap = ids_cap_;
+    }
+};
+// One encode call as its caller sees it (encode_impl): DEVICE pointers.
+struct EncodeRequest : CsrCall {
+    hipStream_t stream = nullptr;
+    uint64_t *padded_counts = nullptr;   // dpt_encode_padded: the caller's counts (id_off is not used)
+    bool dev_call = false;               // dpt_encode itself: it alone takes an armed histogram (dpt_ctx_set_histogram_ex)
+    uint64_t *ctr_snap = nullptr;        // host path: where the counter block's reset copies its first 64 bytes
+    bool no_fallback = false;            // host path: no string needs the 2048-byte or unbounded pass
+};
+
+// dpt_api.cpp
+int ensure_workspace(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint64_t n_str, uint64_t long_bytes, bool staging = true);
+int encode_impl(dpt_ctx *c, const dpt_vocab *v, const EncodeRequest &r);
+// A spans / decode launch from its caller's arguments (v null: without the vocabulary's part; decode_check adds
+// the table's), and the argument checks the device and the host form of a call share.
+SpansLaunch spans_args(const dpt_vocab *v, int mode, const uint8_t *text, const uint64_t *str_off, const uint8_t *cut_mask,
+                       uint64_t n_str, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint32_t *tok_end,
+                       uint32_t *tok_word, int32_t *span_status);
+int spans_check(const SpansLaunch &p, const dpt_vocab *v, uint64_t n_bytes);
+extern const char *const NO_TOK_LEN;   // the spans calls' DPT_E_VOCAB message
+DecodeLaunch decode_args(int kind, const int32_t *ids, const uint64_t *id_off, const int32_t *status, uint64_t n_str);
+int decode_check(DecodeLaunch *p, const dpt_detok *d, int flags);
+
+}  // namespace dpt

@@ -24,6 +24,7 @@ DPT_FLAG_LEN_ONLY = 0x20
 STATUS_OK, STATUS_NO_TOKENIZATION, STATUS_EMPTY_WORD, STATUS_TOO_LONG, STATUS_INTERNAL = range(5)
 DPT_DETOK_PIECES, DPT_DETOK_SP, DPT_DETOK_BYTELEVEL = range(3)
 DPT_DECODE_STRIP_SPACE = 1
+DPT_HOST_LAYOUT_SEGS = 7
 RT_EQUAL, RT_DIFFERS = 0, 5
 
 
@@ -104,6 +105,9 @@ def lib():
     L.dpt_ctx_debug_counter_bias.argtypes = [P, U64]
     L.dpt_debug_launch_plan.argtypes = [I32] * 8 + [U64, I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(I32)]
     L.dpt_debug_vocab_table.argtypes = [P, P, P, ctypes.c_uint32, I32, P, U64, ctypes.POINTER(U64)]
+    if hasattr(L, "dpt_debug_host_layout"):   # (came within ABI 6, like the decode calls)
+        L.dpt_debug_host_layout.argtypes = [I32, U64, U64, U64, I32, U64, ctypes.POINTER(U64)]
+        L.dpt_debug_host_layout.restype = I32
     L.dpt_rccl_get_unique_id.argtypes = [P]
     L.dpt_rccl_comm_create.argtypes = [P, I32, I32, I32, ctypes.POINTER(P)]
     L.dpt_rccl_comm_destroy.argtypes = [P]
@@ -136,5 +140,6 @@ EXPORTED = ["dpt_last_error", "dpt_abi_version", "dpt_vocab_create", "dpt_vocab_
             "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram", "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex",
             "dpt_token_spans", "dpt_token_spans_host",
             "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias", "dpt_debug_launch_plan",
-            "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"] + \
+            "dpt_debug_vocab_table", "dpt_debug_host_layout", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy",
+            "dpt_hist_allreduce"] + \
     list(DECODE_CALLS)

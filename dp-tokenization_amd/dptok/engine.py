@@ -142,20 +142,29 @@ def raise_for_status(status: int, text: str = "") -> None:
     raise DptError("engine internal error (status %d)" % status)
 
 
+def pack_vocab(t2i: Dict[str, int]):
+    """``t2i`` as dpt_vocab_create and dpt_detok_create take it -> (blob u8: the tokens' UTF-8 bytes back to
+    back and a NUL, off u64[n+1], ids int32[n], n)."""
+    enc = [encode_utf8(t) for t in t2i]
+    off = np.zeros(len(enc) + 1, dtype=np.uint64)
+    if enc:
+        off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
+    return blob, off, np.array(list(t2i.values()), dtype=np.int32), len(enc)
+
+
+def _decode_flags(strip_space: bool) -> int:
+    return _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0
+
+
 class Vocab:
     """Device-resident vocabulary (double-array byte trie) built from ``t2i``."""
 
     def __init__(self, t2i: Dict[str, int], device: int = 0):
         L = _lib.lib()
-        toks = list(t2i.keys())
-        enc = [encode_utf8(t) for t in toks]
-        off = np.zeros(len(enc) + 1, dtype=np.uint64)
-        if enc:
-            off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
-        ids = np.array([t2i[t] for t in toks], dtype=np.int32)
+        blob, off, ids, n = pack_vocab(t2i)
         h = ctypes.c_void_p()
-        check(L.dpt_vocab_create(_ptr(blob), _ptr(off), _ptr(ids), len(toks), device, ctypes.byref(h)), "dpt_vocab_create")
+        check(L.dpt_vocab_create(_ptr(blob), _ptr(off), _ptr(ids), n, device, ctypes.byref(h)), "dpt_vocab_create")
         self.handle = h
         self.device = device
         self.t2i = t2i
@@ -567,16 +576,10 @@ class Detok:
         L = _lib.lib()
         if not _lib.has_decode():
             raise DptError(f"{_lib.LIB_PATH} was built before the decode calls (no dpt_detok_create): rebuild it")
-        toks = list(t2i.keys())
-        enc = [encode_utf8(t) for t in toks]
-        off = np.zeros(len(enc) + 1, dtype=np.uint64)
-        if enc:
-            off[1:] = np.cumsum([len(e) for e in enc], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
-        ids = np.array([t2i[t] for t in toks], dtype=np.int32)
+        blob, off, ids, n = pack_vocab(t2i)
         skip = np.array(list(skip_ids), dtype=np.int32)
         h = ctypes.c_void_p()
-        check(L.dpt_detok_create(_ptr(blob), _ptr(off), _ptr(ids), len(toks), DETOK_RULES[rule],
+        check(L.dpt_detok_create(_ptr(blob), _ptr(off), _ptr(ids), n, DETOK_RULES[rule],
                                  _ptr(skip) if len(skip) else None, len(skip), device, ctypes.byref(h)), "dpt_detok_create")
         self.handle = h
         self.device = device
@@ -624,7 +627,7 @@ class Detok:
         bytes[out_off[s]:out_off[s+1]]; dec_status[s] is status[s], or 4 when an id of s has no token (its
         bytes are then unspecified)."""
         ids, id_off, status, n = self._csr(ids, id_off, status)
-        flags = _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0
+        flags = _decode_flags(strip_space)
         out_off = np.zeros(n + 1, dtype=np.uint64)
         dec_status = np.zeros(max(n, 1), dtype=np.int32)
         cap = 4 * len(ids) + 64   # (most pieces are shorter; a longer decode answers DPT_E_CAP with its need)
@@ -657,7 +660,7 @@ class Detok:
         base = int(offs[0])
         check(_lib.lib().dpt_roundtrip_host(self._ctx(), self.handle, _ptr(ids), _ptr(id_off), _ptr(status),
                                             _ptr(text[base:] if base else text), _ptr(offs), n,
-                                            _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, _ptr(rt), _ptr(fd)),
+                                            _decode_flags(strip_space), _ptr(rt), _ptr(fd)),
               "dpt_roundtrip_host")
         rt = rt[:n]
         return rt, np.where(rt == _lib.RT_DIFFERS, fd[:n].astype(np.int64), -1)
@@ -669,7 +672,7 @@ class Detok:
         addresses, stream-ordered, no sync, no workspace."""
         check(_lib.lib().dpt_decode_sizes(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
                                           ctypes.c_void_p(status_ptr or None), n_str,
-                                          _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, ctypes.c_void_p(out_len_ptr),
+                                          _decode_flags(strip_space), ctypes.c_void_p(out_len_ptr),
                                           ctypes.c_void_p(stream or None)), "dpt_decode_sizes")
 
     def decode_device(self, ids_ptr: int, idoff_ptr: int, n_str: int, out_ptr: int, out_off_ptr: int, dec_status_ptr: int,
@@ -678,7 +681,7 @@ class Detok:
         prefix sum of ``sizes_device``'s lengths from any start), dec_status int32 per string."""
         check(_lib.lib().dpt_decode(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
                                     ctypes.c_void_p(status_ptr or None), n_str,
-                                    _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0, ctypes.c_void_p(out_ptr or None),
+                                    _decode_flags(strip_space), ctypes.c_void_p(out_ptr or None),
                                     ctypes.c_void_p(out_off_ptr), ctypes.c_void_p(dec_status_ptr),
                                     ctypes.c_void_p(stream or None)), "dpt_decode")
 
@@ -688,6 +691,6 @@ class Detok:
         only where rt is RT_DIFFERS) of the decode against text / offsets (the encode's own)."""
         check(_lib.lib().dpt_roundtrip(self.handle, ctypes.c_void_p(ids_ptr), ctypes.c_void_p(idoff_ptr),
                                        ctypes.c_void_p(status_ptr or None), ctypes.c_void_p(text_ptr or None),
-                                       ctypes.c_void_p(off_ptr), n_str, _lib.DPT_DECODE_STRIP_SPACE if strip_space else 0,
+                                       ctypes.c_void_p(off_ptr), n_str, _decode_flags(strip_space),
                                        ctypes.c_void_p(rt_ptr), ctypes.c_void_p(first_diff_ptr or None),
                                        ctypes.c_void_p(stream or None)), "dpt_roundtrip")

@@ -378,6 +378,17 @@ int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int edges, int 
 int dpt_debug_vocab_table(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok,
                           int which, void *out, uint64_t cap, uint64_t *size);
 
+/* TEST-ONLY, needs no device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  Where a host-buffer call keeps
+ * its arrays in the ctx's staging buffers (tests/test_host_layout.py holds the rules).  call: 0 dpt_encode_host /
+ * dpt_dp_host*, 1 dpt_token_spans_host, 2 dpt_decode_host (n_bytes: the decoded bytes; 0 for its sizes pass),
+ * 3 dpt_roundtrip_host; flags: bits 1 a cut mask, 2 tok_word, 4 edges; far_pairs: the far edge list's room.
+ * out: DPT_HOST_LAYOUT_INTS uint64 -- for the in side, then the out side: the number of segments, the side's
+ * bytes, then DPT_HOST_LAYOUT_SEGS x {offset, payload bytes, slack bytes}, the segments in their order. */
+#define DPT_HOST_LAYOUT_SEGS 7
+#define DPT_HOST_LAYOUT_INTS (2 * (2 + 3 * DPT_HOST_LAYOUT_SEGS))
+int dpt_debug_host_layout(int call, uint64_t n_bytes, uint64_t n_str, uint64_t n_tok, int flags, uint64_t far_pairs,
+                          uint64_t *out);
+
 /*
  * Multi-GPU without torch (ABI 6; SURVEY.md §8(b) dpt_hist_allreduce, §8(e) "direct RCCL with a
  * file-store unique id").  One process per GPU: rank 0 calls dpt_rccl_get_unique_id and hands the

@@ -1,5 +1,5 @@
 """Small host-path calls (round 4): dpt_encode_host skips the 2048-byte and unbounded passes' launches
-when its own scan of the text shows no string can need them (dpt_api.cpp no_fallback_needed), and
+when its own scan of the text shows no string can need them (dpt_host.cpp no_fallback_needed), and
 brings the counter block back inside its one device-to-host copy.  The scan must agree with the
 kernels' routing exactly, so the cases sit on both sides of every limit -- words of 256 / 257 bytes
 (raw and pre-split), word starts exactly 256 bytes apart, atoms of 4 / 5 bytes (malformed UTF-8),
@@ -103,7 +103,7 @@ def test_one_string_calls(vocabs):
 
 
 def test_zero_copy_calls_after_the_spans_path_moved_the_pinned_buffers(vocabs):
-    """The two host paths share one pair of pinned staging buffers (dpt_api.cpp stage_host), and the
+    """The host paths share one pair of pinned staging buffers (dpt_host.cpp Stager::stage), and the
     one-string zero-copy call addresses them from the device: a spans host call that outgrows them moves
     them, and the next one-string encode must look their device addresses up again.  One Encoder: a
     one-string call (4096-byte pinned buffers, addresses looked up), a dpt_token_spans_host call on 64
@@ -145,6 +145,69 @@ def test_zero_copy_calls_after_the_spans_path_moved_the_pinned_buffers(vocabs):
         assert np.array_equal(g, r)
     for s in ("", "plain ascii words", "naïve 中文 😀 end"):
         one(s, "after encode_csr_spans")
+    text, offs, cut, _, _ = pack_presplit_words([["▁pre", "▁split", "words", "▁é中"]])
+    for g, r, part in zip(enc.encode_csr(text, offs, mode="presplit", cut_mask=cut),
+                          orc.encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut), ("ids", "offsets", "status", "capped")):
+        assert np.array_equal(g, r), ("presplit", part)
+
+
+def test_zero_copy_calls_between_the_decode_roundtrip_and_spans_paths(vocabs):
+    """Every host path of one ctx stages in the same buffers (dpt_host.cpp Stager), and two rules hold them
+    together: a side that does not grow stays where it is, and a one-string zero-copy encode looks the pinned
+    buffers' device addresses up again after a call moved them.  dpt_decode_host is the one call that stages
+    twice -- its out side grows, and moves, between the sizes pass and the decode pass while the in side, ids
+    included, must stay put.  One Encoder's ctx throughout, the decode calls through the C-ABI with that ctx: a
+    one-string encode (4096-byte pinned buffers, addresses looked up), dpt_decode_host on 64 strings of 200 bytes
+    whose ids come from the oracle (so no encode call has grown the buffers), one-string encodes,
+    dpt_roundtrip_host on the same batch, one-string encodes, dpt_token_spans_host, one-string encodes and a
+    PRESPLIT one -- encodes and spans exact against the oracle and tests/spans_ref.py, the decode against
+    tests/decode_ref.py, every round-trip verdict RT_EQUAL."""
+    import decode_ref
+    import spans_ref
+    from dptok import Detok, Encoder, Vocab, _lib, pack_strings, synth
+    from dptok.engine import pack_presplit_words
+    from oracle import oracle
+    t2i = vocabs["llama32k"]
+    enc, orc, detok = Encoder(Vocab(t2i, 0)), oracle.OracleVocab(t2i), Detok(t2i, "sp")
+    L, STRIP = _lib.lib(), _lib.DPT_DECODE_STRIP_SPACE
+
+    def ones(what, strs=("", "plain ascii words", "naïve 中文 😀 end")):
+        for s in strs:
+            text, offs = pack_strings([s])
+            for g, r, part in zip(enc.encode_csr(text, offs), orc.encode_csr(text, offs), ("ids", "offsets", "status", "capped")):
+                assert np.array_equal(g, r), (what, part, s[:30])
+
+    ones("before", ("the first call",))
+    text, offs = pack_strings(synth.unpack(*synth.random_ascii_corpus(64, 200, seed=13)))
+    ids, id_off, st, _ = orc.encode_csr(text, offs)
+    ids, id_off, st = (np.ascontiguousarray(a, dtype=t) for a, t in ((ids, np.int32), (id_off, np.uint64), (st, np.int32)))
+    n, n_tok, n_bytes = len(st), len(ids), int(offs[-1])
+    assert n == 64 and n_bytes > 4096 and 4 * n_tok > 4096 and not st.any()   # more than the first buffers, in and out
+    by_id = decode_ref.pieces_by_id(decode_ref.pairs_of(t2i), "sp")
+    wraw, woff, wst, ok = decode_ref.expected_decode(by_id, ids, id_off, st, strip=True)
+    assert ok.all() and len(wraw) == n_bytes and 8 * n + 4 * n + 16 < 4096   # the sizes pass fits the first out buffer, the bytes do not
+
+    out, out_off, dst = np.zeros(n_bytes + 64, np.uint8), np.full(n + 1, 7, np.uint64), np.full(n, -1, np.int32)
+    _lib.check(L.dpt_decode_host(enc.handle, detok.handle, ids.ctypes.data, id_off.ctypes.data, st.ctypes.data, n, STRIP,
+                                 out.ctypes.data, len(out), out_off.ctypes.data, dst.ctypes.data), "dpt_decode_host")
+    assert np.array_equal(out_off, woff) and np.array_equal(dst, wst) and np.array_equal(out[:n_bytes], wraw)
+    assert out[:n_bytes].tobytes() == text[:n_bytes].tobytes()
+    ones("after the decode call")
+
+    rt, fd = np.full(n, -1, np.int32), np.zeros(n, np.uint32)
+    _lib.check(L.dpt_roundtrip_host(enc.handle, detok.handle, ids.ctypes.data, id_off.ctypes.data, st.ctypes.data,
+                                    text.ctypes.data, offs.ctypes.data, n, STRIP, rt.ctypes.data, fd.ctypes.data), "dpt_roundtrip_host")
+    assert (rt == _lib.RT_EQUAL).all()
+    ones("after the round trip")
+
+    ref = spans_ref.expected(t2i, "raw", text, offs, None, ids, id_off, st)
+    end, word, ss = np.zeros(n_tok, np.uint32), np.zeros(n_tok, np.uint32), np.full(n, -1, np.int32)
+    _lib.check(L.dpt_token_spans_host(enc.handle, enc.vocab.handle, _lib.DPT_MODE_RAW, text.ctypes.data, n_bytes,
+                                      offs.ctypes.data, None, n, ids.ctypes.data, id_off.ctypes.data, st.ctypes.data,
+                                      end.ctypes.data, word.ctypes.data, ss.ctypes.data), "dpt_token_spans_host")
+    for g, r in zip((end, word, ss), ref):
+        assert np.array_equal(g, r)
+    ones("after the spans call")
     text, offs, cut, _, _ = pack_presplit_words([["▁pre", "▁split", "words", "▁é中"]])
     for g, r, part in zip(enc.encode_csr(text, offs, mode="presplit", cut_mask=cut),
                           orc.encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut), ("ids", "offsets", "status", "capped")):

@@ -64,7 +64,7 @@ def test_arena_overflow_host_path_reruns(vocabs):
     from oracle import oracle
     rng = np.random.default_rng(4)
     # long strings interleaved with short ones: only the long ones overflow and run again, and
-    # their ids are spliced between the short strings' (dpt_api.cpp rerun_too_long)
+    # their ids are spliced between the short strings' (dpt_host.cpp rerun_too_long)
     texts = []
     for k, t in enumerate(_long_batch(rng, n=30)):
         texts += [t, "x y z" if k % 2 else "", " ab\ncd"]
