@@ -48,7 +48,7 @@ int dpt::ensure_workspace(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint
     if (need16 && (e = grow(&c->staging16, &c->cap16, n_bytes + 8)) != hipSuccess) return hip_fail(e, "hipMalloc(staging16)");
     if (need32 && (e = grow(&c->staging32, &c->cap32, n_bytes + 8)) != hipSuccess) return hip_fail(e, "hipMalloc(staging32)");
     // long_bytes = 0 (the encode path): the default size, unless the caller reserved the arena -- a
-    // reserved arena is left alone, so a reserved call never reallocates (capture-safe, dpt.h)
+    // reserved arena is left alone, so a reserved call never reallocates (dpt.h)
     const uint64_t lb = long_bytes ? long_bytes : default_long_bytes(n_bytes);
     if (!c->arena || (lb > c->arena_cap && (long_bytes || !c->arena_reserved))) {
         uint64_t cap = c->arena_cap ? c->arena_cap * ARENA_PER_BYTE : 0;

@@ -512,8 +512,11 @@ class Encoder:
               "dpt_token_spans")
 
     def reserve(self, n_bytes: int, n_str: int, long_bytes: int = 0) -> None:
-        """Pre-size the workspace for this vocabulary's staging width (a later call of that size is
-        capture-safe); ``long_bytes``: input bytes the unbounded pass holds per call (0: default)."""
+        """Pre-size the workspace for this vocabulary's staging width (a later call of at most that size
+        allocates nothing and does not synchronise); ``long_bytes``: input bytes the unbounded pass holds
+        per call (0: default).  Not enough to record ``encode_device`` into a HIP graph
+        (``torch.cuda.graph``): the engine keeps host state in step with every call, which a replay does
+        not see -- capture is not supported."""
         check(_lib.lib().dpt_ctx_reserve_vocab(self.handle, self.vocab.handle, n_bytes, n_str, long_bytes),
               "dpt_ctx_reserve_vocab")
 

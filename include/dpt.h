@@ -105,7 +105,12 @@ int dpt_vocab_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const in
 int dpt_vocab_destroy(dpt_vocab *v);
 int dpt_vocab_stats_get(const dpt_vocab *v, dpt_vocab_stats *out);
 
-/* Workspace on `device` (grows on demand; dpt_ctx_reserve makes a later call capture-safe).
+/* Workspace on `device` (grows on demand; after dpt_ctx_reserve* a call of at most the reserved size
+ * allocates nothing and does not synchronise).  NOT capture-safe: dpt_encode keeps host state in step
+ * with every call (which of two batch-sum regions a call of 257..524288 strings uses, the armed
+ * histogram, profiling events), and a replayed graph does not see the host -- its second launch would
+ * write wrong id_off and misplaced ids.  Do not record dpt_encode / dpt_encode_padded into a HIP graph
+ * (hipStreamBeginCapture, torch.cuda.graph); DESIGN.md section 8 has the details.
  * Device-path workspace per call of n_bytes / n_str: the staged ids (2 bytes per input byte when
  * every vocabulary id is in 0..32767, else 4), 16 bytes per string, and the unbounded pass's arena
  * (20 bytes per input byte it holds; by default max(4 MiB, n_bytes/32) input bytes, at most n_bytes). */

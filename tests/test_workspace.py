@@ -81,7 +81,7 @@ def test_arena_overflow_host_path_reruns(vocabs):
 
 def test_reserved_arena_is_not_resized_by_encode(vocabs):
     """An explicitly reserved arena stays as reserved on the device path (no reallocation inside a
-    reserved call: capture-safe), even when the call's default would be larger."""
+    reserved call, include/dpt.h), even when the call's default would be larger."""
     torch = pytest.importorskip("torch")
     from dptok import Encoder, Vocab, synth
     enc = Encoder(Vocab(vocabs["llama32k"], 0))
