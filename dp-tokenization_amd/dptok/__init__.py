@@ -2,14 +2,17 @@
 
 Public surface:
     Vocab, Encoder          batch engine (engine.py)
-    Detok                   ids back to bytes and the round-trip check (engine.py)
+    Detok                   ids back to bytes and the round-trip check (detok.py)
+    pack_strings, TokenSpans  host arrays in and out of the engine (pack.py, pure numpy)
     dp_tokenize_batch       List[str] -> List[List[int]] for a t2i vocabulary
     synth                   synthetic vocabularies/corpora of the BASELINE configs
 The reference-compatible names (dp_tokenize_llama, compute_shortest_tokenizations, ...)
 live in the sibling ``packages`` / ``inspect_tokenizer`` modules of this directory.
 """
 from ._lib import DptError, RT_DIFFERS, RT_EQUAL, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
-from .engine import Detok, Encoder, TokenSpans, Vocab, pack_strings, raise_for_status
+from .detok import Detok
+from .engine import Encoder, Vocab, raise_and_collect, raise_for_status
+from .pack import TokenSpans, pack_strings
 
 __all__ = ["Vocab", "Encoder", "Detok", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
            "STATUS_OK", "STATUS_NO_TOKENIZATION", "STATUS_EMPTY_WORD", "STATUS_TOO_LONG", "STATUS_INTERNAL"]
@@ -36,10 +39,5 @@ def dp_tokenize_batch(texts, t2i, device: int = 0, raise_errors: bool = True):
     the reference's ``dp_tokenize`` closure (packages/tokenizer_utils.py:66-80).
     The vocabulary is uploaded once per ``t2i`` object (keyed by identity and size: a dict that
     is mutated in place without changing its size is not re-read)."""
-    enc = _encoder_for(t2i, device)
-    out = []
-    for t, (ids, st) in zip(texts, enc.encode_strs(texts)):
-        if raise_errors:
-            raise_for_status(st, t)
-        out.append(ids)
-    return out
+    res = _encoder_for(t2i, device).encode_strs(texts)
+    return raise_and_collect(texts, res) if raise_errors else [ids for ids, _ in res]

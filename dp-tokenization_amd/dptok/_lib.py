@@ -44,17 +44,58 @@ U64 = ctypes.c_uint64
 I32 = ctypes.c_int
 U32 = ctypes.c_uint32
 
-# include/dpt.h, "Decode": name -> argument types
-DECODE_CALLS = {
-    "dpt_detok_create": [P, P, P, U32, I32, P, U32, I32, ctypes.POINTER(P)],
-    "dpt_detok_destroy": [P],
-    "dpt_decode_sizes": [P, P, P, P, U64, I32, P, P],
-    "dpt_decode": [P, P, P, P, U64, I32, P, P, P, P],
-    "dpt_roundtrip": [P, P, P, P, P, P, U64, I32, P, P, P],
-    "dpt_decode_host": [P, P, P, P, P, U64, I32, P, U64, P, P],
-    "dpt_roundtrip_host": [P, P, P, P, P, P, P, U64, I32, P, P],
-    "dpt_debug_detok_table": [P, P, P, U32, I32, P, U32, I32, P, U64, ctypes.POINTER(U64)],
+PP, PU64 = ctypes.POINTER(P), ctypes.POINTER(U64)
+
+# include/dpt.h: every exported call, name -> (restype, argtypes).  lib() binds from this table alone.
+CALLS = {
+    "dpt_last_error": (ctypes.c_char_p, []),
+    "dpt_abi_version": (I32, []),
+    "dpt_vocab_create": (I32, [P, P, P, U32, I32, PP]),
+    "dpt_vocab_destroy": (I32, [P]),
+    "dpt_vocab_stats_get": (I32, [P, ctypes.POINTER(VocabStats)]),
+    "dpt_ctx_create": (I32, [I32, PP]),
+    "dpt_ctx_destroy": (I32, [P]),
+    "dpt_ctx_reserve": (I32, [P, U64, U64]),
+    "dpt_ctx_reserve_vocab": (I32, [P, P, U64, U64, U64]),
+    "dpt_ctx_workspace_bytes": (I32, [P, PU64, PU64]),
+    "dpt_ctx_long_need": (I32, [P, PU64, PU64]),
+    "dpt_encode": (I32, [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P, P]),
+    "dpt_encode_host": (I32, [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P]),
+    "dpt_encode_padded": (I32, [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P, P]),
+    "dpt_dp_host": (I32, [P, P, I32, P, U64, P, P, U64, P, P, P]),
+    "dpt_dp_host_far": (I32, [P, P, I32, P, U64, P, P, U64, P, P, P, P, U64, P]),
+    "dpt_token_histogram": (I32, [P, P, U64, P, U32, P]),
+    "dpt_token_spans": (I32, [P, I32, P, U64, P, P, U64, P, P, P, P, P, P, P]),
+    "dpt_token_spans_host": (I32, [P, P, I32, P, U64, P, P, U64, P, P, P, P, P, P]),
+    "dpt_ctx_set_histogram": (I32, [P, P, U32]),
+    "dpt_ctx_set_histogram_ex": (I32, [P, P, U32, I32]),
+    "dpt_ctx_profile": (I32, [P, I32]),
+    "dpt_ctx_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), PU64]),
+    "dpt_ctx_debug_counter_bias": (I32, [P, U64]),
+    "dpt_debug_launch_plan": (I32, [I32] * 8 + [U64, I32, U32, U32, ctypes.POINTER(I32)]),
+    "dpt_debug_vocab_table": (I32, [P, P, P, U32, I32, P, U64, PU64]),
+    "dpt_debug_host_layout": (I32, [I32, U64, U64, U64, I32, U64, PU64]),
+    "dpt_rccl_get_unique_id": (I32, [P]),
+    "dpt_rccl_comm_create": (I32, [P, I32, I32, I32, PP]),
+    "dpt_rccl_comm_destroy": (I32, [P]),
+    "dpt_hist_allreduce": (I32, [P, ctypes.c_size_t, P, P]),
+    # "Decode"
+    "dpt_detok_create": (I32, [P, P, P, U32, I32, P, U32, I32, PP]),
+    "dpt_detok_destroy": (I32, [P]),
+    "dpt_decode_sizes": (I32, [P, P, P, P, U64, I32, P, P]),
+    "dpt_decode": (I32, [P, P, P, P, U64, I32, P, P, P, P]),
+    "dpt_roundtrip": (I32, [P, P, P, P, P, P, U64, I32, P, P, P]),
+    "dpt_decode_host": (I32, [P, P, P, P, P, U64, I32, P, U64, P, P]),
+    "dpt_roundtrip_host": (I32, [P, P, P, P, P, P, P, U64, I32, P, P]),
+    "dpt_debug_detok_table": (I32, [P, P, P, U32, I32, P, U32, I32, P, U64, PU64]),
 }
+# These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
+# ``Detok`` then raises (has_decode).
+OPTIONAL = {"dpt_debug_host_layout", "dpt_detok_create", "dpt_detok_destroy", "dpt_decode_sizes", "dpt_decode",
+            "dpt_roundtrip", "dpt_decode_host", "dpt_roundtrip_host", "dpt_debug_detok_table"}
+EXPORTED = sorted(CALLS)
+# the decode calls: name -> argument types
+DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and name != "dpt_debug_host_layout"}
 
 
 def lib():
@@ -73,50 +114,11 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
-    L.dpt_last_error.restype = ctypes.c_char_p
-    L.dpt_abi_version.restype = I32
-    L.dpt_vocab_create.argtypes = [P, P, P, ctypes.c_uint32, I32, ctypes.POINTER(P)]
-    L.dpt_vocab_destroy.argtypes = [P]
-    L.dpt_vocab_stats_get.argtypes = [P, ctypes.POINTER(VocabStats)]
-    L.dpt_ctx_create.argtypes = [I32, ctypes.POINTER(P)]
-    L.dpt_ctx_destroy.argtypes = [P]
-    L.dpt_ctx_reserve.argtypes = [P, U64, U64]
-    L.dpt_ctx_reserve_vocab.argtypes = [P, P, U64, U64, U64]
-    L.dpt_ctx_workspace_bytes.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
-    L.dpt_ctx_long_need.argtypes = [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]
-    L.dpt_encode.argtypes = [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P, P]
-    L.dpt_encode_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P]
-    L.dpt_encode_padded.argtypes = [P, P, I32, P, U64, P, P, U64, P, U64, P, P, P, P]
-    L.dpt_dp_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P]
-    L.dpt_dp_host_far.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P, P, U64, P]
-    L.dpt_token_histogram.argtypes = [P, P, U64, P, ctypes.c_uint32, P]
-    L.dpt_token_spans.argtypes = [P, I32, P, U64, P, P, U64, P, P, P, P, P, P, P]
-    L.dpt_token_spans_host.argtypes = [P, P, I32, P, U64, P, P, U64, P, P, P, P, P, P]
-    # the decode calls came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still
-    # encodes; ``Detok`` then raises (has_decode)
-    for name, argtypes in DECODE_CALLS.items():
-        if hasattr(L, name):
-            getattr(L, name).argtypes = argtypes
-            getattr(L, name).restype = I32
-    L.dpt_ctx_set_histogram.argtypes = [P, P, ctypes.c_uint32]
-    L.dpt_ctx_set_histogram_ex.argtypes = [P, P, ctypes.c_uint32, I32]
-    L.dpt_ctx_profile.argtypes = [P, I32]
-    L.dpt_ctx_profile_read.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64)]
-    L.dpt_ctx_debug_counter_bias.argtypes = [P, U64]
-    L.dpt_debug_launch_plan.argtypes = [I32] * 8 + [U64, I32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(I32)]
-    L.dpt_debug_vocab_table.argtypes = [P, P, P, ctypes.c_uint32, I32, P, U64, ctypes.POINTER(U64)]
-    if hasattr(L, "dpt_debug_host_layout"):   # (came within ABI 6, like the decode calls)
-        L.dpt_debug_host_layout.argtypes = [I32, U64, U64, U64, I32, U64, ctypes.POINTER(U64)]
-        L.dpt_debug_host_layout.restype = I32
-    L.dpt_rccl_get_unique_id.argtypes = [P]
-    L.dpt_rccl_comm_create.argtypes = [P, I32, I32, I32, ctypes.POINTER(P)]
-    L.dpt_rccl_comm_destroy.argtypes = [P]
-    L.dpt_hist_allreduce.argtypes = [P, ctypes.c_size_t, P, P]
-    for name in ("dpt_vocab_create", "dpt_vocab_destroy", "dpt_vocab_stats_get", "dpt_ctx_create", "dpt_ctx_destroy",
-                 "dpt_ctx_reserve", "dpt_ctx_reserve_vocab", "dpt_ctx_workspace_bytes", "dpt_ctx_long_need", "dpt_encode", "dpt_encode_padded", "dpt_encode_host", "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram",
-                 "dpt_token_spans", "dpt_token_spans_host", "dpt_ctx_set_histogram","dpt_ctx_set_histogram_ex", "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias",
-                 "dpt_debug_launch_plan", "dpt_debug_vocab_table", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy", "dpt_hist_allreduce"):
-        getattr(L, name).restype = I32
+    for name, (restype, argtypes) in CALLS.items():
+        if name in OPTIONAL and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -133,13 +135,16 @@ def check(rc: int, what: str = "") -> None:
         raise DptError(f"{what} failed ({rc}): {msg}")
 
 
-EXPORTED = ["dpt_last_error", "dpt_abi_version", "dpt_vocab_create", "dpt_vocab_destroy", "dpt_vocab_stats_get",
-            "dpt_ctx_create", "dpt_ctx_destroy", "dpt_ctx_reserve", "dpt_ctx_reserve_vocab", "dpt_ctx_workspace_bytes",
-            "dpt_ctx_long_need",
-            "dpt_encode", "dpt_encode_padded", "dpt_encode_host",
-            "dpt_dp_host", "dpt_dp_host_far", "dpt_token_histogram", "dpt_ctx_set_histogram", "dpt_ctx_set_histogram_ex",
-            "dpt_token_spans", "dpt_token_spans_host",
-            "dpt_ctx_profile", "dpt_ctx_profile_read", "dpt_ctx_debug_counter_bias", "dpt_debug_launch_plan",
-            "dpt_debug_vocab_table", "dpt_debug_host_layout", "dpt_rccl_get_unique_id", "dpt_rccl_comm_create", "dpt_rccl_comm_destroy",
-            "dpt_hist_allreduce"] + \
-    list(DECODE_CALLS)
+def new_handle(call: str, *args) -> ctypes.c_void_p:
+    """A handle from the create call ``call``, whose last argument is the handle out."""
+    h = ctypes.c_void_p()
+    check(getattr(lib(), call)(*args, ctypes.byref(h)), call)
+    return h
+
+
+def destroy_handle(obj, attr: str, call: str) -> None:
+    """Give the handle ``obj.attr`` back through ``call`` if the library is still loaded."""
+    h = getattr(obj, attr, None)
+    if h and _lib is not None:
+        getattr(_lib, call)(h)
+        setattr(obj, attr, None)

@@ -42,8 +42,9 @@ if _HERE not in sys.path:
 
 from dptok import Detok, DptError, Encoder, Vocab, raise_for_status  # noqa: E402
 from dptok import _lib as _dpt  # noqa: E402
-from dptok.engine import (PieceTable, TokenSpans, csr_token_spans, pack_presplit_words, pack_strings,  # noqa: E402
-                          pack_word_atoms)
+from dptok.engine import raise_and_collect as _raise_and_collect  # noqa: E402
+from dptok.pack import (PieceTable, TokenSpans, _pack_id_lists, csr_token_spans, pack_presplit_words,  # noqa: E402
+                        pack_strings, pack_word_atoms, presplit_outcome)
 from dptok.hostpool import shared_pool  # noqa: E402
 
 SPACE_TOKEN = "▁"
@@ -152,19 +153,23 @@ def batch_encoder(tokenizer):
     return lambda texts: [tokenizer.encode(t) for t in texts]
 
 
-def _batch_spans(engine, texts, text, offs, mode, cut=None, none=None, fix_status=None) -> List[TokenSpans]:
+def _batch_spans(engine, texts, text, offs, mode, cut=None, none=None, outcome=None) -> List[TokenSpans]:
     """One encode + spans call over a packed batch -> a ``TokenSpans`` per string.  ``none[i]``: string i
-    has no words (an empty result, whatever its status); ``fix_status(i, status)``: the status that
-    decides string i's exception.  Raises what ``dp_tokenize.batch`` raises, string by string in order,
-    and DptError when a string's ids do not tile it (span status 4: never expected)."""
+    has no words (an empty result, whatever its status); ``outcome(status) -> (status, none)``: the
+    statuses that decide the strings' exceptions, and ``none``, once the engine's are known.  Raises what
+    ``dp_tokenize.batch`` raises, string by string in order, and DptError when a string's ids do not tile
+    it (span status 4: never expected)."""
     ids, id_off, st, _, tok_end, tok_word, sst = engine.encode_csr_spans(text, offs, mode=mode, cut_mask=cut)
     out = csr_token_spans(text, offs, ids, id_off, tok_end, tok_word)
+    if outcome is not None:
+        st, none = outcome(st)
+        none = none.tolist()
     stl, sstl = st.tolist(), sst.tolist()
     for i, t in enumerate(texts):
         if none is not None and none[i]:
             out[i] = TokenSpans([], [], [], "")
             continue
-        raise_for_status(fix_status(i, stl[i]) if fix_status else stl[i], t)
+        raise_for_status(stl[i], t)
         if sstl[i] != _dpt.STATUS_OK:
             raise DptError("token spans: the ids do not tile the string (status %d) of %r" % (sstl[i], t[:60]))
     return out
@@ -193,19 +198,6 @@ def _bos_id(tokenizer) -> Optional[int]:
             return None
         bos = e[0] if len(e) == 1 else None
     return None if bos is None else int(bos)
-
-
-def _pack_id_lists(id_lists):
-    """List of id lists -> (ids int32[], id_off u64[n+1])."""
-    import itertools
-    cnt = np.fromiter((len(x) for x in id_lists), dtype=np.int64, count=len(id_lists))
-    ids = np.fromiter(itertools.chain.from_iterable(id_lists), dtype=np.int64, count=int(cnt.sum()))
-    if len(ids) and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):
-        raise DptError("decode: an id outside int32")
-    id_off = np.zeros(len(id_lists) + 1, dtype=np.uint64)
-    if len(cnt):
-        id_off[1:] = np.cumsum(cnt, dtype=np.uint64)
-    return ids.astype(np.int32), id_off
 
 
 def _decode_surface(make_detok, strip, encode_many):
@@ -242,6 +234,22 @@ def _decode_surface(make_detok, strip, encode_many):
     return decode_batch, batch_roundtrip
 
 
+def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
+                    whose, **extra):
+    """Hang the batch calls, the engine and ``extra`` on the two closures of an adapter and return the pair;
+    ``whose``: the decode that ``decode_batch`` is (for its docstring)."""
+    decode_batch.__doc__ = _DECODE_BATCH_DOC % whose
+    batch_roundtrip.__doc__ = _ROUNDTRIP_DOC
+    decode_dp_tokenization.batch = decode_batch
+    dp_tokenize.batch_roundtrip = batch_roundtrip
+    dp_tokenize.batch = encode_many
+    dp_tokenize.batch_spans = spans_many
+    dp_tokenize.engine = engine
+    for name, value in extra.items():
+        setattr(dp_tokenize, name, value)
+    return dp_tokenize, decode_dp_tokenization
+
+
 def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
     t2i: Dict[str, int] = dict(llama_tokenizer.get_vocab())
     vocab_bidict = _InverseDict(t2i)
@@ -252,11 +260,7 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
 
     if pretokenize_option == "raw":
         def encode_many(texts: Sequence[str]) -> List[List[int]]:
-            out = []
-            for t, (ids, st) in zip(texts, engine.encode_strs(list(texts))):
-                raise_for_status(st, t)
-                out.append(ids)
-            return out
+            return _raise_and_collect(texts, engine.encode_strs(list(texts)))
 
         def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
             texts = list(texts)
@@ -276,11 +280,7 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
                 res = engine.encode_packed_presplit(*host.pack(texts))
             else:
                 res = engine.encode_presplit([pretokenize(t) for t in texts])
-            out = []
-            for t, (ids, st) in zip(texts, res):
-                raise_for_status(st, t)
-                out.append(ids)
-            return out
+            return _raise_and_collect(texts, res)
 
         def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
             # the same two packings as encode_many; ``text`` is the pieces' concatenation
@@ -289,11 +289,9 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
                 text, offs, cut, cnt = host.pack(texts)
                 return _batch_spans(engine, texts, text, offs, "presplit", cut, none=(cnt == 0).tolist())
             text, offs, cut, n_words, cut_at = pack_presplit_words([pretokenize(t) for t in texts])
-
-            def fix(i, s):   # (Encoder.encode_presplit: a string is cut at its first empty word -> IndexError)
-                return _dpt.STATUS_EMPTY_WORD if cut_at[i] >= 0 and s in (_dpt.STATUS_OK, _dpt.STATUS_EMPTY_WORD) else s
+            # (as Encoder.encode_presplit: a string is cut at its first empty word -> IndexError)
             return _batch_spans(engine, texts, text, offs, "presplit", cut,
-                                none=[cut_at[i] < 0 and n_words[i] == 0 for i in range(len(texts))], fix_status=fix)
+                                outcome=lambda st: presplit_outcome(st, n_words, cut_at))
     else:
         def encode_many(texts):
             raise NameError("name 'pretokenize_func' is not defined")
@@ -316,16 +314,8 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
     # is dropped.  The round trip compares with the ORIGINAL text in both modes.
     decode_batch, batch_roundtrip = _decode_surface(
         lambda: Detok(t2i, "sp", [b for b in [_bos_id(llama_tokenizer)] if b is not None], _device()), True, encode_many)
-    decode_batch.__doc__ = _DECODE_BATCH_DOC % "SentencePiece's"
-    batch_roundtrip.__doc__ = _ROUNDTRIP_DOC
-    decode_dp_tokenization.batch = decode_batch
-    dp_tokenize.batch_roundtrip = batch_roundtrip
-    dp_tokenize.batch = encode_many
-    dp_tokenize.batch_spans = spans_many
-    dp_tokenize.engine = engine
-    if pretokenize_option == "llama":
-        dp_tokenize.host_pool = host
-    return dp_tokenize, decode_dp_tokenization
+    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
+                           "SentencePiece's", **({"host_pool": host} if pretokenize_option == "llama" else {}))
 
 
 BLOOM_TOKENIZER_JSON = ("{}/models--bigscience--bloom-3b/snapshots/"
@@ -368,11 +358,7 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
 
     def encode_many(texts: Sequence[str]) -> List[List[int]]:
         batch = [[atoms_of(w) for w in pretokenize(t)] for t in texts]
-        out = []
-        for t, (ids, st) in zip(texts, engine.encode_word_atoms(batch)):
-            raise_for_status(st, t)
-            out.append(ids)
-        return out
+        return _raise_and_collect(texts, engine.encode_word_atoms(batch))
 
     def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
         # ``text`` is the atoms' concatenation (the byte-level alphabet's characters, one per input byte)
@@ -391,12 +377,5 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
     # the UTF-8 of the input
     decode_batch, batch_roundtrip = _decode_surface(lambda: Detok(dict(vocab_to_index), "bytelevel", (), _device()), False,
                                                     encode_many)
-    decode_batch.__doc__ = _DECODE_BATCH_DOC % "ByteLevel's"
-    batch_roundtrip.__doc__ = _ROUNDTRIP_DOC
-    decode_dp_tokenization.batch = decode_batch
-    dp_tokenize.batch_roundtrip = batch_roundtrip
-    dp_tokenize.batch = encode_many
-    dp_tokenize.batch_spans = spans_many
-    dp_tokenize.engine = engine
-    dp_tokenize.vocab_to_index = vocab_to_index
-    return dp_tokenize, decode_dp_tokenization
+    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
+                           "ByteLevel's", vocab_to_index=vocab_to_index)

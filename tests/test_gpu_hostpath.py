@@ -212,3 +212,67 @@ def test_zero_copy_calls_between_the_decode_roundtrip_and_spans_paths(vocabs):
     for g, r, part in zip(enc.encode_csr(text, offs, mode="presplit", cut_mask=cut),
                           orc.encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut), ("ids", "offsets", "status", "capped")):
         assert np.array_equal(g, r), ("presplit", part)
+
+
+TOY = {"a": 0, "b": 1, "ab": 2, "▁a": 3}   # (the vocabulary of test_llama_sp.py test_encode_presplit_empty_word_order)
+
+
+def test_encode_word_atoms_lists():
+    """Encoder.encode_word_atoms ends in csr_lists: per string the oracle's ids and status, ([], ok) for a
+    string of no words; a word with no tokenization fails its whole string."""
+    from dptok import Encoder, STATUS_NO_TOKENIZATION, STATUS_OK, Vocab
+    from dptok.engine import pack_word_atoms
+    from oracle import oracle
+    strings = [[], [["a", "b"]], [["a"], ["z"], ["b"]], [["▁", "a"]], [["a", "b"], ["▁", "a"], ["b"]], [["b"]]]
+    got = Encoder(Vocab(TOY, 0)).encode_word_atoms(strings)
+    text, offs, cut = pack_word_atoms(strings)
+    ids, id_off, st, _ = oracle.OracleVocab(TOY).encode_csr(text, offs, mode=oracle.ATOMS, cut_mask=cut)
+    want = [([], STATUS_OK) if not words else (ids[int(id_off[i]):int(id_off[i + 1])].tolist(), int(st[i]))
+            for i, words in enumerate(strings)]
+    assert got == want
+    assert got[0] == ([], STATUS_OK) and got[1] == ([2], STATUS_OK) and got[2][1] == STATUS_NO_TOKENIZATION
+    assert got[3] == ([3], STATUS_OK) and got[4] == ([2, 3, 1], STATUS_OK)
+
+
+def test_encode_csr_spans_from_a_nonzero_offset():
+    """A host batch may start anywhere in its buffers: three pre-split strings packed after 5 junk bytes, the
+    cut mask moved the same way, give what the batch packed at offset 0 gives (and its ids are the oracle's)."""
+    from dptok import Encoder, Vocab
+    from dptok.engine import pack_presplit_words
+    from oracle import oracle
+    text, offs, cut, _, _ = pack_presplit_words([["ab", "▁a"], ["▁a", "b", "a"], ["a", "b", "ab"]])
+    enc = Encoder(Vocab(TOY, 0))
+    at0 = enc.encode_csr_spans(text, offs, mode="presplit", cut_mask=cut)
+    ref = oracle.OracleVocab(TOY).encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut)
+    for g, r in zip(at0[:4], ref):
+        assert np.array_equal(g, r)
+    assert at0[0].tolist() == [2, 3, 3, 1, 0, 0, 1, 2] and not at0[2].any() and not at0[6].any()
+    junk = np.frombuffer(b"zz zz", dtype=np.uint8)
+    at5 = enc.encode_csr_spans(np.concatenate([junk, text]), offs + np.uint64(5), mode="presplit",
+                               cut_mask=np.concatenate([np.ones(5, np.uint8), cut]))
+    assert len(at5) == 7
+    for g, r in zip(at5, at0):
+        assert g.dtype == r.dtype and np.array_equal(g, r)
+
+
+def test_encode_device_null_pointers_as_plain_ints():
+    """The device-pointer methods pass plain ints to the void* arguments: 0 must arrive as NULL (no capped
+    output, no cut mask, the default stream)."""
+    import torch
+    from dptok import Encoder, Vocab, pack_strings
+    from oracle import oracle
+    text, offs = pack_strings(["ab", "", "a ab", "b"])
+    n, n_bytes = len(offs) - 1, int(offs[-1])
+    dev = torch.device("cuda", 0)
+    d_text = torch.tensor(text, device=dev)
+    d_offs = torch.tensor(offs.view(np.int64), device=dev)
+    d_ids = torch.full((n_bytes + 1,), -1, dtype=torch.int32, device=dev)
+    d_idoff = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+    d_st = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    Encoder(Vocab(TOY, 0)).encode_device(d_text.data_ptr(), n_bytes, d_offs.data_ptr(), n, d_ids.data_ptr(), n_bytes + 1,
+                                         d_idoff.data_ptr(), d_st.data_ptr(), 0, 0, 0)
+    torch.cuda.synchronize()
+    ids, id_off, st, _ = oracle.OracleVocab(TOY).encode_csr(text, offs)
+    assert d_idoff.cpu().numpy().tolist() == id_off.tolist() and d_st.cpu().numpy().tolist() == st.tolist()
+    assert d_ids.cpu().numpy()[:len(ids)].tolist() == ids.tolist() and ids.tolist() == [3, 1, 3, 3, 1]
+    assert st.tolist() == [0, 2, 0, 1]   # ("" is the reference's IndexError, "b" has no tokenization)
