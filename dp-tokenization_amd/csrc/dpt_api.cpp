@@ -498,6 +498,32 @@ int dpt_token_histogram(const uint64_t *id_off, const int32_t *status, uint64_t 
     return DPT_OK;
 }
 
+int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts, const int32_t *status, uint64_t n_str,
+                const dpt_collate_opts *opts, void *input_ids, void *attention_mask, void *labels, uint32_t *lengths,
+                void *hip_stream) {
+    if (!ids) return fail(DPT_E_ARG, "null ids");
+    if (!off) return fail(DPT_E_ARG, "null off");
+    if (!opts) return fail(DPT_E_ARG, "null opts");
+    if (!input_ids) return fail(DPT_E_ARG, "null input_ids");
+    const uint32_t known = DPT_COLLATE_BOS | DPT_COLLATE_EOS | DPT_COLLATE_PAD_LEFT | DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64;
+    if (opts->flags & ~known) return fail(DPT_E_ARG, "unknown bits in opts->flags");
+    const uint32_t n_special = ((opts->flags & DPT_COLLATE_BOS) ? 1u : 0u) + ((opts->flags & DPT_COLLATE_EOS) ? 1u : 0u);
+    if (opts->row_len == 0) return fail(DPT_E_ARG, "opts->row_len is 0");
+    if (opts->row_len < n_special) return fail(DPT_E_ARG, "opts->row_len holds fewer elements than the BOS / EOS asked for");
+    if (opts->row_len > (1u << 31)) return fail(DPT_E_ARG, "opts->row_len over 2^31");
+    if (opts->row_stride && opts->row_stride < opts->row_len) return fail(DPT_E_ARG, "opts->row_stride under row_len");
+    if (n_str == 0) return DPT_OK;
+    dpt::CollateLaunch p{};
+    p.ids = ids; p.off = off; p.counts = counts; p.status = status; p.n_str = n_str;
+    p.row_len = opts->row_len; p.row_stride = opts->row_stride ? opts->row_stride : opts->row_len;
+    p.pad_id = opts->pad_id; p.bos_id = opts->bos_id; p.eos_id = opts->eos_id; p.ignore_id = opts->ignore_id;
+    p.flags = opts->flags;
+    p.input_ids = input_ids; p.mask = attention_mask; p.labels = labels; p.lengths = lengths;
+    const hipError_t e = dpt::launch_collate(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "collate launch");
+    return DPT_OK;
+}
+
 int dpt_ctx_set_histogram_ex(dpt_ctx *c, int64_t *hist, uint32_t n_bins, int flags) {
     if (!c) return fail(DPT_E_ARG, "null ctx");
     if (hist && (n_bins < 2 || n_bins > DPT_HIST_MAX_BINS)) return fail(DPT_E_ARG, "n_bins outside 2..DPT_HIST_MAX_BINS");

@@ -1,5 +1,5 @@
 // Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp)
-// and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip).
+// and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -291,6 +291,25 @@ struct DecodeLaunch {
     int32_t *result;
 };
 hipError_t launch_decode(const DecodeLaunch &p, hipStream_t stream);
+
+// One launch of the collate kernel (dpt_collate.hip; include/dpt.h dpt_collate): every pointer a device pointer,
+// the options already checked (row_len >= the specials asked for, row_stride >= row_len, known flags).
+struct CollateLaunch {
+    const int32_t *ids;
+    const uint64_t *off;       // n_str + 1
+    const uint64_t *counts;    // nullable: the token counts come from off
+    const int32_t *status;     // nullable: all 0
+    uint64_t n_str;
+    uint32_t row_len;
+    uint64_t row_stride;       // elements, >= row_len
+    int32_t pad_id, bos_id, eos_id, ignore_id;
+    uint32_t flags;            // DPT_COLLATE_*
+    void *input_ids;           // int32, or int64 with DPT_COLLATE_I64 (and the next two)
+    void *mask;                // nullable
+    void *labels;              // nullable
+    uint32_t *lengths;         // nullable
+};
+hipError_t launch_collate(const CollateLaunch &p, hipStream_t stream);
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

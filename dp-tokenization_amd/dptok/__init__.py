@@ -3,6 +3,8 @@
 Public surface:
     Vocab, Encoder          batch engine (engine.py)
     Detok                   ids back to bytes and the round-trip check (detok.py)
+    collate                 padded model inputs from an encoded batch, on the device (collate.py: the
+                            ``collate_device`` / ``model_inputs`` calls; imported on demand, it needs torch)
     pack_strings, TokenSpans  host arrays in and out of the engine (pack.py, pure numpy)
     dp_tokenize_batch       List[str] -> List[List[int]] for a t2i vocabulary
     synth                   synthetic vocabularies/corpora of the BASELINE configs

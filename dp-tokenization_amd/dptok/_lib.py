@@ -38,6 +38,15 @@ class VocabStats(ctypes.Structure):
                 ("hash_max_probe", ctypes.c_uint32), ("hash_buckets", ctypes.c_uint32)]
 
 
+class CollateOpts(ctypes.Structure):
+    """dpt_collate_opts"""
+    _fields_ = [("row_len", ctypes.c_uint32), ("row_stride", ctypes.c_uint64), ("pad_id", ctypes.c_int32),
+                ("bos_id", ctypes.c_int32), ("eos_id", ctypes.c_int32), ("ignore_id", ctypes.c_int32),
+                ("flags", ctypes.c_uint32)]
+
+
+COLLATE_BOS, COLLATE_EOS, COLLATE_PAD_LEFT, COLLATE_TRUNC_LEFT, COLLATE_I64 = 1, 2, 4, 8, 16
+
 _lib = None
 P = ctypes.c_void_p
 U64 = ctypes.c_uint64
@@ -88,6 +97,8 @@ CALLS = {
     "dpt_decode_host": (I32, [P, P, P, P, P, U64, I32, P, U64, P, P]),
     "dpt_roundtrip_host": (I32, [P, P, P, P, P, P, P, U64, I32, P, P]),
     "dpt_debug_detok_table": (I32, [P, P, P, U32, I32, P, U32, I32, P, U64, PU64]),
+    # model-input batches
+    "dpt_collate": (I32, [P, P, P, P, U64, ctypes.POINTER(CollateOpts), P, P, P, P, P]),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -96,6 +107,9 @@ OPTIONAL = {"dpt_debug_host_layout", "dpt_detok_create", "dpt_detok_destroy", "d
 EXPORTED = sorted(CALLS)
 # the decode calls: name -> argument types
 DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and name != "dpt_debug_host_layout"}
+# Also within ABI 6 and probed for like OPTIONAL's (a set of its own: OPTIONAL less the layout call is, by
+# tests/test_pack.py, exactly the decode calls); ``collate.collate_device`` raises without it (has_collate).
+OPTIONAL_LATER = {"dpt_collate"}
 
 
 def lib():
@@ -115,7 +129,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if name in OPTIONAL and not hasattr(L, name):
+        if (name in OPTIONAL or name in OPTIONAL_LATER) and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -127,6 +141,11 @@ def has_decode() -> bool:
     """The loaded library exports the decode calls (a libdpt.so built before them does not)."""
     L = lib()
     return all(hasattr(L, name) for name in DECODE_CALLS)
+
+
+def has_collate() -> bool:
+    """The loaded library exports dpt_collate."""
+    return hasattr(lib(), "dpt_collate")
 
 
 def check(rc: int, what: str = "") -> None:

@@ -1,0 +1,102 @@
+"""Model-input batches on the device (dpt_collate, include/dpt.h): the ids of an encoded batch as padded
+``input_ids`` / ``attention_mask`` / ``labels`` rows -- what the reference's ``llama_preprocessing_function``
+(main_analyze_s2orc.py:61-93) and the Trainer's collator produce on the host.
+
+``collate_device`` is the raw call over device addresses; ``model_inputs`` the same over torch tensors."""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+from . import _lib
+from ._lib import (COLLATE_BOS, COLLATE_EOS, COLLATE_I64, COLLATE_PAD_LEFT, COLLATE_TRUNC_LEFT, CollateOpts, DptError,
+                   check)
+
+
+def collate_flags(bos_id=None, eos_id=None, pad_left=False, trunc_left=False, int64=True) -> int:
+    return ((COLLATE_BOS if bos_id is not None else 0) | (COLLATE_EOS if eos_id is not None else 0)
+            | (COLLATE_PAD_LEFT if pad_left else 0) | (COLLATE_TRUNC_LEFT if trunc_left else 0)
+            | (COLLATE_I64 if int64 else 0))
+
+
+def collate_device(ids_ptr: int, off_ptr: int, n_str: int, input_ids_ptr: int, row_len: int, *, counts_ptr: int = 0,
+                   status_ptr: int = 0, mask_ptr: int = 0, labels_ptr: int = 0, lengths_ptr: int = 0, row_stride: int = 0,
+                   pad_id: int = 0, bos_id: Optional[int] = None, eos_id: Optional[int] = None, ignore_id: int = -100,
+                   pad_left: bool = False, trunc_left: bool = False, int64: bool = True, stream: int = 0) -> None:
+    """dpt_collate over device addresses (e.g. ``torch.Tensor.data_ptr()``; 0 = NULL): stream-ordered, no sync.
+    ``counts_ptr`` 0: ``off`` is dpt_encode's id_off; else dpt_encode_padded's str_off and counts.  ``bos_id`` /
+    ``eos_id`` None: no such special.  Rows are int64, or int32 with ``int64=False``; ``lengths`` is uint32."""
+    if not _lib.has_collate():
+        raise DptError("this libdpt.so has no dpt_collate")
+    opts = CollateOpts(row_len, row_stride, pad_id, bos_id or 0, eos_id or 0, ignore_id,
+                       collate_flags(bos_id, eos_id, pad_left, trunc_left, int64))
+    check(_lib.lib().dpt_collate(ids_ptr, off_ptr, counts_ptr, status_ptr, n_str, ctypes.byref(opts), input_ids_ptr,
+                                 mask_ptr, labels_ptr, lengths_ptr, stream), "dpt_collate")
+
+
+def model_inputs(ids, off, status=None, counts=None, *, padding: str = "longest", max_length: Optional[int] = None,
+                 pad_to_multiple_of: Optional[int] = None, labels: bool = False, pad_id: int = 0,
+                 bos_id: Optional[int] = None, eos_id: Optional[int] = None, ignore_id: int = -100,
+                 padding_side: str = "right", truncation_side: str = "right", int64: bool = True) -> Dict[str, object]:
+    """Torch device tensors of an encoded batch -> ``{"input_ids", "attention_mask", "lengths"[, "labels"]}``,
+    allocated on the inputs' device and filled on torch's current stream by one dpt_collate launch.
+
+    ``ids`` int32, ``off`` (int64 / uint64 bit patterns, n_str + 1 entries), ``status`` int32 or None and
+    ``counts`` or None are what ``Encoder.encode_device`` (off = id_off) or ``encode_device_padded``
+    (off = str_off, counts) wrote.  ``padding="longest"``: the row length is the longest kept sequence, read
+    back from the offsets or counts (that one scalar is the only synchronisation), capped by ``max_length``;
+    ``"max_length"``: the row length is ``max_length`` and nothing synchronises.  Either is then rounded up to
+    ``pad_to_multiple_of`` and is at least max(the specials, 1).  Rows are int64 (``int64=False``: int32),
+    ``lengths`` int32 per string."""
+    import torch
+    if padding not in ("longest", "max_length"):
+        raise ValueError("padding must be 'longest' or 'max_length'")
+    if padding_side not in ("left", "right") or truncation_side not in ("left", "right"):
+        raise ValueError("padding_side / truncation_side must be 'left' or 'right'")
+    n_str = off.numel() - 1
+    if n_str < 0:
+        raise ValueError("off needs n_str + 1 entries")
+    for t in (ids, off, status, counts):
+        if t is not None and (not t.is_contiguous() or t.device != ids.device):
+            raise ValueError("ids, off, status and counts must be contiguous tensors on one device")
+    if ids.dtype != torch.int32 or off.element_size() != 8 or (counts is not None and counts.element_size() != 8) \
+            or (status is not None and status.dtype != torch.int32):
+        raise ValueError("ids / status must be int32, off / counts 8-byte integers")
+    n_special = (bos_id is not None) + (eos_id is not None)
+    if padding == "max_length":
+        if max_length is None:
+            raise ValueError("padding='max_length' needs max_length")
+        row_len = int(max_length)
+    else:
+        row_len = 0
+        if n_str:
+            n = counts.view(torch.int64)[:n_str] if counts is not None else off.view(torch.int64).diff()
+            if status is not None:
+                n = n.masked_fill(status[:n_str] != 0, -n_special)   # a failed string's row is all pad
+            row_len = int(n.max()) + n_special
+        if max_length is not None:
+            row_len = min(row_len, int(max_length))
+    row_len = max(row_len, n_special, 1)
+    if pad_to_multiple_of:
+        row_len = -(-row_len // pad_to_multiple_of) * pad_to_multiple_of
+    dtype = torch.int64 if int64 else torch.int32
+    dev = ids.device
+    out = {"input_ids": torch.empty((n_str, row_len), dtype=dtype, device=dev),
+           "attention_mask": torch.empty((n_str, row_len), dtype=dtype, device=dev),
+           "lengths": torch.empty(n_str, dtype=torch.int32, device=dev)}
+    if labels:
+        out["labels"] = torch.empty((n_str, row_len), dtype=dtype, device=dev)
+    if n_str == 0:
+        return out
+    if ids.numel() == 0:   # (an empty tensor has no address; no id is read)
+        ids = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        collate_device(ids.data_ptr(), off.data_ptr(), n_str, out["input_ids"].data_ptr(), row_len,
+                       counts_ptr=counts.data_ptr() if counts is not None else 0,
+                       status_ptr=status.data_ptr() if status is not None else 0,
+                       mask_ptr=out["attention_mask"].data_ptr(),
+                       labels_ptr=out["labels"].data_ptr() if labels else 0, lengths_ptr=out["lengths"].data_ptr(),
+                       pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, ignore_id=ignore_id,
+                       pad_left=padding_side == "left", trunc_left=truncation_side == "left", int64=int64,
+                       stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out

@@ -21,6 +21,9 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   the (start, end) of token k in characters of ``text``, ``word_ids[k]`` the 0-based word it lies in
   (what the probe at reference main_analyze_s2orc.py:275-290 re-tokenizes every word to learn).  Same
   exceptions as ``batch``.
+* ``dp_tokenize.batch_model_inputs(List[str], ...) -> dict``: the batch as padded ``input_ids`` /
+  ``attention_mask`` / ``labels`` / ``lengths`` tensors on the GPU (dpt_encode_padded + dpt_collate; what
+  reference main_analyze_s2orc.py:61-93 and the collator build on the host); see its docstring.
 * ``decode_dp_tokenization.batch(List[List[int]]) -> List[str]`` and ``dp_tokenize.batch_roundtrip(List[str])
   -> List[Optional[int]]``: the tokenizer's own decode of a batch, and the caller's round-trip assert
   (reference main_analyze_s2orc.py:84-87), each in one GPU launch; ``decode_dp_tokenization`` itself stays
@@ -234,8 +237,90 @@ def _decode_surface(make_detok, strip, encode_many):
     return decode_batch, batch_roundtrip
 
 
-def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
-                    whose, **extra):
+_MODEL_INPUTS_DOC = """``dp_tokenize.batch_model_inputs(texts, max_length=None, padding="longest", pad_to_multiple_of=None,
+add_bos=False, add_eos=False, padding_side="right", truncation_side="right", labels=False, errors="raise") -> dict``:
+the batch as model inputs on the GPU -- what the reference's llama_preprocessing_function (main_analyze_s2orc.py:
+61-93) and the Trainer's collator build on the host.  The packed text goes up, dpt_encode_padded and dpt_collate
+run back to back, and nothing comes back but the statuses (and, for ``padding="longest"``, the row length).
+``input_ids`` / ``attention_mask`` (/ ``labels``, pad positions -100) are int64 ``[len(texts), row]`` tensors on the
+engine's device, ``lengths`` int32 per string.  The row is the longest sequence capped by ``max_length``
+(``padding="max_length"``: exactly ``max_length``), rounded up to ``pad_to_multiple_of``.  The pad id is the
+tokenizer's ``pad_token_id``, else its ``eos_token_id``, else 0; ``add_bos`` / ``add_eos`` put its BOS / EOS id
+around the kept ids (in llama mode the BOS piece ``tokenizer.encode`` adds is already a word of the text).
+``errors="raise"``: what ``dp_tokenize.batch`` raises, for the first failed string in order; ``"mask"``: a
+failed string's row is all pad with mask 0 and length 0, and ``status`` (int32 per string) is returned too."""
+
+
+def _special_ids(tokenizer):
+    """(bos, eos, pad) ids of a tokenizer object: bos / eos None when it has none; pad is its ``pad_token_id``,
+    else its ``eos_token_id``, else 0."""
+    eos = getattr(tokenizer, "eos_token_id", None)
+    pad = getattr(tokenizer, "pad_token_id", None)
+    eos = None if eos is None else int(eos)
+    return _bos_id(tokenizer), eos, int(pad) if pad is not None else eos if eos is not None else 0
+
+
+def _model_inputs_surface(engine, tokenizer, pack_batch):
+    """``batch_model_inputs`` over one adapter's packing: ``pack_batch(texts) -> (text, offs, mode, cut, none,
+    outcome)``, the buffers of its ``batch`` call with ``none`` / ``outcome`` as ``_batch_spans`` takes them."""
+
+    def batch_model_inputs(texts, max_length=None, padding="longest", pad_to_multiple_of=None, add_bos=False,
+                           add_eos=False, padding_side="right", truncation_side="right", labels=False, errors="raise"):
+        import torch
+        from dptok.collate import model_inputs
+        if errors not in ("raise", "mask"):
+            raise ValueError("errors must be 'raise' or 'mask'")
+        texts = list(texts)
+        bos, eos, pad = _special_ids(tokenizer)
+        if (add_bos and bos is None) or (add_eos and eos is None):
+            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
+        text, offs, mode, cut, none, outcome = pack_batch(texts)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n, b0 = len(offs) - 1, int(offs[0])
+        n_bytes = int(offs[-1]) - b0
+        dev = torch.device("cuda", engine.vocab.device)
+
+        def up(a):   # the batch's bytes (at least one, so the tensor has an address)
+            a = np.ascontiguousarray(a, dtype=np.uint8)[b0:b0 + n_bytes]
+            if not n_bytes or not a.flags.writeable:   # (torch wraps writable arrays only)
+                a = a.copy() if n_bytes else np.zeros(1, dtype=np.uint8)
+            return torch.from_numpy(a).to(dev)
+
+        with torch.cuda.device(dev):
+            d_text, d_cut = up(text), (up(cut) if cut is not None else None)
+            d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
+            ids = torch.empty(max(n_bytes, 1), dtype=torch.int32, device=dev)
+            counts = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+            st = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            if n:
+                engine.encode_device_padded(d_text.data_ptr(), n_bytes, d_offs.data_ptr(), n, ids.data_ptr(), max(n_bytes, 1),
+                                            counts.data_ptr(), st.data_ptr(), cut_ptr=d_cut.data_ptr() if d_cut is not None else 0,
+                                            stream=torch.cuda.current_stream(dev).cuda_stream, mode=mode)
+            st = st[:n]
+            if outcome is not None:   # (the word-list packing: the statuses depend on the engine's, read back)
+                fixed, none = outcome(st.cpu().numpy())
+                st = torch.from_numpy(np.ascontiguousarray(fixed, dtype=np.int32)).to(dev)
+            if none is not None and n:   # strings without words: nothing, whatever the engine made of them
+                d_none = torch.from_numpy(np.ascontiguousarray(none, dtype=bool)).to(dev)
+                st = st.masked_fill(d_none, _dpt.STATUS_OK)
+                counts = counts[:n].masked_fill(d_none, 0)
+            out = model_inputs(ids, d_offs, st, counts[:n].contiguous(), padding=padding, max_length=max_length,
+                               pad_to_multiple_of=pad_to_multiple_of, labels=labels, pad_id=pad,
+                               bos_id=bos if add_bos else None, eos_id=eos if add_eos else None,
+                               padding_side=padding_side, truncation_side=truncation_side)
+            if errors == "mask":
+                out["status"] = st
+                return out
+            for i in np.flatnonzero(st.cpu().numpy()).tolist()[:1]:
+                raise_for_status(int(st[i]), texts[i])
+        return out
+
+    batch_model_inputs.__doc__ = _MODEL_INPUTS_DOC
+    return batch_model_inputs
+
+
+def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, inputs_many, decode_batch,
+                    batch_roundtrip, whose, **extra):
     """Hang the batch calls, the engine and ``extra`` on the two closures of an adapter and return the pair;
     ``whose``: the decode that ``decode_batch`` is (for its docstring)."""
     decode_batch.__doc__ = _DECODE_BATCH_DOC % whose
@@ -244,6 +329,7 @@ def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, sp
     dp_tokenize.batch_roundtrip = batch_roundtrip
     dp_tokenize.batch = encode_many
     dp_tokenize.batch_spans = spans_many
+    dp_tokenize.batch_model_inputs = inputs_many
     dp_tokenize.engine = engine
     for name, value in extra.items():
         setattr(dp_tokenize, name, value)
@@ -265,6 +351,9 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
         def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
             texts = list(texts)
             return _batch_spans(engine, texts, *pack_strings(texts), "raw")
+
+        def pack_batch(texts):
+            return (*pack_strings(texts), "raw", None, None, None)
     elif pretokenize_option == "llama":
         pretokenize = pretokenize_with_llama(llama_tokenizer, vocab_bidict)
         pieces = PieceTable(t2i)
@@ -292,10 +381,18 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
             # (as Encoder.encode_presplit: a string is cut at its first empty word -> IndexError)
             return _batch_spans(engine, texts, text, offs, "presplit", cut,
                                 outcome=lambda st: presplit_outcome(st, n_words, cut_at))
+
+        def pack_batch(texts):
+            # the same two packings again
+            if pieces.ok and not pieces.empty_piece:
+                text, offs, cut, cnt = host.pack(texts)
+                return text, offs, "presplit", cut, cnt == 0, None
+            text, offs, cut, n_words, cut_at = pack_presplit_words([pretokenize(t) for t in texts])
+            return text, offs, "presplit", cut, None, lambda st: presplit_outcome(st, n_words, cut_at)
     else:
         def encode_many(texts):
             raise NameError("name 'pretokenize_func' is not defined")
-        spans_many = encode_many
+        spans_many = pack_batch = encode_many
 
     if pretokenize_option == "raw":
         def dp_tokenize(input_str) -> List[int]:
@@ -314,7 +411,8 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
     # is dropped.  The round trip compares with the ORIGINAL text in both modes.
     decode_batch, batch_roundtrip = _decode_surface(
         lambda: Detok(t2i, "sp", [b for b in [_bos_id(llama_tokenizer)] if b is not None], _device()), True, encode_many)
-    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
+    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
+                           _model_inputs_surface(engine, llama_tokenizer, pack_batch), decode_batch, batch_roundtrip,
                            "SentencePiece's", **({"host_pool": host} if pretokenize_option == "llama" else {}))
 
 
@@ -367,6 +465,11 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
         text, offs, cut = pack_word_atoms(batch)
         return _batch_spans(engine, texts, text, offs, "atoms", cut, none=[not words for words in batch])
 
+    def pack_batch(texts):
+        batch = [[atoms_of(w) for w in pretokenize(t)] for t in texts]
+        text, offs, cut = pack_word_atoms(batch)
+        return text, offs, "atoms", cut, [not words for words in batch], None
+
     def dp_tokenize(input_str) -> List[int]:
         return encode_many([input_str])[0]
 
@@ -377,5 +480,6 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
     # the UTF-8 of the input
     decode_batch, batch_roundtrip = _decode_surface(lambda: Detok(dict(vocab_to_index), "bytelevel", (), _device()), False,
                                                     encode_many)
-    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, decode_batch, batch_roundtrip,
+    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
+                           _model_inputs_surface(engine, bloom_tokenizer, pack_batch), decode_batch, batch_roundtrip,
                            "ByteLevel's", vocab_to_index=vocab_to_index)

@@ -22,6 +22,8 @@
  *                        (dp_tokenize on every pre-token, to tell which words the DP shortened)
  *   dpt_decode, dpt_roundtrip <- the decode_dp_tokenization closure, reference packages/tokenizer_utils.py:82-84,
  *                        :176-179, and the caller's round-trip assert, main_analyze_s2orc.py:84-87
+ *   dpt_collate        <- llama_preprocessing_function's model inputs, reference main_analyze_s2orc.py:61-93
+ *                        (input_ids, attention_mask = [1] * len(ids), truncation; the collator's padding)
  *   dpt_hist_allreduce <- SURVEY.md §8(b)/(e): the one collective of a sharded corpus (the
  *                        reference is single-process, llama_s2orc.sh:10; no call site there)
  *
@@ -326,6 +328,54 @@ int dpt_roundtrip_host(dpt_ctx *c, const dpt_detok *d, const int32_t *ids, const
 #define DPT_DETOK_SCALAR_INTS 4
 int dpt_debug_detok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok, int rule,
                           const int32_t *skip_ids, uint32_t n_skip, int which, void *out, uint64_t cap, uint64_t *size);
+
+/*
+ * Model-input batches: the ids of an encoded batch as padded [n_str, row_len] rows -- what the reference's
+ * llama_preprocessing_function hands the Trainer (main_analyze_s2orc.py:61-93: input_ids, attention_mask =
+ * [1] * len(ids), truncation to max_length) after the collator has padded the batch.  Added within ABI 6
+ * (DPT_ABI_VERSION unchanged): a binding that may meet an older libdpt.so probes for the symbol.
+ *
+ * ids (int32), off (uint64, n_str + 1 entries, off[0] need not be 0), counts (nullable, uint64 per string) and
+ * status (nullable: all 0) describe the batch: string s has the tokens t[k] = ids[off[s] - off[0] + k] for
+ * k < n, with n = off[s+1] - off[s] when counts == NULL (dpt_encode's layout, off = id_off) and n = counts[s]
+ * otherwise (dpt_encode_padded's layout, off = str_off).  With L = row_len and n_special = the number of
+ * DPT_COLLATE_BOS / DPT_COLLATE_EOS set, a string with status[s] == 0 gives
+ *   keep = min(n, L - n_special) tokens: the first keep, or with DPT_COLLATE_TRUNC_LEFT the last keep
+ *   seq  = [bos_id] + kept + [eos_id] (the specials survive truncation), len = keep + n_special
+ *   input_ids row s:  seq in [0, len) and pad_id in [len, L); with DPT_COLLATE_PAD_LEFT pad_id in [0, L - len)
+ *                     and seq in [L - len, L)
+ *   attention_mask:   1 where the row holds seq, 0 where it holds pad_id
+ *   labels:           the row of input_ids with ignore_id where the mask is 0
+ *   lengths[s] = len  (an empty string gives its specials only)
+ * and a string with status[s] != 0 a row of pad_id, mask 0, labels ignore_id and lengths[s] = 0, whatever its
+ * off range or count holds.  Ids pass through unvalidated.  Row s starts at element s * row_stride of each of
+ * input_ids, attention_mask and labels (row_stride 0: row_len; else >= row_len); their elements are int32, or
+ * with DPT_COLLATE_I64 int64 (sign-extended).  attention_mask, labels and lengths are nullable.  Elements
+ * [row_len, row_stride) of a row and everything outside the n_str rows are never written.  Outputs must not
+ * overlap inputs and need their element's alignment only (4 or 8 bytes).
+ * DPT_E_ARG, before any device work: null ids, off, opts or input_ids; row_len 0 or < n_special; row_stride
+ * non-zero and < row_len; unknown flags.  n_str == 0 launches nothing.
+ * DEVICE pointers on the current device; stream-ordered on hip_stream, never synchronises, allocates nothing
+ * and needs no dpt_ctx and no vocabulary: any number of calls may be in flight.  No host-buffer form (the
+ * product is a device tensor).  off monotone, row_len <= 2^31, n_str * row_stride < 2^63.
+ */
+#define DPT_COLLATE_BOS 1
+#define DPT_COLLATE_EOS 2
+#define DPT_COLLATE_PAD_LEFT 4
+#define DPT_COLLATE_TRUNC_LEFT 8
+#define DPT_COLLATE_I64 16
+typedef struct {
+    uint32_t row_len;      /* L: elements per row */
+    uint64_t row_stride;   /* elements between row starts (0: row_len) */
+    int32_t pad_id;
+    int32_t bos_id;        /* read with DPT_COLLATE_BOS */
+    int32_t eos_id;        /* read with DPT_COLLATE_EOS */
+    int32_t ignore_id;     /* labels at pad positions (e.g. -100) */
+    uint32_t flags;        /* DPT_COLLATE_* */
+} dpt_collate_opts;
+int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts, const int32_t *status,
+                uint64_t n_str, const dpt_collate_opts *opts, void *input_ids, void *attention_mask,
+                void *labels, uint32_t *lengths, void *hip_stream);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
