@@ -1,5 +1,5 @@
-// Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp)
-// and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip).
+// Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp,
+// dpt_pretok.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip, dpt_pretok.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -310,6 +310,50 @@ struct CollateLaunch {
     uint32_t *lengths;         // nullable
 };
 hipError_t launch_collate(const CollateLaunch &p, hipStream_t stream);
+
+// Pre-tokenization table of a vocabulary (dpt_pretok.cpp build_pretok_tables; include/dpt.h dpt_pretok_create), as
+// host bytes exactly as dpt_pretok_create uploads them.
+constexpr uint32_t PRETOK_BMP_WORDS = 2048;   // the known set below U+10000, one bit per code point
+struct PretokTables {
+    std::vector<uint32_t> bmp;      // PRETOK_BMP_WORDS: bit cp & 31 of word cp >> 5
+    std::vector<uint32_t> astral;   // the known code points from U+10000 up, ascending
+    std::vector<uint8_t> lit;       // 8 uint32 (the literals' first bytes as a bitmap) | n_lit + 1 uint32 offsets | bytes
+    std::vector<uint8_t> prefix;    // the BOS piece, then U+2581
+    bool runs_ok = true;
+    uint32_t n_known = 0, n_lit = 0, bos_len = 0;
+};
+// returns 0 or an error message (*code: DPT_E_ARG or DPT_E_VOCAB); calls no HIP function
+const char *build_pretok_tables(const uint8_t *blob, const uint64_t *off, uint32_t n, const uint8_t *bos, uint32_t bos_len,
+                                const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, PretokTables *out, int *code);
+
+// One launch of the pre-tokenization kernels (dpt_pretok.hip; include/dpt.h dpt_pretok_sizes, dpt_pretok_write):
+// every pointer a device pointer.
+struct PretokLaunch {
+    bool write;                  // false: the sizes pass
+    const uint8_t *text;
+    const uint64_t *str_off;
+    uint64_t n_str;
+    // the table
+    const uint32_t *bmp;
+    const uint32_t *astral;      // n_astral entries (null when 0)
+    uint32_t n_astral;
+    uint64_t lit_first[4];       // the literals' first bytes as a bitmap
+    const uint32_t *lit_off;     // n_lit + 1
+    const uint8_t *lit_bytes;
+    uint32_t n_lit;
+    const uint8_t *prefix;       // bos_len + 3 bytes
+    uint32_t bos_len;
+    bool runs_ok;
+    uint64_t ascii_known[2];     // bmp's first four words: the known code points below U+0080
+    // sizes
+    uint64_t *out_len;
+    int32_t *pre_status;         // written by sizes, read by write
+    // write
+    uint8_t *out_text;
+    const uint64_t *out_off;
+    uint8_t *cut_mask;
+};
+hipError_t launch_pretok(const PretokLaunch &p, hipStream_t stream);
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

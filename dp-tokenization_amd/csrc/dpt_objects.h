@@ -27,6 +27,20 @@ struct dpt_detok {
     uint32_t n_tab = 0;
 };
 
+// The device copy of a pre-tokenization table (dpt_pretok.cpp build_pretok_tables), and what of it travels with the
+// kernel arguments.
+struct dpt_pretok {
+    int device = 0;
+    uint32_t *d_bmp = nullptr;      // dpt::PRETOK_BMP_WORDS
+    uint32_t *d_astral = nullptr;   // n_astral known code points from U+10000 up (null: none)
+    uint8_t *d_lit = nullptr;       // the literal block: 8 words, n_lit + 1 offsets, the bytes
+    uint8_t *d_prefix = nullptr;    // the BOS piece, then U+2581
+    uint32_t n_astral = 0, n_lit = 0, bos_len = 0;
+    bool runs_ok = true;
+    uint64_t ascii_known[2] = {0, 0};
+    uint64_t lit_first[4] = {0, 0, 0, 0};
+};
+
 struct dpt_ctx {
     int device = 0;
     // workspace of the device path (ensure_workspace)

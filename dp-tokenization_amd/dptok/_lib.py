@@ -26,6 +26,8 @@ DPT_DETOK_PIECES, DPT_DETOK_SP, DPT_DETOK_BYTELEVEL = range(3)
 DPT_DECODE_STRIP_SPACE = 1
 DPT_HOST_LAYOUT_SEGS = 7
 RT_EQUAL, RT_DIFFERS = 0, 5
+PRETOK_NEEDS_HOST = 6
+DPT_E_ARG = -1
 
 
 class DptError(RuntimeError):
@@ -99,6 +101,12 @@ CALLS = {
     "dpt_debug_detok_table": (I32, [P, P, P, U32, I32, P, U32, I32, P, U64, PU64]),
     # model-input batches
     "dpt_collate": (I32, [P, P, P, P, U64, ctypes.POINTER(CollateOpts), P, P, P, P, P]),
+    # llama-mode pre-tokenization on the device
+    "dpt_pretok_create": (I32, [P, P, U32, P, U32, P, P, U32, I32, PP]),
+    "dpt_pretok_destroy": (I32, [P]),
+    "dpt_pretok_sizes": (I32, [P, P, P, U64, P, P, P]),
+    "dpt_pretok_write": (I32, [P, P, P, U64, P, P, P, P, P]),
+    "dpt_debug_pretok_table": (I32, [P, P, U32, P, U32, P, P, U32, I32, P, U64, PU64]),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -110,6 +118,9 @@ DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and n
 # Also within ABI 6 and probed for like OPTIONAL's (a set of its own: OPTIONAL less the layout call is, by
 # tests/test_pack.py, exactly the decode calls); ``collate.collate_device`` raises without it (has_collate).
 OPTIONAL_LATER = {"dpt_collate"}
+# Likewise the pre-tokenization calls: name -> argument types; ``pretok.Pretok`` raises without them (has_pretok).
+PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name}
+OPTIONAL_PRETOK = set(PRETOK_CALLS)
 
 
 def lib():
@@ -129,7 +140,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if (name in OPTIONAL or name in OPTIONAL_LATER) and not hasattr(L, name):
+        if (name in OPTIONAL or name in OPTIONAL_LATER or name in OPTIONAL_PRETOK) and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -146,6 +157,12 @@ def has_decode() -> bool:
 def has_collate() -> bool:
     """The loaded library exports dpt_collate."""
     return hasattr(lib(), "dpt_collate")
+
+
+def has_pretok() -> bool:
+    """The loaded library exports the pre-tokenization calls."""
+    L = lib()
+    return all(hasattr(L, name) for name in PRETOK_CALLS)
 
 
 def check(rc: int, what: str = "") -> None:

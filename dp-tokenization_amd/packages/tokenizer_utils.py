@@ -13,6 +13,12 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   (reference: ipdb.set_trace then max([]) at dp_tokenize.py:84), an empty word -> IndexError
   (dp_tokenize.py:49).  An unknown ``pretokenize_option`` fails at call time with NameError,
   like the reference's unbound ``pretokenize_func``.
+* ``dp_tokenize_llama(llama_tokenizer, 'llama', device_pretokenize=True)``: the same pair with llama mode's
+  pre-tokenization on the GPU (dptok/pretok.py; the rule: include/dpt.h dpt_pretok_create) for every string
+  whose words are a per-character function of its text; the strings the rule does not certify go through the
+  host path below as one sub-batch.  Same ids and exceptions; ``dp_tokenize.pretok_stats`` reads as
+  (certified, sent to the host) of the last call.  Construction checks a probe list against the tokenizer object
+  and raises DptError when a certified probe's words differ.  The default leaves the host path untouched.
 * ``dp_tokenize.batch(List[str]) -> List[List[int]]``: the batched form (one GPU launch, in both
   modes).
 * ``dp_tokenize.batch_spans(List[str]) -> List[TokenSpans]``: the batch's ids aligned to the text --
@@ -336,7 +342,158 @@ def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, sp
     return dp_tokenize, decode_dp_tokenization
 
 
-def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
+class PretokStats:
+    """``dp_tokenize.pretok_stats``: of the last batch call, the strings the device rule certified and the
+    strings sent through the host tokenizer.  Reads as the tuple (certified, sent_to_host)."""
+
+    def __init__(self):
+        self.certified = self.sent_to_host = 0
+
+    def set(self, certified: int, sent_to_host: int) -> None:
+        self.certified, self.sent_to_host = int(certified), int(sent_to_host)
+
+    def __iter__(self):
+        return iter((self.certified, self.sent_to_host))
+
+    def __eq__(self, other):
+        return tuple(self) == tuple(other)
+
+    def __repr__(self):
+        return "PretokStats(certified=%d, sent_to_host=%d)" % tuple(self)
+
+
+def _pretok_literals(tokenizer, t2i) -> List[str]:
+    """The strings a tokenizer object may treat specially inside a text -- the device rule refuses a text
+    that holds one: its ``all_special_tokens``, its added vocabulary, the pieces of its BOS / EOS / UNK / PAD
+    ids, and every vocabulary piece that reads as a control symbol (``<...>`` other than a byte piece
+    ``<0xNN>``; a SentencePiece processor wrapped without those attributes has its ``<unk>``, ``<s>``,
+    ``</s>`` only there)."""
+    inverse = {i: t for t, i in t2i.items()}
+    out = [t for t in (getattr(tokenizer, "all_special_tokens", None) or []) if isinstance(t, str)]
+    added = getattr(tokenizer, "get_added_vocab", None)
+    if callable(added):
+        out += list(added())
+    ids = [_bos_id(tokenizer)] + [getattr(tokenizer, a, None) for a in ("eos_token_id", "unk_token_id", "pad_token_id")]
+    out += [inverse[int(i)] for i in ids if i is not None and int(i) in inverse]
+    out += [t for t in t2i if len(t) >= 3 and t[0] == "<" and t[-1] == ">" and not (len(t) == 6 and t.startswith("<0x"))]
+    return [t for t in dict.fromkeys(out) if t]
+
+
+def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
+    """llama mode with the pre-tokenization on the device (dptok/pretok.py; the rule: include/dpt.h
+    dpt_pretok_create) -> (encode_csr_lists, pack_merged, stats): the strings the rule certifies never see the
+    tokenizer object, the others (pre_status 6) go through ``host.pack`` as one sub-batch and are merged back
+    by index.  Construction runs the probe list through both and raises DptError on the first certified probe
+    whose words differ: the guard for tokenizers the rule was not pinned on."""
+    import torch
+    from dptok.pretok import NEEDS_HOST, Pretok
+    from dptok.pretok_probes import PROBES
+    from dptok.engine import csr_lists
+
+    bos = _bos_id(tokenizer)
+    inverse = {i: t for t, i in t2i.items()}
+    if bos is not None and bos not in inverse:
+        raise DptError("device_pretokenize: the BOS id %d has no piece" % bos)
+    literals = _pretok_literals(tokenizer, t2i)
+    pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
+    dev = torch.device("cuda", _device())
+    stats = PretokStats()
+
+    def presplit(texts):
+        """-> device (text2, offs2 int64[n + 1], cut, pre_status) and the refused strings' indices (host)."""
+        text, offs = pack_strings(texts)
+        with torch.cuda.device(dev):
+            d_text = torch.from_numpy(text.copy()).to(dev)
+            d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
+            text2, offs2, cut, pre = pretok.presplit(d_text, d_offs)
+        pre_h = pre.cpu().numpy()
+        refused = np.flatnonzero(pre_h == NEEDS_HOST)
+        stats.set(len(texts) - len(refused), len(refused))
+        return text2, offs2, cut, refused
+
+    def encode_csr_lists(texts):
+        """Per string (ids, status), as ``Encoder.encode_packed_presplit`` gives them for ``host.pack(texts)``."""
+        n = len(texts)
+        if n == 0:
+            stats.set(0, 0)
+            return []
+        text2, offs2, cut, refused = presplit(texts)
+        n2 = int(text2.numel())
+        with torch.cuda.device(dev):
+            ids = torch.empty(max(n2, 1), dtype=torch.int32, device=dev)
+            id_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            st = torch.empty(n, dtype=torch.int32, device=dev)
+            engine.encode_device(text2.data_ptr(), n2, offs2.data_ptr(), n, ids.data_ptr(), max(n2, 1), id_off.data_ptr(),
+                                 st.data_ptr(), cut_ptr=cut.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
+                                 mode="presplit")
+            id_off_h = id_off.cpu().numpy().view(np.uint64)
+            ids_h = ids[:int(id_off_h[-1])].cpu().numpy()
+            st_h = st.cpu().numpy()
+            none = (torch.diff(offs2) == 0).cpu().numpy()   # nothing to tokenize (and every refused string)
+        out = csr_lists(ids_h, id_off_h, st_h, none=none, keep_failed=False)
+        if len(refused):
+            sub = engine.encode_packed_presplit(*host.pack([texts[i] for i in refused.tolist()]))
+            for i, r in zip(refused.tolist(), sub):
+                out[i] = r
+        return out
+
+    def pack_merged(texts):
+        """``host.pack(texts)``'s arrays (text, offs, cut, pieces per string -- here 0 or 1: only its being 0
+        is read) with the certified strings' part made on the device."""
+        n = len(texts)
+        if n == 0:
+            stats.set(0, 0)
+            return host.pack(texts)
+        text2, offs2, cut, refused = presplit(texts)
+        t2, c2, o2 = text2.cpu().numpy(), cut.cpu().numpy(), offs2.cpu().numpy()
+        lens = np.diff(o2)
+        cnt = (lens > 0).astype(np.int64)
+        if not len(refused):
+            return np.append(t2, np.uint8(0)), o2.astype(np.uint64), np.append(c2, np.uint8(0)), cnt
+        ht, ho, hc, hcnt = host.pack([texts[i] for i in refused.tolist()])
+        ho = ho.astype(np.int64)
+        lens[refused] = np.diff(ho)
+        cnt[refused] = hcnt
+        offs = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=offs[1:])
+        text = np.zeros(int(offs[-1]) + 1, dtype=np.uint8)
+        cutm = np.zeros(int(offs[-1]) + 1, dtype=np.uint8)
+        # certified strings keep their order among themselves, and so do the refused ones: two masked copies
+        sid = np.repeat(np.arange(n), lens)
+        from_host = np.zeros(n, dtype=bool)
+        from_host[refused] = True
+        m = from_host[sid]
+        text[:-1][m], cutm[:-1][m] = ht[:int(ho[-1])], hc[:int(ho[-1])]
+        text[:-1][~m], cutm[:-1][~m] = t2, c2
+        return text, offs.astype(np.uint64), cutm, cnt
+
+    # the self-check
+    got = _presplit_words(presplit, PROBES)
+    for probe, words in zip(PROBES, got):
+        if words is not None and words != merge_words(probe):
+            raise DptError("device_pretokenize: the device rule gives %r for the probe %r, the tokenizer %r: this "
+                           "tokenizer is not one the rule holds for (a normalising model, other added-token behaviour)"
+                           % (words, probe, merge_words(probe)))
+    stats.set(0, 0)
+    return encode_csr_lists, pack_merged, stats
+
+
+def _presplit_words(presplit, texts) -> List[Optional[List[str]]]:
+    """The device rule's words per text (None where it refuses the text), read back from ``presplit``."""
+    text2, offs2, cut, refused = presplit(list(texts))
+    t2, c2, o2 = text2.cpu().numpy().tobytes(), cut.cpu().numpy(), offs2.cpu().numpy().tolist()
+    no = set(refused.tolist())
+    out: List[Optional[List[str]]] = []
+    for s in range(len(o2) - 1):
+        if s in no:
+            out.append(None)
+            continue
+        starts = (np.flatnonzero(c2[o2[s]:o2[s + 1]]) + o2[s]).tolist() + [o2[s + 1]]
+        out.append([t2[a:b].decode("utf-8", "replace") for a, b in zip(starts, starts[1:])])
+    return out
+
+
+def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama", device_pretokenize=False):
     t2i: Dict[str, int] = dict(llama_tokenizer.get_vocab())
     vocab_bidict = _InverseDict(t2i)
     engine = Encoder(Vocab(t2i, _device()))
@@ -389,6 +546,26 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
                 return text, offs, "presplit", cut, cnt == 0, None
             text, offs, cut, n_words, cut_at = pack_presplit_words([pretokenize(t) for t in texts])
             return text, offs, "presplit", cut, None, lambda st: presplit_outcome(st, n_words, cut_at)
+
+        pretok_stats = None
+        if device_pretokenize:
+            # the words come from the device rule wherever it certifies the text; everything downstream is the same
+            if not (pieces.ok and not pieces.empty_piece):
+                raise DptError("device_pretokenize needs a vocabulary with dense ids and no empty piece")
+            device_lists, pack_merged, pretok_stats = _device_pretokenizer(llama_tokenizer, t2i, engine, host, pretokenize)
+
+            def encode_many(texts: Sequence[str]) -> List[List[int]]:   # noqa: F811
+                texts = list(texts)
+                return _raise_and_collect(texts, device_lists(texts))
+
+            def spans_many(texts: Sequence[str]) -> List[TokenSpans]:   # noqa: F811
+                texts = list(texts)
+                text, offs, cut, cnt = pack_merged(texts)
+                return _batch_spans(engine, texts, text, offs, "presplit", cut, none=(cnt == 0).tolist())
+
+            def pack_batch(texts):   # noqa: F811
+                text, offs, cut, cnt = pack_merged(list(texts))
+                return text, offs, "presplit", cut, cnt == 0, None
     else:
         def encode_many(texts):
             raise NameError("name 'pretokenize_func' is not defined")
@@ -413,7 +590,8 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama"):
         lambda: Detok(t2i, "sp", [b for b in [_bos_id(llama_tokenizer)] if b is not None], _device()), True, encode_many)
     return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
                            _model_inputs_surface(engine, llama_tokenizer, pack_batch), decode_batch, batch_roundtrip,
-                           "SentencePiece's", **({"host_pool": host} if pretokenize_option == "llama" else {}))
+                           "SentencePiece's", **({"host_pool": host} if pretokenize_option == "llama" else {}),
+                           **({"pretok_stats": pretok_stats} if pretokenize_option == "llama" and device_pretokenize else {}))
 
 
 BLOOM_TOKENIZER_JSON = ("{}/models--bigscience--bloom-3b/snapshots/"

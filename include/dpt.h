@@ -16,6 +16,9 @@
  *                        (packages/tokenizer_utils.py:33-50, DPT_MODE_RAW) or by
  *                        pretokenize_with_llama + merge_tokens
  *                        (packages/tokenizer_utils.py:7-31, DPT_MODE_PRESPLIT)
+ *   dpt_pretok_sizes, dpt_pretok_write <- pretokenize_with_llama + merge_tokens themselves
+ *                        (packages/tokenizer_utils.py:7-31) for the strings whose words are a per-character
+ *                        function of the text: DPT_MODE_PRESPLIT input made on the device
  *   dpt_token_histogram <- the length comparison of the S2ORC probe,
  *                        reference main_analyze_s2orc.py:269-297 (len(dp_tokenize(x)))
  *   dpt_token_spans    <- the probe's per-word comparison, reference main_analyze_s2orc.py:275-290
@@ -75,6 +78,7 @@ extern "C" {
                                         call (dpt_ctx_long_need / dpt_ctx_reserve_vocab); dpt_encode_host and
                                         dpt_dp_host grow the arena and rerun, so they never do */
 #define DPT_STATUS_INTERNAL 4        /* engine invariant violated (never expected) */
+/* (5 = DPT_RT_DIFFERS, dpt_roundtrip's rt; 6 = DPT_PRETOK_NEEDS_HOST, dpt_pretok_sizes' pre_status) */
 
 typedef struct dpt_vocab dpt_vocab;
 typedef struct dpt_ctx dpt_ctx;
@@ -376,6 +380,81 @@ typedef struct {
 int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts, const int32_t *status,
                 uint64_t n_str, const dpt_collate_opts *opts, void *input_ids, void *attention_mask,
                 void *labels, uint32_t *lengths, void *hip_stream);
+
+/*
+ * Llama-mode pre-tokenization on the device: text in, DPT_MODE_PRESPLIT input (text + cut mask) out -- what the
+ * reference's default pre-tokenizer, pretokenize_with_llama + merge_tokens (packages/tokenizer_utils.py:7-31,
+ * selected at :52, main_analyze_s2orc.py:74, :256), keeps of SentencePiece's output: the concatenation of the pieces
+ * and which pieces start with U+2581.  For a Llama-style model (identity normaliser, dummy prefix, byte fallback, no
+ * whitespace folding) both are a per-character function of the text, except on a few input classes where the merge
+ * order or the tokenizer object decides; those strings are marked DPT_PRETOK_NEEDS_HOST and left to the caller's host
+ * tokenizer.  Added within ABI 6 (DPT_ABI_VERSION unchanged): a binding that may meet an older libdpt.so probes for
+ * the symbols.
+ *
+ * A dpt_pretok is the table of one vocabulary (dpt_vocab_create's first three arguments; empty strings are ignored):
+ *   known     the code points that are a one-character piece
+ *   runs_ok   no piece of two or more characters consists of U+2581 only
+ * with the BOS piece (bos_len 0: no BOS word; at most DPT_PRETOK_MAX_BOS bytes) and n_lit literal strings -- the
+ * tokenizer's special and added tokens, which its encode matches in the text before the model runs: literal k is
+ * lit_blob[lit_off[k] - lit_off[0] .. lit_off[k+1] - lit_off[0]), at most DPT_PRETOK_MAX_LITERALS of 1 ..
+ * DPT_PRETOK_MAX_LITERAL_BYTES bytes each.  DPT_E_ARG beyond those limits.  DPT_E_VOCAB when one of the byte pieces
+ * <0x00> .. <0xFF> is missing, when a piece holds U+2581 after its first character and is not U+2581 only (the
+ * word starts would depend on the merges), or when the BOS piece is not in the vocabulary.  Immutable after creation;
+ * may be shared by threads and streams.
+ *
+ * A string is certified (pre_status[s] = 0) unless
+ *   - its first byte is ' ' (the tokenizer objects disagree about a leading space),
+ *   - it holds U+2581 (indistinguishable from a space afterwards),
+ *   - it holds one of the literals as a substring (the tokenizer object decides what they become),
+ *   - it holds two consecutive spaces while !runs_ok (a multi-U+2581 piece would swallow word starts),
+ *   - it is not well-formed UTF-8: a truncated sequence (at the string's end too: the next string's bytes never
+ *     complete it), an overlong form, a surrogate, a value above U+10FFFF, a stray continuation byte,
+ *   - its pre-split form would reach 4 GiB;
+ * then pre_status[s] = DPT_PRETOK_NEEDS_HOST, out_len[s] = 0 and nothing is written for it.  On the recorded
+ * SentencePiece cases (tests/golden/sp_llama_cases.json.gz: two tokenizer objects, 565 texts each) the rule certifies
+ * 292 texts per tokenizer, all with the recorded words, and refuses every one of the 236 texts on which the two
+ * tokenizer objects disagree.  The rule is pinned on that model only: a caller with another tokenizer checks it first
+ * (the Python adapter runs a probe list through both at construction).
+ * The pre-split form of a certified string: the BOS piece's bytes, one word; then, only when the text is not empty,
+ * U+2581 opening a word; then per character: ' ' -> U+2581 opening a word, a known character -> its own bytes, any
+ * other character -> <0xNN> (upper-case hex) for each of its UTF-8 bytes.  cut_mask is 1 at the first byte of the
+ * output and at the first byte of every word-opening U+2581, 0 elsewhere.  An empty text gives the BOS word alone,
+ * and nothing at all (length 0, status 0) without a BOS piece.
+ *   dpt_pretok_sizes  out_len[s] (uint64) = the bytes of string s's pre-split form, pre_status[s] (int32) as above
+ *   dpt_pretok_write  the form of string s at out_text[out_off[s] - out_off[0] ..] and its mask at the same index of
+ *                     cut_mask; out_off (n_str + 1 entries; out_off[0] need not be 0) is the caller's prefix sum of
+ *                     out_len, pre_status what the sizes pass wrote.  Every store stays inside the string's own
+ *                     [out_off[s], out_off[s+1]) whatever the bytes hold
+ * text and str_off as dpt_encode's (str_off[0] need not be 0, no alignment is assumed); no load goes beyond a
+ * string's last byte.  DEVICE pointers on the table's device; stream-ordered on hip_stream, never synchronise,
+ * allocate nothing and need no dpt_ctx: any number of calls may be in flight on one dpt_pretok.  DPT_E_ARG, before any
+ * device work, for a null pointer; n_str == 0 launches nothing.  Strings < 4 GiB, str_off and out_off monotone (the
+ * device calls cannot check device-resident offsets).  No host-buffer form: the product feeds dpt_encode on the device.
+ */
+typedef struct dpt_pretok dpt_pretok;
+#define DPT_PRETOK_NEEDS_HOST 6   /* per-string value of pre_status */
+#define DPT_PRETOK_MAX_LITERALS 32
+#define DPT_PRETOK_MAX_LITERAL_BYTES 64
+#define DPT_PRETOK_MAX_BOS 61
+int dpt_pretok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
+                      uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int device,
+                      dpt_pretok **out);
+int dpt_pretok_destroy(dpt_pretok *p);
+int dpt_pretok_sizes(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str, uint64_t *out_len,
+                     int32_t *pre_status, void *hip_stream);
+int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                     const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
+                     void *hip_stream);
+/* TEST-ONLY, needs no device.  The bytes dpt_pretok_create would upload for these arguments, built on the host
+ * (tests/pretok_ref.py holds a model of the format).  which: 0 the known set below U+10000 as a bitmap (2048 uint32:
+ * bit cp & 31 of word cp >> 5), 1 the known code points from U+10000 up (uint32, ascending), 2 the literal block
+ * (8 uint32: the bitmap of the literals' first bytes; n_lit + 1 uint32: their offsets from 0; their bytes), 3 the
+ * prefix (the BOS piece, then U+2581), 4 DPT_PRETOK_SCALAR_INTS int64: runs_ok, the number of known code points,
+ * n_lit, bos_len.  *size = the table's bytes, always; it is copied to out (nullable) when cap >= *size, else DPT_E_CAP. */
+#define DPT_PRETOK_SCALAR_INTS 4
+int dpt_debug_pretok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
+                           uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int which,
+                           void *out, uint64_t cap, uint64_t *size);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
