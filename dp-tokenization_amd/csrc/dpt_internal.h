@@ -1,5 +1,6 @@
 // Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp,
-// dpt_pretok.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip, dpt_pretok.hip).
+// dpt_pretok.cpp, dpt_bytelevel.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip,
+// dpt_pretok.hip, dpt_bytelevel.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -354,6 +355,37 @@ struct PretokLaunch {
     uint8_t *cut_mask;
 };
 hipError_t launch_pretok(const PretokLaunch &p, hipStream_t stream);
+
+// Separator table of a byte-level split (dpt_bytelevel.cpp build_bytelevel_tables; include/dpt.h dpt_bytelevel_create),
+// as dpt_bytelevel_create keeps and uploads it.
+struct ByteLevelTables {
+    uint64_t ascii[2] = {0, 0};     // the separators below U+0080: bit cp & 63 of word cp >> 6
+    std::vector<uint32_t> high;     // the separators from U+0080 up, ascending, each once
+    uint32_t n_sep = 0;             // distinct separators
+};
+// returns 0 or an error message (DPT_E_ARG); calls no HIP function
+const char *build_bytelevel_tables(const uint32_t *sep_cps, uint32_t n_sep, ByteLevelTables *out);
+
+// One launch of the byte-level split kernels (dpt_bytelevel.hip; include/dpt.h dpt_bytelevel_sizes,
+// dpt_bytelevel_write): every pointer a device pointer.
+struct ByteLevelLaunch {
+    bool write;                  // false: the sizes pass
+    const uint8_t *text;
+    const uint64_t *str_off;
+    uint64_t n_str;
+    // the table (read by write alone: the sizes do not depend on the separators)
+    uint64_t ascii_sep[2];
+    const uint32_t *high;        // n_high entries, ascending (null when 0)
+    uint32_t n_high;
+    // sizes
+    uint64_t *out_len;
+    int32_t *pre_status;         // written by sizes, read by write
+    // write
+    uint8_t *out_text;
+    const uint64_t *out_off;
+    uint8_t *cut_mask;
+};
+hipError_t launch_bytelevel(const ByteLevelLaunch &p, hipStream_t stream);
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

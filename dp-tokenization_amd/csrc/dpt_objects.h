@@ -41,6 +41,15 @@ struct dpt_pretok {
     uint64_t lit_first[4] = {0, 0, 0, 0};
 };
 
+// The device copy of a byte-level split's separator table (dpt_bytelevel.cpp build_bytelevel_tables): the separators
+// below U+0080 travel with the kernel arguments.
+struct dpt_bytelevel {
+    int device = 0;
+    uint32_t *d_high = nullptr;     // n_high separators from U+0080 up, ascending (null: none)
+    uint32_t n_high = 0;
+    uint64_t ascii[2] = {0, 0};
+};
+
 struct dpt_ctx {
     int device = 0;
     // workspace of the device path (ensure_workspace)

@@ -4,6 +4,7 @@ Public surface:
     Vocab, Encoder          batch engine (engine.py)
     Detok                   ids back to bytes and the round-trip check (detok.py)
     Pretok                  llama mode's pre-split text made on the device (pretok.py)
+    ByteLevelSplit          the BLOOM adapter's ATOMS input made on the device (bytelevel.py)
     collate                 padded model inputs from an encoded batch, on the device (collate.py: the
                             ``collate_device`` / ``model_inputs`` calls; imported on demand, it needs torch)
     pack_strings, TokenSpans  host arrays in and out of the engine (pack.py, pure numpy)
@@ -13,12 +14,13 @@ The reference-compatible names (dp_tokenize_llama, compute_shortest_tokenization
 live in the sibling ``packages`` / ``inspect_tokenizer`` modules of this directory.
 """
 from ._lib import DptError, RT_DIFFERS, RT_EQUAL, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
+from .bytelevel import BLOOM_SEPARATORS, ByteLevelSplit
 from .detok import Detok
 from .engine import Encoder, Vocab, raise_and_collect, raise_for_status
 from .pack import TokenSpans, pack_strings
 from .pretok import Pretok
 
-__all__ = ["Vocab", "Encoder", "Detok", "Pretok", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
+__all__ = ["Vocab", "Encoder", "Detok", "Pretok", "ByteLevelSplit", "BLOOM_SEPARATORS", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
            "STATUS_OK", "STATUS_NO_TOKENIZATION", "STATUS_EMPTY_WORD", "STATUS_TOO_LONG", "STATUS_INTERNAL"]
 
 

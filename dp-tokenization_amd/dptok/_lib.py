@@ -107,6 +107,12 @@ CALLS = {
     "dpt_pretok_sizes": (I32, [P, P, P, U64, P, P, P]),
     "dpt_pretok_write": (I32, [P, P, P, U64, P, P, P, P, P]),
     "dpt_debug_pretok_table": (I32, [P, P, U32, P, U32, P, P, U32, I32, P, U64, PU64]),
+    # byte-level (BLOOM) pre-tokenization on the device
+    "dpt_bytelevel_create": (I32, [P, U32, I32, PP]),
+    "dpt_bytelevel_destroy": (I32, [P]),
+    "dpt_bytelevel_sizes": (I32, [P, P, P, U64, P, P, P]),
+    "dpt_bytelevel_write": (I32, [P, P, P, U64, P, P, P, P, P]),
+    "dpt_debug_bytelevel_table": (I32, [P, U32, I32, P, U64, PU64]),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -121,6 +127,9 @@ OPTIONAL_LATER = {"dpt_collate"}
 # Likewise the pre-tokenization calls: name -> argument types; ``pretok.Pretok`` raises without them (has_pretok).
 PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name}
 OPTIONAL_PRETOK = set(PRETOK_CALLS)
+# And the byte-level split calls; ``bytelevel.ByteLevelSplit`` raises without them (has_bytelevel).
+BYTELEVEL_CALLS = {name: CALLS[name][1] for name in CALLS if "_bytelevel_" in name}
+OPTIONAL_BYTELEVEL = set(BYTELEVEL_CALLS)
 
 
 def lib():
@@ -140,7 +149,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if (name in OPTIONAL or name in OPTIONAL_LATER or name in OPTIONAL_PRETOK) and not hasattr(L, name):
+        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -163,6 +172,12 @@ def has_pretok() -> bool:
     """The loaded library exports the pre-tokenization calls."""
     L = lib()
     return all(hasattr(L, name) for name in PRETOK_CALLS)
+
+
+def has_bytelevel() -> bool:
+    """The loaded library exports the byte-level split calls."""
+    L = lib()
+    return all(hasattr(L, name) for name in BYTELEVEL_CALLS)
 
 
 def check(rc: int, what: str = "") -> None:

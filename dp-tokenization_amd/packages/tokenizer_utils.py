@@ -19,6 +19,10 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   host path below as one sub-batch.  Same ids and exceptions; ``dp_tokenize.pretok_stats`` reads as
   (certified, sent to the host) of the last call.  Construction checks a probe list against the tokenizer object
   and raises DptError when a certified probe's words differ.  The default leaves the host path untouched.
+* ``dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=True)``: the BLOOM adapter with its words and
+  atoms made on the GPU too (dptok/bytelevel.py; the rule: include/dpt.h dpt_bytelevel_create).  The rule is exact, so
+  only text that is not well-formed UTF-8 goes through the host path; construction checks the pre-tokenizer's shape,
+  the byte alphabet and a probe list, and raises DptError on the first difference.
 * ``dp_tokenize.batch(List[str]) -> List[List[int]]``: the batched form (one GPU launch, in both
   modes).
 * ``dp_tokenize.batch_spans(List[str]) -> List[TokenSpans]``: the batch's ids aligned to the text --
@@ -379,23 +383,16 @@ def _pretok_literals(tokenizer, t2i) -> List[str]:
     return [t for t in dict.fromkeys(out) if t]
 
 
-def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
-    """llama mode with the pre-tokenization on the device (dptok/pretok.py; the rule: include/dpt.h
-    dpt_pretok_create) -> (encode_csr_lists, pack_merged, stats): the strings the rule certifies never see the
-    tokenizer object, the others (pre_status 6) go through ``host.pack`` as one sub-batch and are merged back
-    by index.  Construction runs the probe list through both and raises DptError on the first certified probe
-    whose words differ: the guard for tokenizers the rule was not pinned on."""
+def _device_split_paths(split, mode, engine, host_pack):
+    """The batch paths of an adapter whose pre-tokenization runs on the device.  ``split(d_text, d_offs)`` -> device
+    (text2, offs2 int64[n + 1], cut, pre_status): ``Pretok.presplit`` or ``ByteLevelSplit.split``;  ``host_pack(texts)``
+    -> the host path's (text, offs, cut, cnt) for ``mode``, cnt[i] == 0: string i has no words.  The strings the
+    device refuses (pre_status 6) go through ``host_pack`` as one sub-batch and are merged back by index.
+    -> (presplit, encode_csr_lists, pack_merged, stats)."""
     import torch
-    from dptok.pretok import NEEDS_HOST, Pretok
-    from dptok.pretok_probes import PROBES
+    from dptok.pretok import NEEDS_HOST
     from dptok.engine import csr_lists
 
-    bos = _bos_id(tokenizer)
-    inverse = {i: t for t, i in t2i.items()}
-    if bos is not None and bos not in inverse:
-        raise DptError("device_pretokenize: the BOS id %d has no piece" % bos)
-    literals = _pretok_literals(tokenizer, t2i)
-    pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
     dev = torch.device("cuda", _device())
     stats = PretokStats()
 
@@ -405,14 +402,14 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
         with torch.cuda.device(dev):
             d_text = torch.from_numpy(text.copy()).to(dev)
             d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
-            text2, offs2, cut, pre = pretok.presplit(d_text, d_offs)
+            text2, offs2, cut, pre = split(d_text, d_offs)
         pre_h = pre.cpu().numpy()
         refused = np.flatnonzero(pre_h == NEEDS_HOST)
         stats.set(len(texts) - len(refused), len(refused))
         return text2, offs2, cut, refused
 
     def encode_csr_lists(texts):
-        """Per string (ids, status), as ``Encoder.encode_packed_presplit`` gives them for ``host.pack(texts)``."""
+        """Per string (ids, status), as the host path's one launch over ``host_pack(texts)`` gives them."""
         n = len(texts)
         if n == 0:
             stats.set(0, 0)
@@ -425,32 +422,34 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
             st = torch.empty(n, dtype=torch.int32, device=dev)
             engine.encode_device(text2.data_ptr(), n2, offs2.data_ptr(), n, ids.data_ptr(), max(n2, 1), id_off.data_ptr(),
                                  st.data_ptr(), cut_ptr=cut.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
-                                 mode="presplit")
+                                 mode=mode)
             id_off_h = id_off.cpu().numpy().view(np.uint64)
             ids_h = ids[:int(id_off_h[-1])].cpu().numpy()
             st_h = st.cpu().numpy()
             none = (torch.diff(offs2) == 0).cpu().numpy()   # nothing to tokenize (and every refused string)
         out = csr_lists(ids_h, id_off_h, st_h, none=none, keep_failed=False)
         if len(refused):
-            sub = engine.encode_packed_presplit(*host.pack([texts[i] for i in refused.tolist()]))
+            text, offs, cutm, cnt = host_pack([texts[i] for i in refused.tolist()])
+            h_ids, h_off, h_st, _ = engine.encode_csr(text, offs, mode=mode, cut_mask=cutm)
+            sub = csr_lists(h_ids, h_off, h_st, none=(np.asarray(cnt) == 0), keep_failed=False)
             for i, r in zip(refused.tolist(), sub):
                 out[i] = r
         return out
 
     def pack_merged(texts):
-        """``host.pack(texts)``'s arrays (text, offs, cut, pieces per string -- here 0 or 1: only its being 0
-        is read) with the certified strings' part made on the device."""
+        """``host_pack(texts)``'s arrays (text, offs, cut, words per string -- here 0 or 1 for the strings made on the
+        device: only its being 0 is read) with every string the device takes made there."""
         n = len(texts)
         if n == 0:
             stats.set(0, 0)
-            return host.pack(texts)
+            return host_pack(texts)
         text2, offs2, cut, refused = presplit(texts)
         t2, c2, o2 = text2.cpu().numpy(), cut.cpu().numpy(), offs2.cpu().numpy()
         lens = np.diff(o2)
         cnt = (lens > 0).astype(np.int64)
         if not len(refused):
             return np.append(t2, np.uint8(0)), o2.astype(np.uint64), np.append(c2, np.uint8(0)), cnt
-        ht, ho, hc, hcnt = host.pack([texts[i] for i in refused.tolist()])
+        ht, ho, hc, hcnt = host_pack([texts[i] for i in refused.tolist()])
         ho = ho.astype(np.int64)
         lens[refused] = np.diff(ho)
         cnt[refused] = hcnt
@@ -458,7 +457,7 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
         np.cumsum(lens, out=offs[1:])
         text = np.zeros(int(offs[-1]) + 1, dtype=np.uint8)
         cutm = np.zeros(int(offs[-1]) + 1, dtype=np.uint8)
-        # certified strings keep their order among themselves, and so do the refused ones: two masked copies
+        # the device's strings keep their order among themselves, and so do the refused ones: two masked copies
         sid = np.repeat(np.arange(n), lens)
         from_host = np.zeros(n, dtype=bool)
         from_host[refused] = True
@@ -466,6 +465,26 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
         text[:-1][m], cutm[:-1][m] = ht[:int(ho[-1])], hc[:int(ho[-1])]
         text[:-1][~m], cutm[:-1][~m] = t2, c2
         return text, offs.astype(np.uint64), cutm, cnt
+
+    return presplit, encode_csr_lists, pack_merged, stats
+
+
+def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
+    """llama mode with the pre-tokenization on the device (dptok/pretok.py; the rule: include/dpt.h
+    dpt_pretok_create) -> (encode_csr_lists, pack_merged, stats): the strings the rule certifies never see the
+    tokenizer object, the others (pre_status 6) go through ``host.pack`` as one sub-batch and are merged back
+    by index.  Construction runs the probe list through both and raises DptError on the first certified probe
+    whose words differ: the guard for tokenizers the rule was not pinned on."""
+    from dptok.pretok import Pretok
+    from dptok.pretok_probes import PROBES
+
+    bos = _bos_id(tokenizer)
+    inverse = {i: t for t, i in t2i.items()}
+    if bos is not None and bos not in inverse:
+        raise DptError("device_pretokenize: the BOS id %d has no piece" % bos)
+    literals = _pretok_literals(tokenizer, t2i)
+    pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
+    presplit, encode_csr_lists, pack_merged, stats = _device_split_paths(pretok.presplit, "presplit", engine, host.pack)
 
     # the self-check
     got = _presplit_words(presplit, PROBES)
@@ -478,8 +497,9 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
     return encode_csr_lists, pack_merged, stats
 
 
-def _presplit_words(presplit, texts) -> List[Optional[List[str]]]:
-    """The device rule's words per text (None where it refuses the text), read back from ``presplit``."""
+def _presplit_words(presplit, texts, bit: int = 0xFF) -> List[Optional[List[str]]]:
+    """The device rule's words per text (None where it refuses the text), read back from ``presplit``; ``bit``:
+    the bits of the cut mask that open a word (ATOMS masks: 1)."""
     text2, offs2, cut, refused = presplit(list(texts))
     t2, c2, o2 = text2.cpu().numpy().tobytes(), cut.cpu().numpy(), offs2.cpu().numpy().tolist()
     no = set(refused.tolist())
@@ -488,7 +508,7 @@ def _presplit_words(presplit, texts) -> List[Optional[List[str]]]:
         if s in no:
             out.append(None)
             continue
-        starts = (np.flatnonzero(c2[o2[s]:o2[s + 1]]) + o2[s]).tolist() + [o2[s + 1]]
+        starts = (np.flatnonzero(c2[o2[s]:o2[s + 1]] & bit) + o2[s]).tolist() + [o2[s + 1]]
         out.append([t2[a:b].decode("utf-8", "replace") for a, b in zip(starts, starts[1:])])
     return out
 
@@ -598,7 +618,56 @@ BLOOM_TOKENIZER_JSON = ("{}/models--bigscience--bloom-3b/snapshots/"
                         "52bc5b43010b4844513826b8be3f78c7344c37d7/tokenizer.json")
 
 
-def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
+BLOOM_SPLIT_PATTERN = " ?[^(\\s|[.,!?…。，、।۔،])]+"
+
+
+def _device_bytelevel(tokenizer, vocab_to_index, engine, host_pack, pretokenize):
+    """The BLOOM adapter with its pre-tokenization on the device (dptok/bytelevel.py; the rule: include/dpt.h
+    dpt_bytelevel_create) -> (encode_csr_lists, pack_merged, stats).  The rule is exact for one pre-tokenizer and
+    one alphabet, so construction checks both: the tokenizer's pre-tokenizer must be Sequence[Split(Regex(
+    BLOOM_SPLIT_PATTERN), isolated), ByteLevel(add_prefix_space=False, use_regex=False)], every character of the
+    byte alphabet must be a vocabulary entry that ``convert_ids_to_tokens`` gives back unchanged, and the probe list
+    must come out of the device rule as out of ``pre_tokenize_str``.  DptError names the first difference."""
+    import json
+    from dptok.bytelevel import BLOOM_SEPARATORS, ByteLevelSplit, bytes_to_unicode
+    from dptok.bytelevel_probes import PROBES
+
+    try:
+        pre = json.loads(tokenizer._tokenizer.to_str()).get("pre_tokenizer")
+    except Exception as e:   # noqa: BLE001
+        raise DptError("device_pretokenize: the tokenizer's pre-tokenizer cannot be read (%s)" % e)
+    steps = pre.get("pretokenizers") if isinstance(pre, dict) and pre.get("type") == "Sequence" else None
+    if not (isinstance(steps, list) and len(steps) == 2 and all(isinstance(x, dict) for x in steps)):
+        raise DptError("device_pretokenize: the pre-tokenizer is not Sequence[Split, ByteLevel]: %r" % (pre,))
+    split, level = steps
+    for what, got, want in (("first step", split.get("type"), "Split"), ("Split pattern", split.get("pattern"), {"Regex": BLOOM_SPLIT_PATTERN}),
+                            ("Split behavior", split.get("behavior"), "Isolated"), ("Split invert", bool(split.get("invert")), False),
+                            ("second step", level.get("type"), "ByteLevel"),
+                            ("ByteLevel add_prefix_space", bool(level.get("add_prefix_space")), False),
+                            ("ByteLevel use_regex", bool(level.get("use_regex")), False)):
+        if got != want:
+            raise DptError("device_pretokenize: the pre-tokenizer's %s is %r, the device rule needs %r" % (what, got, want))
+    alphabet = bytes_to_unicode()
+    for b in range(256):
+        if alphabet[b] not in vocab_to_index:
+            raise DptError("device_pretokenize: the byte alphabet's %r (byte 0x%02X) is not in the vocabulary" % (alphabet[b], b))
+    back = tokenizer.convert_ids_to_tokens([vocab_to_index[alphabet[b]] for b in range(256)])
+    for b in range(256):
+        if back[b] != alphabet[b]:
+            raise DptError("device_pretokenize: convert_ids_to_tokens gives %r for the byte alphabet's %r (byte 0x%02X)"
+                           % (back[b], alphabet[b], b))
+    splitter = ByteLevelSplit(BLOOM_SEPARATORS, _device())
+    presplit, encode_csr_lists, pack_merged, stats = _device_split_paths(splitter.split, "atoms", engine, host_pack)
+    got = _presplit_words(presplit, PROBES, bit=1)
+    for probe, words in zip(PROBES, got):
+        if words != pretokenize(probe):
+            raise DptError("device_pretokenize: the device rule gives %r for the probe %r, the tokenizer %r: this "
+                           "pre-tokenizer is not the one the rule holds for" % (words, probe, pretokenize(probe)))
+    stats.set(0, 0)
+    return encode_csr_lists, pack_merged, stats
+
+
+def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=False):
     """BLOOM byte-level adapter (reference tokenizer_utils.py:98-181).
 
     * the vocabulary is ``tokenizer.json``'s ``model.vocab`` with ids = its **enumeration
@@ -611,6 +680,13 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
     The reference's ``merges`` -> ``token_to_source_merge`` map (:113-116) feeds only the unused
     ``unwind_to_base_tokenization``; merges are parsed here in either tokenizer.json form
     ("a b" strings or [a, b] pairs) and otherwise unused.
+
+    ``device_pretokenize=True``: the words and atoms are made on the GPU as well (dptok/bytelevel.py; the rule:
+    include/dpt.h dpt_bytelevel_create) -- text up, two kernels, the atoms-mode encode, ids back; the tokenizer object
+    is asked only at construction (``_device_bytelevel``: DptError unless its pre-tokenizer and alphabet are the ones
+    the rule is exact for) and for text that is not well-formed UTF-8, which goes through the host path as one
+    sub-batch.  Same ids and exceptions; ``dp_tokenize.pretok_stats`` reads as (made on the device, sent to the host)
+    of the last call.  The default leaves the host path untouched.
     """
     import json
 
@@ -648,6 +724,27 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
         text, offs, cut = pack_word_atoms(batch)
         return text, offs, "atoms", cut, [not words for words in batch], None
 
+    pretok_stats = None
+    if device_pretokenize:
+        def host_pack(texts):
+            batch = [[atoms_of(w) for w in pretokenize(t)] for t in texts]
+            return (*pack_word_atoms(batch), np.fromiter((len(words) for words in batch), dtype=np.int64, count=len(batch)))
+
+        device_lists, pack_merged, pretok_stats = _device_bytelevel(bloom_tokenizer, vocab_to_index, engine, host_pack, pretokenize)
+
+        def encode_many(texts: Sequence[str]) -> List[List[int]]:   # noqa: F811
+            texts = list(texts)
+            return _raise_and_collect(texts, device_lists(texts))
+
+        def spans_many(texts: Sequence[str]) -> List[TokenSpans]:   # noqa: F811
+            texts = list(texts)
+            text, offs, cut, cnt = pack_merged(texts)
+            return _batch_spans(engine, texts, text, offs, "atoms", cut, none=(cnt == 0).tolist())
+
+        def pack_batch(texts):   # noqa: F811
+            text, offs, cut, cnt = pack_merged(list(texts))
+            return text, offs, "atoms", cut, cnt == 0, None
+
     def dp_tokenize(input_str) -> List[int]:
         return encode_many([input_str])[0]
 
@@ -660,4 +757,5 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR):
                                                     encode_many)
     return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
                            _model_inputs_surface(engine, bloom_tokenizer, pack_batch), decode_batch, batch_roundtrip,
-                           "ByteLevel's", vocab_to_index=vocab_to_index)
+                           "ByteLevel's", vocab_to_index=vocab_to_index,
+                           **({"pretok_stats": pretok_stats} if device_pretokenize else {}))

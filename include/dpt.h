@@ -19,6 +19,8 @@
  *   dpt_pretok_sizes, dpt_pretok_write <- pretokenize_with_llama + merge_tokens themselves
  *                        (packages/tokenizer_utils.py:7-31) for the strings whose words are a per-character
  *                        function of the text: DPT_MODE_PRESPLIT input made on the device
+ *   dpt_bytelevel_sizes, dpt_bytelevel_write <- the BLOOM adapter's pre_tokenize_str + per-character atoms
+ *                        (packages/tokenizer_utils.py:155-162): DPT_MODE_ATOMS input made on the device
  *   dpt_token_histogram <- the length comparison of the S2ORC probe,
  *                        reference main_analyze_s2orc.py:269-297 (len(dp_tokenize(x)))
  *   dpt_token_spans    <- the probe's per-word comparison, reference main_analyze_s2orc.py:275-290
@@ -455,6 +457,62 @@ int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *s
 int dpt_debug_pretok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
                            uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int which,
                            void *out, uint64_t cap, uint64_t *size);
+
+/*
+ * Byte-level pre-tokenization on the device: text in, DPT_MODE_ATOMS input (text + cut mask) out -- what the BLOOM
+ * adapter (packages/tokenizer_utils.py dp_tokenize_bloom) builds on the host from the tokenizer's pre-tokenizer,
+ * Sequence[Split(Regex(" ?[^(\s|[.,!?...])]+"), isolated), ByteLevel(add_prefix_space=False, use_regex=False)], and a
+ * dictionary lookup per character.  Both halves are local functions of the text, so the rule is exact: only text
+ * that is not well-formed UTF-8 is left to the caller's host path.  Added within ABI 6 (DPT_ABI_VERSION unchanged): a
+ * binding that may meet an older libdpt.so probes for the symbols.
+ *
+ * A dpt_bytelevel is the separator set SEP of one split of the family "optional U+0020, then one or more
+ * non-separators, isolated": n_sep (1 .. DPT_BYTELEVEL_MAX_SEPARATORS) Unicode scalar values, U+0020 among them,
+ * duplicates collapse.  DPT_E_ARG for a null pointer, a count outside that range, a value that is not a scalar value
+ * (a surrogate, above U+10FFFF) or a set without U+0020.  Immutable after creation; may be shared by threads and
+ * streams.  BLOOM's set has 39 members (dptok/bytelevel.py BLOOM_SEPARATORS).
+ *
+ * Word starts, over the characters c[0..n) of a string: a space c[i] == U+0020 is ABSORBED when c[i+1] exists and
+ * is not in SEP.  A word starts at i == 0, at an absorbed space, at a non-separator whose predecessor is a separator
+ * that is not an absorbed space, and at a separator that is not absorbed and whose predecessor is a non-separator;
+ * nowhere else.  Runs of unabsorbed separators form one word ("a  b" -> "a", " ", " b"); the empty string has none.
+ * Atoms: every input byte is one atom, its GPT-2 bytes-to-unicode character (DPT_DETOK_BYTELEVEL's alphabet): bytes
+ * 0x21 .. 0x7E stay one byte, every other byte becomes a two-byte UTF-8 character (U+00A1 .. U+0143).
+ * The output is DPT_MODE_ATOMS input: the atoms' UTF-8, and a cut mask that is 3 at the first byte of a word's first
+ * atom, 2 at the first byte of every other atom, 0 at an atom's second byte.
+ *
+ * pre_status[s] = 0 unless the string is not well-formed UTF-8 (the classes dpt_pretok_sizes refuses: a truncated
+ * sequence -- at the string's end too: the next string's bytes never complete it --, an overlong form, a surrogate,
+ * a value above U+10FFFF, a stray continuation byte) or its form would reach 4 GiB; then pre_status[s] =
+ * DPT_PRETOK_NEEDS_HOST, out_len[s] = 0 and nothing is written for it.
+ *   dpt_bytelevel_sizes  out_len[s] (uint64) = the bytes of string s's ATOMS form, pre_status[s] (int32) as above
+ *   dpt_bytelevel_write  the form of string s at out_text[out_off[s] - out_off[0] ..] and its mask at the same index
+ *                        of cut_mask; out_off (n_str + 1 entries; out_off[0] need not be 0) is the caller's prefix
+ *                        sum of out_len, pre_status what the sizes pass wrote.  Every store stays inside the
+ *                        string's own [out_off[s], out_off[s+1]) whatever the bytes hold
+ * text and str_off as dpt_encode's (str_off[0] need not be 0, no alignment is assumed); no load goes beyond a
+ * string's last byte.  DEVICE pointers on the table's device; stream-ordered on hip_stream, never synchronise,
+ * allocate nothing and need no dpt_ctx: any number of calls may be in flight on one dpt_bytelevel.  DPT_E_ARG, before
+ * any device work, for a null pointer; n_str == 0 launches nothing.  Strings < 4 GiB, str_off and out_off monotone.
+ * No host-buffer form: the product feeds dpt_encode on the device.
+ */
+typedef struct dpt_bytelevel dpt_bytelevel;
+#define DPT_BYTELEVEL_MAX_SEPARATORS 256
+int dpt_bytelevel_create(const uint32_t *sep_cps, uint32_t n_sep, int device, dpt_bytelevel **out);
+int dpt_bytelevel_destroy(dpt_bytelevel *p);
+int dpt_bytelevel_sizes(const dpt_bytelevel *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                        uint64_t *out_len, int32_t *pre_status, void *hip_stream);
+int dpt_bytelevel_write(const dpt_bytelevel *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                        const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
+                        void *hip_stream);
+/* TEST-ONLY, needs no device.  What dpt_bytelevel_create would keep and upload for these arguments, built on the
+ * host (tests/bytelevel_ref.py holds a model of the format).  which: 0 the separators below U+0080 as a bitmap (2
+ * uint64: bit cp & 63 of word cp >> 6), 1 the separators from U+0080 up (uint32, ascending, each once), 2
+ * DPT_BYTELEVEL_SCALAR_INTS int64: the distinct separators, those from U+0080 up.  *size = the table's bytes, always;
+ * it is copied to out (nullable) when cap >= *size, else DPT_E_CAP. */
+#define DPT_BYTELEVEL_SCALAR_INTS 2
+int dpt_debug_bytelevel_table(const uint32_t *sep_cps, uint32_t n_sep, int which, void *out, uint64_t cap,
+                              uint64_t *size);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
