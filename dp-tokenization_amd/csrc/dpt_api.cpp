@@ -117,14 +117,6 @@ void launch_vocab(const dpt_vocab *v, dpt::EncodeLaunch *p) {
     p->ws_node = v->ws_node; p->ws_base = v->ws_base; p->ws_id = v->ws_id;
 }
 
-// A host table as a fresh device buffer (an empty table: none, *d stays null).
-template <typename D, typename T>
-hipError_t upload(D **d, const std::vector<T> &h) {
-    if (h.empty()) return hipSuccess;
-    const hipError_t e = hipMalloc((void **)d, h.size() * sizeof(T));
-    return e != hipSuccess ? e : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-}
-
 // dpt_vocab_destroy, and dpt_vocab_create's exit after a failed upload
 void vocab_free(dpt_vocab *v) {
     DeviceGuard g(v->device);
@@ -133,7 +125,11 @@ void vocab_free(dpt_vocab *v) {
     delete v;
 }
 
-// dpt_vocab_create, dpt_detok_create, dpt_ctx_create (no table): a device of this index exists and the token table's offsets ascend.
+}  // namespace
+
+namespace dpt {
+void set_last_error(const std::string &msg) { g_err = msg; }   // (dpt_rccl.cpp, dpt_vocab.cpp)
+
 int check_device_and_table(int device, const uint64_t *tok_off, uint32_t n_tok) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(DPT_E_NODEV, "no HIP device");
@@ -142,11 +138,6 @@ int check_device_and_table(int device, const uint64_t *tok_off, uint32_t n_tok) 
         if (tok_off[t + 1] < tok_off[t]) return fail(DPT_E_ARG, "tok_off not monotone");
     return DPT_OK;
 }
-
-}  // namespace
-
-namespace dpt {
-void set_last_error(const std::string &msg) { g_err = msg; }   // (dpt_rccl.cpp, dpt_vocab.cpp)
 }
 
 int dpt::encode_impl(dpt_ctx *c, const dpt_vocab *v, const EncodeRequest &r) {
@@ -487,84 +478,6 @@ int dpt_roundtrip(const dpt_detok *d, const int32_t *ids, const uint64_t *id_off
     p.text = text; p.str_off = str_off; p.result = rt; p.first_diff = first_diff;
     if (const int rc = decode_check(&p, d, flags)) return rc;
     return decode_launch(p, d, hip_stream);
-}
-
-int dpt_pretok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
-                      uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int device,
-                      dpt_pretok **out) {
-    if (!out || !tok_off || (!utf8_blob && n_tok && tok_off[n_tok] != tok_off[0]) || (bos_len && !bos_piece) ||
-        (n_lit && (!lit_blob || !lit_off)))
-        return fail(DPT_E_ARG, "null argument");
-    *out = nullptr;
-    if (const int rc = check_device_and_table(device, tok_off, n_tok)) return rc;
-    dpt::PretokTables t;
-    int code = DPT_OK;
-    if (const char *err = dpt::build_pretok_tables(utf8_blob, tok_off, n_tok, bos_piece, bos_len, lit_blob, lit_off, n_lit, &t, &code))
-        return fail(code, err);
-    DeviceGuard g(device);
-    dpt_pretok *p = new (std::nothrow) dpt_pretok();
-    if (!p) return fail(DPT_E_ARG, "out of host memory");
-    p->device = device; p->n_astral = (uint32_t)t.astral.size(); p->n_lit = t.n_lit; p->bos_len = t.bos_len; p->runs_ok = t.runs_ok;
-    uint32_t first[8];
-    memcpy(first, t.lit.data(), sizeof(first));
-    for (int k = 0; k < 2; k++) p->ascii_known[k] = t.bmp[2 * k] | (uint64_t)t.bmp[2 * k + 1] << 32;
-    for (int k = 0; k < 4; k++) p->lit_first[k] = first[2 * k] | (uint64_t)first[2 * k + 1] << 32;
-    hipError_t e = upload(&p->d_bmp, t.bmp);
-    if (e == hipSuccess) e = upload(&p->d_astral, t.astral);
-    if (e == hipSuccess) e = upload(&p->d_lit, t.lit);
-    if (e == hipSuccess) e = upload(&p->d_prefix, t.prefix);
-    if (e != hipSuccess) {
-        dpt_pretok_destroy(p);
-        return hip_fail(e, "pre-tokenization table upload");
-    }
-    *out = p;
-    return DPT_OK;
-}
-
-int dpt_pretok_destroy(dpt_pretok *p) {
-    if (!p) return DPT_OK;
-    DeviceGuard g(p->device);
-    for (void *d : {(void *)p->d_bmp, (void *)p->d_astral, (void *)p->d_lit, (void *)p->d_prefix}) (void)hipFree(d);
-    delete p;
-    return DPT_OK;
-}
-
-// The table's part of a pre-tokenization launch, and the launch.
-static int pretok_launch(const dpt_pretok *t, dpt::PretokLaunch p, void *hip_stream) {
-    p.bmp = t->d_bmp; p.astral = t->d_astral; p.n_astral = t->n_astral;
-    p.lit_off = reinterpret_cast<const uint32_t *>(t->d_lit) + 8;
-    p.lit_bytes = t->d_lit + 4 * (8 + t->n_lit + 1);
-    p.n_lit = t->n_lit; p.prefix = t->d_prefix; p.bos_len = t->bos_len; p.runs_ok = t->runs_ok;
-    for (int k = 0; k < 2; k++) p.ascii_known[k] = t->ascii_known[k];
-    for (int k = 0; k < 4; k++) p.lit_first[k] = t->lit_first[k];
-    DeviceGuard g(t->device);
-    const hipError_t e = dpt::launch_pretok(p, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "pre-tokenization launch");
-    return DPT_OK;
-}
-
-int dpt_pretok_sizes(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str, uint64_t *out_len,
-                     int32_t *pre_status, void *hip_stream) {
-    if (!p) return fail(DPT_E_ARG, "null pretok");
-    if (!text || !str_off) return fail(DPT_E_ARG, "null text / str_off");
-    if (!out_len || !pre_status) return fail(DPT_E_ARG, "null out_len / pre_status");
-    if (n_str == 0) return DPT_OK;
-    dpt::PretokLaunch a{};
-    a.write = false; a.text = text; a.str_off = str_off; a.n_str = n_str; a.out_len = out_len; a.pre_status = pre_status;
-    return pretok_launch(p, a, hip_stream);
-}
-
-int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
-                     const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
-                     void *hip_stream) {
-    if (!p) return fail(DPT_E_ARG, "null pretok");
-    if (!text || !str_off) return fail(DPT_E_ARG, "null text / str_off");
-    if (!pre_status || !out_text || !out_off || !cut_mask) return fail(DPT_E_ARG, "null pre_status / out_text / out_off / cut_mask");
-    if (n_str == 0) return DPT_OK;
-    dpt::PretokLaunch a{};
-    a.write = true; a.text = text; a.str_off = str_off; a.n_str = n_str; a.pre_status = const_cast<int32_t *>(pre_status);
-    a.out_text = out_text; a.out_off = out_off; a.cut_mask = cut_mask;
-    return pretok_launch(p, a, hip_stream);
 }
 
 int dpt_token_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist, uint32_t n_bins,

@@ -50,10 +50,7 @@ int dpt_debug_bytelevel_table(const uint32_t *sep_cps, uint32_t n_sep, int which
     const int64_t scalars[DPT_BYTELEVEL_SCALAR_INTS] = {t.n_sep, (int64_t)t.high.size()};
     const void *src[] = {t.ascii, t.high.data(), scalars};
     const uint64_t len[] = {sizeof(t.ascii), t.high.size() * 4, sizeof(scalars)};
-    *size = len[which];
-    if (out && cap < len[which]) return fail(DPT_E_CAP, "table does not fit");
-    if (out && len[which]) memcpy(out, src[which], len[which]);
-    return DPT_OK;
+    return debug_table_out(src[which], len[which], out, cap, size);
 }
 
 int dpt_bytelevel_create(const uint32_t *sep_cps, uint32_t n_sep, int device, dpt_bytelevel **out) {
@@ -61,20 +58,15 @@ int dpt_bytelevel_create(const uint32_t *sep_cps, uint32_t n_sep, int device, dp
     *out = nullptr;
     ByteLevelTables t;
     if (const char *err = build_bytelevel_tables(sep_cps, n_sep, &t)) return fail(DPT_E_ARG, err);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(DPT_E_NODEV, "no HIP device");
-    if (device < 0 || device >= ndev) return fail(DPT_E_ARG, "bad device index");
+    if (const int rc = check_device_and_table(device, nullptr, 0)) return rc;
     DeviceGuard g(device);
     dpt_bytelevel *p = new (std::nothrow) dpt_bytelevel();
     if (!p) return fail(DPT_E_ARG, "out of host memory");
     p->device = device; p->n_high = (uint32_t)t.high.size(); p->ascii[0] = t.ascii[0]; p->ascii[1] = t.ascii[1];
-    if (p->n_high) {
-        hipError_t e = hipMalloc((void **)&p->d_high, t.high.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(p->d_high, t.high.data(), t.high.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            dpt_bytelevel_destroy(p);
-            return hip_fail(e, "separator table upload");
-        }
+    const hipError_t e = upload(&p->d_high, t.high);
+    if (e != hipSuccess) {
+        dpt_bytelevel_destroy(p);
+        return hip_fail(e, "separator table upload");
     }
     *out = p;
     return DPT_OK;
@@ -99,26 +91,15 @@ static int bytelevel_launch(const dpt_bytelevel *t, ByteLevelLaunch p, void *hip
 
 int dpt_bytelevel_sizes(const dpt_bytelevel *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str, uint64_t *out_len,
                         int32_t *pre_status, void *hip_stream) {
-    if (!p) return fail(DPT_E_ARG, "null bytelevel");
-    if (!text || !str_off) return fail(DPT_E_ARG, "null text / str_off");
-    if (!out_len || !pre_status) return fail(DPT_E_ARG, "null out_len / pre_status");
-    if (n_str == 0) return DPT_OK;
-    ByteLevelLaunch a{};
-    a.write = false; a.text = text; a.str_off = str_off; a.n_str = n_str; a.out_len = out_len; a.pre_status = pre_status;
-    return bytelevel_launch(p, a, hip_stream);
+    return split_call(p, "null bytelevel", bytelevel_launch, false, text, str_off, n_str, out_len, pre_status, nullptr, nullptr, nullptr,
+                      hip_stream);
 }
 
 int dpt_bytelevel_write(const dpt_bytelevel *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
                         const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
                         void *hip_stream) {
-    if (!p) return fail(DPT_E_ARG, "null bytelevel");
-    if (!text || !str_off) return fail(DPT_E_ARG, "null text / str_off");
-    if (!pre_status || !out_text || !out_off || !cut_mask) return fail(DPT_E_ARG, "null pre_status / out_text / out_off / cut_mask");
-    if (n_str == 0) return DPT_OK;
-    ByteLevelLaunch a{};
-    a.write = true; a.text = text; a.str_off = str_off; a.n_str = n_str; a.pre_status = const_cast<int32_t *>(pre_status);
-    a.out_text = out_text; a.out_off = out_off; a.cut_mask = cut_mask;
-    return bytelevel_launch(p, a, hip_stream);
+    return split_call(p, "null bytelevel", bytelevel_launch, true, text, str_off, n_str, nullptr, const_cast<int32_t *>(pre_status),
+                      out_text, out_off, cut_mask, hip_stream);
 }
 
 }  // extern "C"

@@ -2,9 +2,10 @@
 //
 // The rule is in include/dpt.h (dpt_bytelevel_create): words start where a three-character window of separator
 // classes says so, and every input byte becomes one atom, its character in the GPT-2 byte alphabet (one byte for 0x21 ..
-// 0x7E, two for every other byte).  dpt_pretok.hip's shape: one wave per string in a grid-stride loop, 64 input bytes
-// per round, lane k holding byte k0 + k (0x100 past the string's end: no load goes beyond its last byte), the round
-// after this one already in registers.
+// 0x7E, two for every other byte).  dpt_pretok.hip's shape, the parts of it that are the same for every splitter
+// taken from dpt_utf8_wave.h: one wave per string in a grid-stride loop, 64 input bytes per round, lane k holding
+// byte k0 + k (0x100 past the string's end: no load goes beyond its last byte), the round after this one already in
+// registers.
 //   - sizes: the length is the string's bytes plus the bytes outside 0x21 .. 0x7E (two popcounts a round); a round
 //     with a byte >= 0x80 also checks that every lead byte opens a well-formed character and counts the continuation
 //     bytes the leads claim against those the string holds.  The separators play no part
@@ -32,9 +33,7 @@
 namespace dpt {
 namespace bl {
 
-using namespace txt;   // NOBYTE, lane_read, byte_load, ahead, utf8_lead
-
-constexpr unsigned WAVES = 4;   // strings per block of 256 threads
+using namespace txt;   // WAVES, NOBYTE, byte_load, ahead, utf8_lead, and the walk's shared parts
 
 __device__ __forceinline__ bool ascii_sep(const ByteLevelLaunch &a, unsigned b) {
     const uint64_t w = b < 64u ? a.ascii_sep[0] : a.ascii_sep[1];
@@ -67,14 +66,9 @@ __global__ void __launch_bounds__(WAVES * 64) bytelevel_kernel(ByteLevelLaunch a
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES;
     const uint64_t so0 = a.str_off[0];
     for (uint64_t s = wave; s < a.n_str; s += n_waves) {
-        uint64_t obase = 0, lim = 0;
-        if (WRITE) {
-            if (a.pre_status[s] != 0) continue;   // refused: nothing is written
-            obase = a.out_off[s] - a.out_off[0];
-            lim = a.out_off[s + 1] - a.out_off[s];
-        }
-        const uint64_t base = a.str_off[s] - so0;
-        const uint64_t n = a.str_off[s + 1] - a.str_off[s];
+        if (WRITE && a.pre_status[s] != 0) continue;   // refused: nothing is written
+        const Str str = open_string<WRITE>(a, s, so0);
+        const uint64_t base = str.base, n = str.n;
         unsigned cur = byte_load(a.text, base, n, 0, lane);
         unsigned nxt = byte_load(a.text, base, n, 64, lane);
         uint64_t total = 0;                 // output bytes of the rounds before this one
@@ -131,50 +125,26 @@ __global__ void __launch_bounds__(WAVES * 64) bytelevel_kernel(ByteLevelLaunch a
                 const unsigned pack = (two ? (0xC0u | ch >> 6) | (0x80u | (ch & 0x3Fu)) << 8 | 1u << 17 : b & 0xFFu) |
                                       (unsigned)((W >> lane) & 1u) << 16;
                 const unsigned ei = wave_incl_scan_add(valid ? (two ? 2u : 1u) : 0u);
-                const unsigned T = (unsigned)__builtin_amdgcn_readlane((int)ei, 63);
-                for (unsigned it = 0; it < T; it += 64) {
-                    const unsigned o = it + lane;
-                    // m = the input bytes of this round whose atoms end at or before o: byte o lies in atom m
-                    unsigned m = 0;
-#pragma unroll
-                    for (unsigned step = 32; step; step >>= 1)
-                        if (lane_read(ei, m + step - 1) <= o) m += step;
-                    const unsigned end = lane_read(ei, m), pk = lane_read(pack, m);   // (garbage where o >= T: not used)
-                    const bool second = ((pk >> 17) & 1u) && o + 1 == end;            // a two-byte atom's second byte
-                    const unsigned out = second ? (pk >> 8) & 0xFFu : pk & 0xFFu;
-                    const unsigned mask = second ? 0u : ((pk >> 16) & 1u) ? 3u : 2u;
-                    const uint64_t g = total + o;   // the byte's index in the string's form
-                    if (o < T && g < lim) {
-                        a.out_text[obase + g] = (uint8_t)out;
-                        a.cut_mask[obase + g] = (uint8_t)mask;
-                    }
-                }
-                total += T;
+                // output byte o lies in the atom of lane m, which ends at `end`
+                total += write_round(a, str.obase, str.lim, lane, ei, total, [&](unsigned o, uint64_t, unsigned m, unsigned end, unsigned *out, unsigned *mask) {
+                    const unsigned pk = lane_read(pack, m);                    // (garbage where o >= T: not used)
+                    const bool second = ((pk >> 17) & 1u) && o + 1 == end;     // a two-byte atom's second byte
+                    *out = second ? (pk >> 8) & 0xFFu : pk & 0xFFu;
+                    *mask = second ? 0u : ((pk >> 16) & 1u) ? 3u : 2u;
+                });
             }
             cur = nxt;
             nxt = after;
             k0 += 64;
         } while (k0 < n);
-        if (!WRITE) {
-            refuse |= claimed != conts;          // a stray continuation byte
-            refuse |= total >= (1ull << 32);
-            if (lane == 0) {
-                a.out_len[s] = refuse ? 0 : total;
-                a.pre_status[s] = refuse ? DPT_PRETOK_NEEDS_HOST : DPT_STATUS_OK;
-            }
-        }
+        if (!WRITE) close_sizes(a, s, lane, total, refuse, claimed, conts);
     }
 }
 
 }  // namespace bl
 
 hipError_t launch_bytelevel(const ByteLevelLaunch &p, hipStream_t stream) {
-    if (p.n_str == 0) return hipSuccess;
-    const uint64_t want = (p.n_str + bl::WAVES - 1) / bl::WAVES;
-    const unsigned blocks = (unsigned)(want < (1ull << 20) ? want : (1ull << 20));   // (more strings: the waves stride)
-    if (p.write) hipLaunchKernelGGL(bl::bytelevel_kernel<true>, dim3(blocks), dim3(bl::WAVES * 64), 0, stream, p);
-    else hipLaunchKernelGGL(bl::bytelevel_kernel<false>, dim3(blocks), dim3(bl::WAVES * 64), 0, stream, p);
-    return hipGetLastError();
+    return txt::launch_split(bl::bytelevel_kernel<false>, bl::bytelevel_kernel<true>, p, stream);
 }
 
 }  // namespace dpt

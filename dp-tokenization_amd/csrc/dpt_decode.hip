@@ -29,11 +29,6 @@ constexpr unsigned WAVES = 4;   // strings per block of 256 threads
 
 __device__ __forceinline__ bool any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 
-// the value of lane `src` (< 64, per lane)
-__device__ __forceinline__ unsigned lane_read(unsigned v, unsigned src) {
-    return (unsigned)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-
 // The id of token k0 + lane (0 past the string's last token: nothing is loaded), and its table entry:
 // {0, 0} past the last token, {0, DETOK_NONE} for an id outside the table -- checked before the load.
 __device__ __forceinline__ int32_t id_load(const int32_t *__restrict__ ids, uint64_t ib, uint64_t ntok, uint64_t k0, unsigned lane) {
@@ -160,8 +155,7 @@ __global__ void __launch_bounds__(WAVES * 64) decode_kernel(DecodeLaunch a) {
 
 hipError_t launch_decode(const DecodeLaunch &p, hipStream_t stream) {
     if (p.n_str == 0) return hipSuccess;
-    const uint64_t want = (p.n_str + dec::WAVES - 1) / dec::WAVES;
-    const unsigned blocks = (unsigned)(want < (1ull << 20) ? want : (1ull << 20));   // (more strings: the waves stride)
+    const unsigned blocks = wave_per_string_blocks(p.n_str, dec::WAVES);
     if (p.kind == DECODE_SIZES) hipLaunchKernelGGL(dec::decode_kernel<DECODE_SIZES>, dim3(blocks), dim3(dec::WAVES * 64), 0, stream, p);
     else if (p.kind == DECODE_BYTES) hipLaunchKernelGGL(dec::decode_kernel<DECODE_BYTES>, dim3(blocks), dim3(dec::WAVES * 64), 0, stream, p);
     else hipLaunchKernelGGL(dec::decode_kernel<DECODE_ROUNDTRIP>, dim3(blocks), dim3(dec::WAVES * 64), 0, stream, p);

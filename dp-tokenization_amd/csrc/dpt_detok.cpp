@@ -159,8 +159,5 @@ extern "C" int dpt_debug_detok_table(const uint8_t *utf8_blob, const uint64_t *t
     const void *src[] = {t.tab.data(), t.blob.data(), scalars};
     const uint64_t len[] = {t.tab.size() * sizeof(uint2), t.blob.size(), sizeof(scalars)};
     if (which < 0 || which >= 3) return fail(DPT_E_ARG, "no such table");
-    *size = len[which];
-    if (out && cap < len[which]) return fail(DPT_E_CAP, "table does not fit");
-    if (out && len[which]) memcpy(out, src[which], len[which]);
-    return DPT_OK;
+    return dpt::debug_table_out(src[which], len[which], out, cap, size);
 }

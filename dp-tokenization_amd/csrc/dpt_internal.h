@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -227,6 +228,12 @@ size_t wsl_scratch_bytes(unsigned max_blocks);
 size_t pend_scratch_bytes(unsigned max_blocks);
 hipError_t launch_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist,
                             uint32_t n_bins, hipStream_t stream);
+// The grid of a one-wave-per-string kernel with `waves` waves to a block: a wave for every string, up to 2^20 blocks
+// (more strings: the waves stride).
+inline unsigned wave_per_string_blocks(uint64_t n_str, unsigned waves) {
+    const uint64_t want = (n_str + waves - 1) / waves;
+    return (unsigned)(want < (1ull << 20) ? want : (1ull << 20));
+}
 // token spans of an encoded batch (dpt_spans.hip; include/dpt.h dpt_token_spans): every pointer a device pointer
 struct SpansLaunch {
     int mode;
@@ -421,5 +428,13 @@ struct VocabTables : VocabScalars {
 // returns 0 or an error message; calls no HIP function
 const char *build_vocab_tables(const uint8_t *blob, const uint64_t *off, const int32_t *ids, uint32_t n, VocabTables *out);
 void set_last_error(const std::string &msg);   // (dpt_api.cpp)
+
+// The end of every dpt_debug_*_table call, the table chosen: its size, and its bytes when `out` is given and holds them.
+inline int debug_table_out(const void *src, uint64_t len, void *out, uint64_t cap, uint64_t *size) {
+    *size = len;
+    if (out && cap < len) return set_last_error("table does not fit"), DPT_E_CAP;
+    if (out && len) memcpy(out, src, len);
+    return DPT_OK;
+}
 
 }  // namespace dpt

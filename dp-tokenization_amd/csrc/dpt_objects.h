@@ -110,6 +110,35 @@ struct DeviceGuard {
     }
 };
 
+// A host table as a fresh device buffer (an empty table: none, *d stays null).
+template <typename D, typename T>
+hipError_t upload(D **d, const std::vector<T> &h) {
+    if (h.empty()) return hipSuccess;
+    const hipError_t e = hipMalloc((void **)d, h.size() * sizeof(T));
+    return e != hipSuccess ? e : hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// Every *_create call (n_tok = 0: no table): a device of this index exists and the token table's offsets ascend.  (dpt_api.cpp)
+int check_device_and_table(int device, const uint64_t *tok_off, uint32_t n_tok);
+
+// What the sizes call (write = false: out_len, pre_status) and the write call (pre_status, out_text, out_off, cut_mask)
+// of a splitter share, dpt_pretok_* and dpt_bytelevel_* alike: the null checks, the launch's common fields, and
+// the launch itself, which adds the table's part -- launch(t, a, hip_stream).
+template <typename Launch, typename Obj>
+int split_call(const Obj *t, const char *null_obj, int (*launch)(const Obj *, Launch, void *), bool write, const uint8_t *text,
+               const uint64_t *str_off, uint64_t n_str, uint64_t *out_len, int32_t *pre_status, uint8_t *out_text,
+               const uint64_t *out_off, uint8_t *cut_mask, void *hip_stream) {
+    if (!t) return fail(DPT_E_ARG, null_obj);
+    if (!text || !str_off) return fail(DPT_E_ARG, "null text / str_off");
+    if (!write && (!out_len || !pre_status)) return fail(DPT_E_ARG, "null out_len / pre_status");
+    if (write && (!pre_status || !out_text || !out_off || !cut_mask)) return fail(DPT_E_ARG, "null pre_status / out_text / out_off / cut_mask");
+    if (n_str == 0) return DPT_OK;
+    Launch a{};
+    a.write = write; a.text = text; a.str_off = str_off; a.n_str = n_str; a.out_len = out_len; a.pre_status = pre_status;
+    a.out_text = out_text; a.out_off = out_off; a.cut_mask = cut_mask;
+    return launch(t, a, hip_stream);
+}
+
 // Device buffer of at least `need` elements: exact on first allocation, +25 % when it grows.  A buffer that
 // already holds `need` is left where it is.
 template <typename T>

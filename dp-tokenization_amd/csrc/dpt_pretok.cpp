@@ -1,10 +1,12 @@
-// dpt_pretok.cpp -- host builder of the pre-tokenization table (include/dpt.h dpt_pretok_create): what the kernels of
-// dpt_pretok.hip need to know of a vocabulary to write llama mode's pre-split text themselves -- which characters
-// are a piece of their own (every other character becomes its byte pieces), whether a run of spaces is safe, the
-// BOS piece, and the literal strings a tokenizer object treats specially.  The rule itself is stated in the header.
+// dpt_pretok.cpp -- the pre-tokenization table (include/dpt.h dpt_pretok_create): its host builder, the object that
+// holds its device copy, and the argument checks of the two device calls whose kernels are in dpt_pretok.hip.  The
+// table is what those kernels need to know of a vocabulary to write llama mode's pre-split text themselves -- which
+// characters are a piece of their own (every other character becomes its byte pieces), whether a run of spaces is
+// safe, the BOS piece, and the literal strings a tokenizer object treats specially.  The rule itself is stated in the
+// header.
 //
-// No HIP call: testable without a device (dpt_debug_pretok_table, tests/test_pretok_tables.py; tests/pretok_ref.py
-// restates the rules).  dpt_api.cpp uploads the bytes and owns the device copy.
+// build_pretok_tables calls no HIP function: testable without a device (dpt_debug_pretok_table,
+// tests/test_pretok_tables.py; tests/pretok_ref.py restates the rules).
 #include <stdint.h>
 #include <string.h>
 
@@ -14,7 +16,7 @@
 #include <unordered_set>
 #include <vector>
 
-#include "dpt_internal.h"
+#include "dpt_objects.h"
 
 namespace dpt {
 
@@ -109,25 +111,93 @@ const char *build_pretok_tables(const uint8_t *blob, const uint64_t *off, uint32
 
 }  // namespace dpt
 
-extern "C" int dpt_debug_pretok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
-                                      uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit,
-                                      int which, void *out, uint64_t cap, uint64_t *size) {
-    auto fail = [](int code, const char *msg) { dpt::set_last_error(msg); return code; };
+using namespace dpt;
+
+extern "C" {
+
+int dpt_debug_pretok_table(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
+                           uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int which,
+                           void *out, uint64_t cap, uint64_t *size) {
     if (!size || !tok_off || (!utf8_blob && n_tok && tok_off[n_tok] != tok_off[0]) || (bos_len && !bos_piece) ||
         (n_lit && (!lit_blob || !lit_off)))
         return fail(DPT_E_ARG, "null argument");
     for (uint32_t t = 0; t < n_tok; t++)
         if (tok_off[t + 1] < tok_off[t]) return fail(DPT_E_ARG, "tok_off not monotone");
     if (which < 0 || which >= 5) return fail(DPT_E_ARG, "no such table");
-    dpt::PretokTables t;
+    PretokTables t;
     int code = DPT_OK;
-    if (const char *err = dpt::build_pretok_tables(utf8_blob, tok_off, n_tok, bos_piece, bos_len, lit_blob, lit_off, n_lit, &t, &code))
+    if (const char *err = build_pretok_tables(utf8_blob, tok_off, n_tok, bos_piece, bos_len, lit_blob, lit_off, n_lit, &t, &code))
         return fail(code, err);
     const int64_t scalars[DPT_PRETOK_SCALAR_INTS] = {t.runs_ok ? 1 : 0, t.n_known, t.n_lit, t.bos_len};
     const void *src[] = {t.bmp.data(), t.astral.data(), t.lit.data(), t.prefix.data(), scalars};
     const uint64_t len[] = {t.bmp.size() * 4, t.astral.size() * 4, t.lit.size(), t.prefix.size(), sizeof(scalars)};
-    *size = len[which];
-    if (out && cap < len[which]) return fail(DPT_E_CAP, "table does not fit");
-    if (out && len[which]) memcpy(out, src[which], len[which]);
+    return debug_table_out(src[which], len[which], out, cap, size);
+}
+
+int dpt_pretok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, uint32_t n_tok, const uint8_t *bos_piece,
+                      uint32_t bos_len, const uint8_t *lit_blob, const uint64_t *lit_off, uint32_t n_lit, int device,
+                      dpt_pretok **out) {
+    if (!out || !tok_off || (!utf8_blob && n_tok && tok_off[n_tok] != tok_off[0]) || (bos_len && !bos_piece) ||
+        (n_lit && (!lit_blob || !lit_off)))
+        return fail(DPT_E_ARG, "null argument");
+    *out = nullptr;
+    if (const int rc = check_device_and_table(device, tok_off, n_tok)) return rc;
+    PretokTables t;
+    int code = DPT_OK;
+    if (const char *err = build_pretok_tables(utf8_blob, tok_off, n_tok, bos_piece, bos_len, lit_blob, lit_off, n_lit, &t, &code))
+        return fail(code, err);
+    DeviceGuard g(device);
+    dpt_pretok *p = new (std::nothrow) dpt_pretok();
+    if (!p) return fail(DPT_E_ARG, "out of host memory");
+    p->device = device; p->n_astral = (uint32_t)t.astral.size(); p->n_lit = t.n_lit; p->bos_len = t.bos_len; p->runs_ok = t.runs_ok;
+    uint32_t first[8];
+    memcpy(first, t.lit.data(), sizeof(first));
+    for (int k = 0; k < 2; k++) p->ascii_known[k] = t.bmp[2 * k] | (uint64_t)t.bmp[2 * k + 1] << 32;
+    for (int k = 0; k < 4; k++) p->lit_first[k] = first[2 * k] | (uint64_t)first[2 * k + 1] << 32;
+    hipError_t e = upload(&p->d_bmp, t.bmp);
+    if (e == hipSuccess) e = upload(&p->d_astral, t.astral);
+    if (e == hipSuccess) e = upload(&p->d_lit, t.lit);
+    if (e == hipSuccess) e = upload(&p->d_prefix, t.prefix);
+    if (e != hipSuccess) {
+        dpt_pretok_destroy(p);
+        return hip_fail(e, "pre-tokenization table upload");
+    }
+    *out = p;
     return DPT_OK;
 }
+
+int dpt_pretok_destroy(dpt_pretok *p) {
+    if (!p) return DPT_OK;
+    DeviceGuard g(p->device);
+    for (void *d : {(void *)p->d_bmp, (void *)p->d_astral, (void *)p->d_lit, (void *)p->d_prefix}) (void)hipFree(d);
+    delete p;
+    return DPT_OK;
+}
+
+// The table's part of a launch, and the launch.
+static int pretok_launch(const dpt_pretok *t, PretokLaunch p, void *hip_stream) {
+    p.bmp = t->d_bmp; p.astral = t->d_astral; p.n_astral = t->n_astral;
+    p.lit_off = reinterpret_cast<const uint32_t *>(t->d_lit) + 8;
+    p.lit_bytes = t->d_lit + 4 * (8 + t->n_lit + 1);
+    p.n_lit = t->n_lit; p.prefix = t->d_prefix; p.bos_len = t->bos_len; p.runs_ok = t->runs_ok;
+    for (int k = 0; k < 2; k++) p.ascii_known[k] = t->ascii_known[k];
+    for (int k = 0; k < 4; k++) p.lit_first[k] = t->lit_first[k];
+    DeviceGuard g(t->device);
+    const hipError_t e = launch_pretok(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "pre-tokenization launch");
+    return DPT_OK;
+}
+
+int dpt_pretok_sizes(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str, uint64_t *out_len,
+                     int32_t *pre_status, void *hip_stream) {
+    return split_call(p, "null pretok", pretok_launch, false, text, str_off, n_str, out_len, pre_status, nullptr, nullptr, nullptr, hip_stream);
+}
+
+int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                     const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
+                     void *hip_stream) {
+    return split_call(p, "null pretok", pretok_launch, true, text, str_off, n_str, nullptr, const_cast<int32_t *>(pre_status), out_text,
+                      out_off, cut_mask, hip_stream);
+}
+
+}  // extern "C"

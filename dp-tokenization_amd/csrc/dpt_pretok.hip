@@ -3,7 +3,8 @@
 // The rule is in include/dpt.h (dpt_pretok_create): a certified string's pre-split form is a per-character function
 // of its text -- ' ' becomes U+2581 opening a word, a character that is a piece of its own stays, any other
 // character becomes <0xNN> for each of its bytes -- behind a fixed prefix (the BOS piece, then U+2581).  One wave per
-// string in a grid-stride loop, 64 input bytes per round, everything in registers (dpt_decode.hip's shape):
+// string in a grid-stride loop, 64 input bytes per round, everything in registers (dpt_decode.hip's shape; the parts
+// of the walk that are the same for every splitter are in dpt_utf8_wave.h, this file holds the rule):
 //   - lane k holds byte k0 + k of the string (0x100 past its end: no load goes beyond the string's last byte).  The
 //     round after this one is already in registers, so a lead-byte lane reads its continuation bytes from its
 //     neighbours' registers and from the next round's: a character may straddle a round, and the bytes that follow a
@@ -24,31 +25,15 @@
 #include <stdint.h>
 
 #include "dpt_internal.h"
+#include "dpt_utf8_wave.h"
 #include "dpt_wave.h"
 
 namespace dpt {
 namespace pre {
 
-constexpr unsigned WAVES = 4;        // strings per block of 256 threads
-constexpr unsigned NOBYTE = 0x100;   // a lane past the string's end
+using namespace txt;   // WAVES, NOBYTE, byte_load, ahead, and the walk's shared parts
 
 enum Kind : unsigned { K_SPACE = 0, K_COPY = 1, K_HEX = 2 };
-
-__device__ __forceinline__ unsigned lane_read(unsigned v, unsigned src) {
-    return (unsigned)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-
-__device__ __forceinline__ unsigned byte_load(const uint8_t *__restrict__ text, uint64_t base, uint64_t n, uint64_t k0, unsigned lane) {
-    const uint64_t p = k0 + lane;
-    return p < n ? (unsigned)text[base + p] : NOBYTE;
-}
-
-// the byte j lanes further on: this round's register, or the next round's
-__device__ __forceinline__ unsigned ahead(unsigned cur, unsigned nxt, unsigned lane, unsigned j) {
-    const unsigned src = lane + j;
-    const unsigned a = lane_read(cur, src & 63u), b = lane_read(nxt, src & 63u);
-    return src < 64u ? a : b;
-}
 
 __device__ __forceinline__ bool ascii_known(const PretokLaunch &a, unsigned b) {
     const uint64_t w = b < 64u ? a.ascii_known[0] : a.ascii_known[1];
@@ -91,6 +76,7 @@ __device__ __forceinline__ Round classify(const PretokLaunch &a, unsigned b, uns
         r.cont = true;
         return r;
     }
+    // (txt::utf8_lead's text: calling it here measured +2 VGPRs in both kernels)
     auto is_cont = [](unsigned x) { return (x & 0x1C0u) == 0x80u; };   // (0x100 is not one)
     unsigned len = 0, cp = 0;
     if (b >= 0xC2u && b < 0xE0u) {
@@ -132,14 +118,9 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES;
     const uint64_t so0 = a.str_off[0];
     for (uint64_t s = wave; s < a.n_str; s += n_waves) {
-        uint64_t obase = 0, lim = 0;
-        if (WRITE) {
-            if (a.pre_status[s] != 0) continue;   // refused: nothing is written
-            obase = a.out_off[s] - a.out_off[0];
-            lim = a.out_off[s + 1] - a.out_off[s];
-        }
-        const uint64_t base = a.str_off[s] - so0;
-        const uint64_t n = a.str_off[s + 1] - a.str_off[s];
+        if (WRITE && a.pre_status[s] != 0) continue;   // refused: nothing is written
+        const Str str = open_string<WRITE>(a, s, so0);
+        const uint64_t base = str.base, n = str.n;
         const unsigned P = a.bos_len + (n ? 3u : 0u);   // the prefix: the BOS piece, and U+2581 before a first character
         unsigned cur = byte_load(a.text, base, n, 0, lane);
         unsigned nxt = byte_load(a.text, base, n, 64, lane);
@@ -180,15 +161,9 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
                 unsigned ei = wave_incl_scan_add(len);
                 const unsigned pfx = k0 == 0 ? P : 0u;   // the prefix goes out with the first round
                 ei += pfx;
-                const unsigned T = (unsigned)__builtin_amdgcn_readlane((int)ei, 63);
-                for (unsigned it = 0; it < T; it += 64) {
-                    const unsigned o = it + lane;
-                    // m = the characters of this round that end at or before o: byte o lies in character m
-                    unsigned m = 0;
-#pragma unroll
-                    for (unsigned step = 32; step; step >>= 1)
-                        if (lane_read(ei, m + step - 1) <= o) m += step;
-                    const unsigned end = lane_read(ei, m), lk = lane_read(r.lk, m);
+                // output byte o lies in the character of lane m, which ends at `end`
+                total += write_round(a, str.obase, str.lim, lane, ei, total, [&](unsigned o, uint64_t g, unsigned m, unsigned end, unsigned *outp, unsigned *mask) {
+                    const unsigned lk = lane_read(r.lk, m);
                     const unsigned kind = lk >> 8, k = o - (end - (lk & 0xFFu));   // (garbage where o < pfx or o >= T: not used)
                     const unsigned j = kind == K_COPY ? k : (k * 43u) >> 8;          // the source byte: k / 6 for k < 24
                     const unsigned src = m + j;
@@ -210,39 +185,22 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
                         const unsigned hx = h < 10u ? '0' + h : 'A' + h - 10u;
                         out = q == 0 ? '<' : q == 1 ? '0' : q == 2 ? 'x' : q == 5 ? '>' : hx;
                     }
-                    const uint64_t g = total + o;   // the byte's index in the string's pre-split form
-                    if (o < T && g < lim) {
-                        a.out_text[obase + g] = (uint8_t)out;
-                        a.cut_mask[obase + g] = opens || g == 0 ? 1 : 0;
-                    }
-                }
-                total += T;
+                    *outp = out;
+                    *mask = opens || g == 0 ? 1 : 0;   // (the string's first byte opens a word too)
+                });
             }
             cur = nxt;
             nxt = after;
             k0 += 64;
         } while (k0 < n);
-        if (!WRITE) {
-            total += P;
-            refuse |= claimed != conts;          // a stray continuation byte
-            refuse |= total >= (1ull << 32);
-            if (lane == 0) {
-                a.out_len[s] = refuse ? 0 : total;
-                a.pre_status[s] = refuse ? DPT_PRETOK_NEEDS_HOST : DPT_STATUS_OK;
-            }
-        }
+        if (!WRITE) close_sizes(a, s, lane, total + P, refuse, claimed, conts);
     }
 }
 
 }  // namespace pre
 
 hipError_t launch_pretok(const PretokLaunch &p, hipStream_t stream) {
-    if (p.n_str == 0) return hipSuccess;
-    const uint64_t want = (p.n_str + pre::WAVES - 1) / pre::WAVES;
-    const unsigned blocks = (unsigned)(want < (1ull << 20) ? want : (1ull << 20));   // (more strings: the waves stride)
-    if (p.write) hipLaunchKernelGGL(pre::pretok_kernel<true>, dim3(blocks), dim3(pre::WAVES * 64), 0, stream, p);
-    else hipLaunchKernelGGL(pre::pretok_kernel<false>, dim3(blocks), dim3(pre::WAVES * 64), 0, stream, p);
-    return hipGetLastError();
+    return txt::launch_split(pre::pretok_kernel<false>, pre::pretok_kernel<true>, p, stream);
 }
 
 }  // namespace dpt

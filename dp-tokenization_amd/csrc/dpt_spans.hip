@@ -29,11 +29,6 @@ constexpr unsigned WAVES = 4;   // strings per block of 256 threads
 
 __device__ __forceinline__ bool any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 
-// the value of lane `src` (< 64, per lane)
-__device__ __forceinline__ unsigned lane_read(unsigned v, unsigned src) {
-    return (unsigned)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
-}
-
 // The byte a text chunk needs of input position tb + lane: the text's (RAW) or the cut mask's; 0 at or
 // past the string's end (nothing is loaded there).  Loaded one chunk ahead of its use.
 template <int MODE>
@@ -180,8 +175,7 @@ __global__ void __launch_bounds__(WAVES * 64) spans_kernel(SpansLaunch a) {
 
 hipError_t launch_spans(const SpansLaunch &p, hipStream_t stream) {
     if (p.n_str == 0) return hipSuccess;
-    const uint64_t want = (p.n_str + spn::WAVES - 1) / spn::WAVES;
-    const unsigned blocks = (unsigned)(want < (1ull << 20) ? want : (1ull << 20));   // (more strings: the waves stride)
+    const unsigned blocks = wave_per_string_blocks(p.n_str, spn::WAVES);
     const int mode = p.mode & DPT_MODE_MASK;
     if (mode == DPT_MODE_RAW) hipLaunchKernelGGL(spn::spans_kernel<DPT_MODE_RAW>, dim3(blocks), dim3(spn::WAVES * 64), 0, stream, p);
     else if (mode == DPT_MODE_PRESPLIT) hipLaunchKernelGGL(spn::spans_kernel<DPT_MODE_PRESPLIT>, dim3(blocks), dim3(spn::WAVES * 64), 0, stream, p);

@@ -426,8 +426,5 @@ extern "C" int dpt_debug_vocab_table(const uint8_t *utf8_blob, const uint64_t *t
     const uint64_t len[] = {dpt::bytes_of(t.slots), dpt::bytes_of(t.slot_ids), dpt::bytes_of(t.slots4), dpt::bytes_of(t.pair),
                             dpt::bytes_of(t.tok_len), sizeof(scalars)};
     if (which < 0 || which >= 6) return fail(DPT_E_ARG, "no such table");
-    *size = len[which];
-    if (out && cap < len[which]) return fail(DPT_E_CAP, "table does not fit");
-    if (out && len[which]) memcpy(out, src[which], len[which]);
-    return DPT_OK;
+    return dpt::debug_table_out(src[which], len[which], out, cap, size);
 }

@@ -11,6 +11,11 @@ __device__ __forceinline__ unsigned uni(unsigned x) { return __builtin_amdgcn_re
 
 __device__ __forceinline__ uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
+// the value of lane `src` (< 64, per lane)
+__device__ __forceinline__ unsigned lane_read(unsigned v, unsigned src) {
+    return (unsigned)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
+}
+
 // inclusive add-scan over 64 lanes (GFX9 DPP: row_shr 1/2/4/8, row_bcast 15/31)
 __device__ __forceinline__ unsigned wave_incl_scan_add(unsigned v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, true);  // row_shr:1

@@ -19,6 +19,32 @@ def pack_literals(literals: Iterable[str]):
     return blob, off, len(enc)
 
 
+def two_pass_split(sizes_device, write_device, text_t, offs_t):
+    """The two passes of a device splitter (``Pretok.presplit``, ``ByteLevelSplit.split``) over torch device tensors
+    (text uint8, offsets int64[n + 1]) -> (text2 uint8, offs2 int64[n + 1] from 0, cut uint8, pre_status int32[n]) on
+    the same device: ``sizes_device``, a cumsum, ``write_device``.  One host read (the total)."""
+    import torch
+    n = offs_t.numel() - 1
+    dev = text_t.device
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if text_t.numel() == 0:   # (a batch of empty strings: the call still wants an address)
+            text_t = torch.zeros(1, dtype=torch.uint8, device=dev)
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        pre_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        offs2 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n > 0:
+            sizes_device(text_t.data_ptr(), offs_t.data_ptr(), n, out_len.data_ptr(), pre_status.data_ptr(), stream)
+            torch.cumsum(out_len[:n], 0, out=offs2[1:])
+        total = int(offs2[-1]) if n > 0 else 0
+        text2 = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        cut = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        if n > 0:
+            write_device(text_t.data_ptr(), offs_t.data_ptr(), n, pre_status.data_ptr(), text2.data_ptr(),
+                         offs2.data_ptr(), cut.data_ptr(), stream)
+    return text2[:total], offs2, cut[:total], pre_status[:n]
+
+
 class Pretok:
     """Device-resident pre-tokenization table of ``t2i`` (include/dpt.h dpt_pretok_create): the words that
     ``pretokenize_with_llama`` + ``merge_tokens`` (reference packages/tokenizer_utils.py:7-31) build from a
@@ -59,23 +85,4 @@ class Pretok:
     def presplit(self, text_t, offs_t):
         """torch device tensors in (text uint8, offsets int64[n + 1]) -> (text2 uint8, offs2 int64[n + 1] from 0,
         cut uint8, pre_status int32[n]) on the same device: sizes, a cumsum, write.  One host read (the total)."""
-        import torch
-        n = offs_t.numel() - 1
-        dev = text_t.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if text_t.numel() == 0:   # (a batch of empty strings: the call still wants an address)
-                text_t = torch.zeros(1, dtype=torch.uint8, device=dev)
-            out_len = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-            pre_status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-            offs2 = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-            if n > 0:
-                self.sizes_device(text_t.data_ptr(), offs_t.data_ptr(), n, out_len.data_ptr(), pre_status.data_ptr(), stream)
-                torch.cumsum(out_len[:n], 0, out=offs2[1:])
-            total = int(offs2[-1]) if n > 0 else 0
-            text2 = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-            cut = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-            if n > 0:
-                self.write_device(text_t.data_ptr(), offs_t.data_ptr(), n, pre_status.data_ptr(), text2.data_ptr(),
-                                  offs2.data_ptr(), cut.data_ptr(), stream)
-        return text2[:total], offs2, cut[:total], pre_status[:n]
+        return two_pass_split(self.sizes_device, self.write_device, text_t, offs_t)

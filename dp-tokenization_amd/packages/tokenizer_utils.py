@@ -388,9 +388,10 @@ def _device_split_paths(split, mode, engine, host_pack):
     (text2, offs2 int64[n + 1], cut, pre_status): ``Pretok.presplit`` or ``ByteLevelSplit.split``;  ``host_pack(texts)``
     -> the host path's (text, offs, cut, cnt) for ``mode``, cnt[i] == 0: string i has no words.  The strings the
     device refuses (pre_status 6) go through ``host_pack`` as one sub-batch and are merged back by index.
-    -> (presplit, encode_csr_lists, pack_merged, stats)."""
+    -> (presplit, encode_many, spans_many, pack_batch, stats): ``presplit`` for ``_probe_check``, the next three what
+    the adapter hangs on its closure in place of the host path's, ``stats`` its ``pretok_stats``."""
     import torch
-    from dptok.pretok import NEEDS_HOST
+    from dptok._lib import PRETOK_NEEDS_HOST as NEEDS_HOST
     from dptok.engine import csr_lists
 
     dev = torch.device("cuda", _device())
@@ -466,12 +467,37 @@ def _device_split_paths(split, mode, engine, host_pack):
         text[:-1][~m], cutm[:-1][~m] = t2, c2
         return text, offs.astype(np.uint64), cutm, cnt
 
-    return presplit, encode_csr_lists, pack_merged, stats
+    def encode_many(texts: Sequence[str]) -> List[List[int]]:
+        texts = list(texts)
+        return _raise_and_collect(texts, encode_csr_lists(texts))
+
+    def spans_many(texts: Sequence[str]) -> List[TokenSpans]:
+        texts = list(texts)
+        text, offs, cut, cnt = pack_merged(texts)
+        return _batch_spans(engine, texts, text, offs, mode, cut, none=(cnt == 0).tolist())
+
+    def pack_batch(texts):
+        text, offs, cut, cnt = pack_merged(list(texts))
+        return text, offs, mode, cut, cnt == 0, None
+
+    return presplit, encode_many, spans_many, pack_batch, stats
+
+
+def _probe_check(presplit, stats, probes, host_words, bit, skip_refused, not_for):
+    """The self-check of a device rule at construction: every probe's words out of ``presplit`` (``bit``: the bits
+    of the cut mask that open a word) against ``host_words(probe)``, the tokenizer's.  DptError on the first
+    difference; a probe the rule refuses is left out when ``skip_refused`` (the rule certifies only some texts) and is
+    a difference otherwise (the rule is exact)."""
+    for probe, words in zip(probes, _presplit_words(presplit, probes, bit)):
+        if (words is not None or not skip_refused) and words != host_words(probe):
+            raise DptError("device_pretokenize: the device rule gives %r for the probe %r, the tokenizer %r: this %s"
+                           % (words, probe, host_words(probe), not_for))
+    stats.set(0, 0)
 
 
 def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
     """llama mode with the pre-tokenization on the device (dptok/pretok.py; the rule: include/dpt.h
-    dpt_pretok_create) -> (encode_csr_lists, pack_merged, stats): the strings the rule certifies never see the
+    dpt_pretok_create) -> (encode_many, spans_many, pack_batch, stats): the strings the rule certifies never see the
     tokenizer object, the others (pre_status 6) go through ``host.pack`` as one sub-batch and are merged back
     by index.  Construction runs the probe list through both and raises DptError on the first certified probe
     whose words differ: the guard for tokenizers the rule was not pinned on."""
@@ -484,17 +510,10 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
         raise DptError("device_pretokenize: the BOS id %d has no piece" % bos)
     literals = _pretok_literals(tokenizer, t2i)
     pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
-    presplit, encode_csr_lists, pack_merged, stats = _device_split_paths(pretok.presplit, "presplit", engine, host.pack)
-
-    # the self-check
-    got = _presplit_words(presplit, PROBES)
-    for probe, words in zip(PROBES, got):
-        if words is not None and words != merge_words(probe):
-            raise DptError("device_pretokenize: the device rule gives %r for the probe %r, the tokenizer %r: this "
-                           "tokenizer is not one the rule holds for (a normalising model, other added-token behaviour)"
-                           % (words, probe, merge_words(probe)))
-    stats.set(0, 0)
-    return encode_csr_lists, pack_merged, stats
+    presplit, *paths, stats = _device_split_paths(pretok.presplit, "presplit", engine, host.pack)
+    _probe_check(presplit, stats, PROBES, merge_words, 0xFF, True,
+                 "tokenizer is not one the rule holds for (a normalising model, other added-token behaviour)")
+    return (*paths, stats)
 
 
 def _presplit_words(presplit, texts, bit: int = 0xFF) -> List[Optional[List[str]]]:
@@ -572,20 +591,7 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama", device_pretok
             # the words come from the device rule wherever it certifies the text; everything downstream is the same
             if not (pieces.ok and not pieces.empty_piece):
                 raise DptError("device_pretokenize needs a vocabulary with dense ids and no empty piece")
-            device_lists, pack_merged, pretok_stats = _device_pretokenizer(llama_tokenizer, t2i, engine, host, pretokenize)
-
-            def encode_many(texts: Sequence[str]) -> List[List[int]]:   # noqa: F811
-                texts = list(texts)
-                return _raise_and_collect(texts, device_lists(texts))
-
-            def spans_many(texts: Sequence[str]) -> List[TokenSpans]:   # noqa: F811
-                texts = list(texts)
-                text, offs, cut, cnt = pack_merged(texts)
-                return _batch_spans(engine, texts, text, offs, "presplit", cut, none=(cnt == 0).tolist())
-
-            def pack_batch(texts):   # noqa: F811
-                text, offs, cut, cnt = pack_merged(list(texts))
-                return text, offs, "presplit", cut, cnt == 0, None
+            encode_many, spans_many, pack_batch, pretok_stats = _device_pretokenizer(llama_tokenizer, t2i, engine, host, pretokenize)
     else:
         def encode_many(texts):
             raise NameError("name 'pretokenize_func' is not defined")
@@ -623,7 +629,7 @@ BLOOM_SPLIT_PATTERN = " ?[^(\\s|[.,!?…。，、।۔،])]+"
 
 def _device_bytelevel(tokenizer, vocab_to_index, engine, host_pack, pretokenize):
     """The BLOOM adapter with its pre-tokenization on the device (dptok/bytelevel.py; the rule: include/dpt.h
-    dpt_bytelevel_create) -> (encode_csr_lists, pack_merged, stats).  The rule is exact for one pre-tokenizer and
+    dpt_bytelevel_create) -> (encode_many, spans_many, pack_batch, stats).  The rule is exact for one pre-tokenizer and
     one alphabet, so construction checks both: the tokenizer's pre-tokenizer must be Sequence[Split(Regex(
     BLOOM_SPLIT_PATTERN), isolated), ByteLevel(add_prefix_space=False, use_regex=False)], every character of the
     byte alphabet must be a vocabulary entry that ``convert_ids_to_tokens`` gives back unchanged, and the probe list
@@ -657,14 +663,9 @@ def _device_bytelevel(tokenizer, vocab_to_index, engine, host_pack, pretokenize)
             raise DptError("device_pretokenize: convert_ids_to_tokens gives %r for the byte alphabet's %r (byte 0x%02X)"
                            % (back[b], alphabet[b], b))
     splitter = ByteLevelSplit(BLOOM_SEPARATORS, _device())
-    presplit, encode_csr_lists, pack_merged, stats = _device_split_paths(splitter.split, "atoms", engine, host_pack)
-    got = _presplit_words(presplit, PROBES, bit=1)
-    for probe, words in zip(PROBES, got):
-        if words != pretokenize(probe):
-            raise DptError("device_pretokenize: the device rule gives %r for the probe %r, the tokenizer %r: this "
-                           "pre-tokenizer is not the one the rule holds for" % (words, probe, pretokenize(probe)))
-    stats.set(0, 0)
-    return encode_csr_lists, pack_merged, stats
+    presplit, *paths, stats = _device_split_paths(splitter.split, "atoms", engine, host_pack)
+    _probe_check(presplit, stats, PROBES, pretokenize, 1, False, "pre-tokenizer is not the one the rule holds for")
+    return (*paths, stats)
 
 
 def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=False):
@@ -730,20 +731,8 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=False):
             batch = [[atoms_of(w) for w in pretokenize(t)] for t in texts]
             return (*pack_word_atoms(batch), np.fromiter((len(words) for words in batch), dtype=np.int64, count=len(batch)))
 
-        device_lists, pack_merged, pretok_stats = _device_bytelevel(bloom_tokenizer, vocab_to_index, engine, host_pack, pretokenize)
-
-        def encode_many(texts: Sequence[str]) -> List[List[int]]:   # noqa: F811
-            texts = list(texts)
-            return _raise_and_collect(texts, device_lists(texts))
-
-        def spans_many(texts: Sequence[str]) -> List[TokenSpans]:   # noqa: F811
-            texts = list(texts)
-            text, offs, cut, cnt = pack_merged(texts)
-            return _batch_spans(engine, texts, text, offs, "atoms", cut, none=(cnt == 0).tolist())
-
-        def pack_batch(texts):   # noqa: F811
-            text, offs, cut, cnt = pack_merged(list(texts))
-            return text, offs, "atoms", cut, cnt == 0, None
+        encode_many, spans_many, pack_batch, pretok_stats = _device_bytelevel(bloom_tokenizer, vocab_to_index, engine, host_pack,
+                                                                             pretokenize)
 
     def dp_tokenize(input_str) -> List[int]:
         return encode_many([input_str])[0]

@@ -9,6 +9,7 @@ import pytest
 from conftest import load_golden
 
 import pretok_ref as pr
+import split_harness
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +19,6 @@ LITERALS = ["<unk>", "<s>", "</s>"]
 # the Arabic block the texts use, some CJK, some emoji
 KNOWN = (set(range(0x20, 0x7E)) - {ord("^")}) | {ord(c) for c in "éèüßñçàâîœ€"} | set(range(0x0621, 0x0636)) | \
     set(range(0x4E00, 0x4F00)) | set(range(0x1F600, 0x1F620))
-G = 67   # canary bytes on each side of an output (odd: the outputs start at odd addresses)
 
 
 def _t2i(known=KNOWN, runs_ok=True, bos="<s>"):
@@ -42,59 +42,9 @@ def tables():
     return {"runs_ok": _pair(), "no_runs": _pair(runs_ok=False), "no_bos": _pair(bos="")}
 
 
-def _run(pretok, strings, pad=3, off0=1_000_003, out0=77):
-    """sizes + write over ``strings`` -> (pre_status, out_len, text2 bytes, cut bytes).  The text sits at an odd
-    address between continuation bytes (a load beyond a string's end would complete a truncated character),
-    str_off and out_off start at off0 / out0, and every output lies between canaries that must survive."""
-    import torch
-    dev = torch.device("cuda", 0)
-    n = len(strings)
-    blob = np.frombuffer(b"\xbf" * pad + b"".join(strings) + b"\x80" * 8, dtype=np.uint8).copy()
-    offs = np.full(n + 1, off0, dtype=np.int64)
-    offs[1:] += np.cumsum([len(s) for s in strings], dtype=np.int64)
-    d_blob, d_offs = torch.from_numpy(blob).to(dev), torch.from_numpy(offs).to(dev)
-
-    def guarded(nbytes):
-        return torch.full((G + nbytes + G,), 0xAA, dtype=torch.uint8, device=dev)
-
-    def inner(buf, nbytes):
-        got = buf.cpu().numpy()
-        assert (got[:G] == 0xAA).all() and (got[G + nbytes:] == 0xAA).all(), "a store outside the output"
-        return got[G:G + nbytes]
-
-    b_len, b_st = guarded(8 * n + 5)[5:], guarded(4 * n + 1)[1:]      # (8- and 4-byte aligned behind the canary)
-    assert (b_len.data_ptr() + G) % 8 == 0 and (b_st.data_ptr() + G) % 4 == 0
-    pretok.sizes_device(d_blob.data_ptr() + pad, d_offs.data_ptr(), n, b_len.data_ptr() + G, b_st.data_ptr() + G)
-    torch.cuda.synchronize()
-    out_len = inner(b_len, 8 * n).copy().view(np.uint64)
-    pre = inner(b_st, 4 * n).copy().view(np.int32)
-    out_off = np.full(n + 1, out0, dtype=np.int64)
-    out_off[1:] += np.cumsum(out_len.astype(np.int64))
-    total = int(out_off[-1]) - out0
-    d_out_off = torch.from_numpy(out_off).to(dev)
-    b_text, b_cut = guarded(total), guarded(total)
-    assert (b_text.data_ptr() + G) % 2 == 1
-    pretok.write_device(d_blob.data_ptr() + pad, d_offs.data_ptr(), n, b_st.data_ptr() + G, b_text.data_ptr() + G,
-                        d_out_off.data_ptr(), b_cut.data_ptr() + G)
-    torch.cuda.synchronize()
-    inner(b_len, 8 * n), inner(b_st, 4 * n)
-    return pre, out_len, inner(b_text, total).tobytes(), inner(b_cut, total).tobytes()
-
-
 def _check(pair, strings, **kw):
     pretok, table = pair
-    want = pr.presplit(table, strings)
-    got = _run(pretok, strings, **kw)
-    bad = np.flatnonzero(got[0] != want[0])
-    assert not len(bad), ("pre_status", [(int(i), strings[i][:80], int(got[0][i]), int(want[0][i])) for i in bad[:5]])
-    bad = np.flatnonzero(got[1] != want[1])
-    assert not len(bad), ("out_len", [(int(i), strings[i][:80], int(got[1][i]), int(want[1][i])) for i in bad[:5]])
-    for what, g, w in (("text", got[2], want[2]), ("cut", got[3], want[3])):
-        if g != w:
-            k = next(i for i in range(len(w)) if g[i] != w[i])
-            s = int(np.searchsorted(np.cumsum(want[1].astype(np.int64)), k, side="right"))
-            raise AssertionError((what, "string", s, strings[s][:80], "byte", k, g[max(k - 8, 0):k + 8], w[max(k - 8, 0):k + 8]))
-    return want
+    return split_harness.check(pretok, lambda strs: pr.presplit(table, strs), strings, **kw)
 
 
 def _ascii(n, length, seed):
