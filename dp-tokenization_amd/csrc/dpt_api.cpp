@@ -127,6 +127,18 @@ void vocab_free(dpt_vocab *v) {
 
 }  // namespace
 
+// (dpt_internal.h)  The environment is read on every call, as kernel_variant reads DPT_KERNEL.
+unsigned dpt::wave_per_string_blocks(uint64_t n_str, unsigned waves) {
+    const uint64_t want = (n_str + waves - 1) / waves;
+    uint64_t blocks = want < (1ull << 20) ? want : (1ull << 20);
+    if (const char *e = getenv("DPT_WAVE_GRID_BLOCKS")) {
+        char *end = nullptr;
+        const long long cap = strtoll(e, &end, 10);
+        if (end != e && *end == '\0' && cap > 0 && (uint64_t)cap < blocks) blocks = (uint64_t)cap;
+    }
+    return (unsigned)blocks;
+}
+
 namespace dpt {
 void set_last_error(const std::string &msg) { g_err = msg; }   // (dpt_rccl.cpp, dpt_vocab.cpp)
 
@@ -386,6 +398,12 @@ int dpt_ctx_debug_counter_bias(dpt_ctx *c, uint64_t bias) {
     if (!c) return fail(DPT_E_ARG, "null ctx");
     if (bias >= (1ull << 62)) return fail(DPT_E_ARG, "counter bias too large");
     c->counter_bias = bias;
+    return DPT_OK;
+}
+
+int dpt_debug_wave_grid(uint64_t n_str, uint32_t waves, uint32_t *blocks) {
+    if (!blocks || waves == 0) return fail(DPT_E_ARG, "bad wave grid arguments");
+    *blocks = dpt::wave_per_string_blocks(n_str, waves);
     return DPT_OK;
 }
 

@@ -229,11 +229,9 @@ size_t pend_scratch_bytes(unsigned max_blocks);
 hipError_t launch_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist,
                             uint32_t n_bins, hipStream_t stream);
 // The grid of a one-wave-per-string kernel with `waves` waves to a block: a wave for every string, up to 2^20 blocks
-// (more strings: the waves stride).
-inline unsigned wave_per_string_blocks(uint64_t n_str, unsigned waves) {
-    const uint64_t want = (n_str + waves - 1) / waves;
-    return (unsigned)(want < (1ull << 20) ? want : (1ull << 20));
-}
+// (more strings: the waves stride).  DPT_WAVE_GRID_BLOCKS=<n> caps it at n blocks, read per call (dpt_api.cpp; tests
+// run many trips of the stride on small batches with it); unset, empty, not a number or <= 0: no cap.
+unsigned wave_per_string_blocks(uint64_t n_str, unsigned waves);
 // token spans of an encoded batch (dpt_spans.hip; include/dpt.h dpt_token_spans): every pointer a device pointer
 struct SpansLaunch {
     int mode;

@@ -86,6 +86,7 @@ CALLS = {
     "dpt_debug_launch_plan": (I32, [I32] * 8 + [U64, I32, U32, U32, ctypes.POINTER(I32)]),
     "dpt_debug_vocab_table": (I32, [P, P, P, U32, I32, P, U64, PU64]),
     "dpt_debug_host_layout": (I32, [I32, U64, U64, U64, I32, U64, PU64]),
+    "dpt_debug_wave_grid": (I32, [U64, U32, ctypes.POINTER(U32)]),
     "dpt_rccl_get_unique_id": (I32, [P]),
     "dpt_rccl_comm_create": (I32, [P, I32, I32, I32, PP]),
     "dpt_rccl_comm_destroy": (I32, [P]),
@@ -123,7 +124,8 @@ EXPORTED = sorted(CALLS)
 DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and name != "dpt_debug_host_layout"}
 # Also within ABI 6 and probed for like OPTIONAL's (a set of its own: OPTIONAL less the layout call is, by
 # tests/test_pack.py, exactly the decode calls); ``collate.collate_device`` raises without it (has_collate).
-OPTIONAL_LATER = {"dpt_collate"}
+# dpt_debug_wave_grid is test-only: ``wave_grid`` below raises without it.
+OPTIONAL_LATER = {"dpt_collate", "dpt_debug_wave_grid"}
 # Likewise the pre-tokenization calls: name -> argument types; ``pretok.Pretok`` raises without them (has_pretok).
 PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name}
 OPTIONAL_PRETOK = set(PRETOK_CALLS)
@@ -178,6 +180,17 @@ def has_bytelevel() -> bool:
     """The loaded library exports the byte-level split calls."""
     L = lib()
     return all(hasattr(L, name) for name in BYTELEVEL_CALLS)
+
+
+def wave_grid(n_str: int, waves: int = 4) -> int:
+    """dpt_debug_wave_grid: the blocks a one-wave-per-string kernel gets for ``n_str`` strings under the current
+    environment (DPT_WAVE_GRID_BLOCKS caps it; test-only, needs no device)."""
+    L = lib()
+    if not hasattr(L, "dpt_debug_wave_grid"):
+        raise DptError(f"{LIB_PATH} was built before dpt_debug_wave_grid: rebuild it")
+    blocks = U32()
+    check(L.dpt_debug_wave_grid(n_str, waves, ctypes.byref(blocks)), "dpt_debug_wave_grid")
+    return blocks.value
 
 
 def check(rc: int, what: str = "") -> None:

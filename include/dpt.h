@@ -581,6 +581,14 @@ int dpt_debug_vocab_table(const uint8_t *utf8_blob, const uint64_t *tok_off, con
 int dpt_debug_host_layout(int call, uint64_t n_bytes, uint64_t n_str, uint64_t n_tok, int flags, uint64_t far_pairs,
                           uint64_t *out);
 
+/* TEST-ONLY, needs no device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  *blocks = the grid a
+ * one-wave-per-string kernel with `waves` waves to a block (the decode, spans, pre-tokenization and byte-level
+ * kernels: 4) gets for n_str strings under the current environment: min(ceil(n_str / waves), 2^20) blocks, so
+ * that a wave takes a second string only in calls of more than waves * 2^20 strings -- and at most
+ * DPT_WAVE_GRID_BLOCKS blocks when that variable holds a decimal number > 0 (read on every call; for tests that
+ * run many trips of the waves' stride on small batches, tests/test_gpu_wave_stride.py). */
+int dpt_debug_wave_grid(uint64_t n_str, uint32_t waves, uint32_t *blocks);
+
 /*
  * Multi-GPU without torch (ABI 6; SURVEY.md §8(b) dpt_hist_allreduce, §8(e) "direct RCCL with a
  * file-store unique id").  One process per GPU: rank 0 calls dpt_rccl_get_unique_id and hands the

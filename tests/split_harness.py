@@ -10,12 +10,19 @@ def _run(split, strings, pad=3, off0=1_000_003, out0=77):
     """sizes + write over ``strings`` -> (pre_status, out_len, text2 bytes, cut bytes).  The text sits at an odd
     address between continuation bytes (a load beyond a string's end would complete a truncated character),
     str_off and out_off start at off0 / out0, and every output lies between canaries that must survive."""
+    return run_packed(split, b"".join(strings), np.array([len(s) for s in strings], dtype=np.int64), pad, off0, out0)
+
+
+def run_packed(split, raw, lens, pad=3, off0=1_000_003, out0=77):
+    """``_run`` over the strings of ``lens`` bytes each that ``raw`` holds back to back (batches too large for a
+    list of strings)."""
     import torch
     dev = torch.device("cuda", 0)
-    n = len(strings)
-    blob = np.frombuffer(b"\xbf" * pad + b"".join(strings) + b"\x80" * 8, dtype=np.uint8).copy()
+    n = len(lens)
+    blob = np.frombuffer(b"\xbf" * pad + raw + b"\x80" * 8, dtype=np.uint8).copy()
     offs = np.full(n + 1, off0, dtype=np.int64)
-    offs[1:] += np.cumsum([len(s) for s in strings], dtype=np.int64)
+    offs[1:] += np.cumsum(lens, dtype=np.int64)
+    assert int(offs[-1]) - off0 == len(raw)
     d_blob, d_offs = torch.from_numpy(blob).to(dev), torch.from_numpy(offs).to(dev)
 
     def guarded(nbytes):

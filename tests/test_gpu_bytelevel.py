@@ -45,7 +45,8 @@ def test_fixture_batch(splitter):
 
 # ------------------------------------------------------------------ 2. round edges
 
-def test_round_edges(splitter):
+def round_edge_strings():
+    """Strings on the kernel's 64-byte round edges, all well-formed (also run by test_gpu_wave_stride.py)."""
     base = (b"abcdefghij klmno,pqrst. uvwxyz [01234] 56789! " * 5)
     strings = [base[:L] for L in (0, 1, 63, 64, 65, 127, 128, 129, 200)]
     strings += [b"a" * L for L in (1, 63, 64, 65, 127, 128, 129)]
@@ -70,6 +71,11 @@ def test_round_edges(splitter):
     strings += ["".join(chr(c) for c in br.BLOOM_SEPARATORS).encode() * 3, b". , ! ? ( ) |" * 12, sep3 * 50, b"\n" * 130]   # only separators
     strings += ["中文字龍".encode() * 20, emoji * 40, "éüßñ".encode() * 33, "ءبي".encode() * 30, ("。" + "中" * 21).encode() * 3]   # only bytes >= 0x80
     strings += ["a[b]c (d|e) f.g,h!i?j".encode(), bytes(range(0x80)) * 2, bytes(range(0x7F, -1, -1))]
+    return strings
+
+
+def test_round_edges(splitter):
+    strings, emoji = round_edge_strings(), "😀".encode()
     st, ln, text2, cut = _check(splitter, strings)
     assert not st.any()
     d = dict(zip(strings, zip(ln.tolist(), range(len(strings)))))
@@ -89,7 +95,12 @@ MALFORMED = [b"a\xc3", b"\xe2\x82", b"ab\xf0\x9f\x98", b"\xf0", b"\xc0\xaf", b"\
              b"\xe2\x82\x28", b"\xf0\x28\x8c\xbc", b"\xf0\x9f\x28\xbc", b"\xf0\x9f\x98\x28"]
 
 
-def test_malformed(splitter):
+WELL_FORMED = ["é€😀".encode(), b"\xed\x9f\xbf", b"\xee\x80\x80", b"\xf4\x8f\xbf\xbf", b"\xf0\x90\x80\x80", b"\xe0\xa0\x80", b"\xc2\x80"]
+
+
+def malformed_strings():
+    """MALFORMED in its paddings, truncated characters before continuation bytes, and WELL_FORMED (also run by
+    test_gpu_wave_stride.py)."""
     strings = []
     for m in MALFORMED:
         strings += [m, b"ok " + m, m + b" ok", b"a" * 62 + m, b"a" * 63 + m + b"z" * 70, b"a" * 130 + m]
@@ -97,8 +108,11 @@ def test_malformed(splitter):
     for a, b in ((b"a\xe2\x82", b"\xac b"), (b"ab\xf0\x9f", b"\x98\x80"), (b"x" * 63 + b"\xc3", b"\xa9"), (b"q\xe2", b"\x82\xac"),
                  (b"x" * 62 + b"\xe3\x80", b"\x82")):
         strings += [a, b, b"fine"]
-    well = ["é€😀".encode(), b"\xed\x9f\xbf", b"\xee\x80\x80", b"\xf4\x8f\xbf\xbf", b"\xf0\x90\x80\x80", b"\xe0\xa0\x80", b"\xc2\x80"]
-    strings += well
+    return strings + WELL_FORMED
+
+
+def test_malformed(splitter):
+    strings, well = malformed_strings(), WELL_FORMED
     want = _check(splitter, strings)
     st = dict(zip(strings, want[0].tolist()))
     assert all(st[m] == br.NEEDS_HOST for m in MALFORMED) and all(st[w] == 0 for w in well)
@@ -106,6 +120,9 @@ def test_malformed(splitter):
 
 
 # ------------------------------------------------------------------ 4. call shapes
+
+OTHER_SEPARATORS = [0x20, ord("o"), 0x4E2D, 0x1F600, 0xF6]   # a second separator set: one in every length class
+
 
 def test_call_shapes(splitter):
     import torch
@@ -147,11 +164,11 @@ def test_call_shapes(splitter):
     blob = np.frombuffer(b"".join(strings[:500]), dtype=np.uint8).copy()
     offs = np.concatenate([[0], np.cumsum([len(x) for x in strings[:500]])]).astype(np.int64)
     from dptok import ByteLevelSplit
-    other = ByteLevelSplit([0x20, ord("o"), 0x4E2D, 0x1F600, 0xF6])
+    other = ByteLevelSplit(OTHER_SEPARATORS)
     with torch.cuda.stream(s):
         text2, offs2, cut, pre = other.split(torch.from_numpy(blob).cuda(), torch.from_numpy(offs).cuda())
     s.synchronize()
-    want = br.split(br.build_table([0x20, ord("o"), 0x4E2D, 0x1F600, 0xF6]), strings[:500])
+    want = br.split(br.build_table(OTHER_SEPARATORS), strings[:500])
     assert pre.cpu().numpy().tolist() == want[0].tolist() and np.diff(offs2.cpu().numpy()).tolist() == want[1].tolist()
     assert text2.cpu().numpy().tobytes() == want[2] and cut.cpu().numpy().tobytes() == want[3]
     empty = splitter.split(torch.zeros(0, dtype=torch.uint8, device="cuda:0"), torch.zeros(1, dtype=torch.int64, device="cuda:0"))

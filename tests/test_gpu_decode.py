@@ -96,8 +96,13 @@ LONG_A, LONG_B = "Q" * 300, "Z" * 5000
 
 @pytest.fixture(scope="module")
 def edge_batch():
+    return build_edge_batch()
+
+
+def build_edge_batch():
     """Strings on the walk's edges as one CSR batch (ids, id_off, the texts to compare with), the Detok and
-    decode_ref's expectations, computed once."""
+    decode_ref's expectations, computed once; "lists" / "texts" / "by_id": the batch string by string and
+    decode_ref's table (test_gpu_wave_stride.py reorders them)."""
     from dptok import Detok, Encoder, Vocab, pack_strings, synth
     t2i = dict(synth.llama_shaped_vocab())
     assert t2i["<s>"] == SKIP and LONG_A not in t2i and max(t2i.values()) == 31999
@@ -147,7 +152,8 @@ def edge_batch():
     n_made = len(made)
     assert not want_rt[0][:401 + n_made].any()
     assert want_rt[0][401 + n_made:].tolist() == [5] * 10 and want_rt[1][401 + n_made:].tolist() == [63, 64, 64, 65, 63, 4000, 302, 0, 0, 62]
-    return {"detok": Detok(dt2i, "sp", [SKIP]), "ids": flat, "id_off": io, "text": tx, "offs": to, "dec": want_dec, "rt": want_rt}
+    return {"detok": Detok(dt2i, "sp", [SKIP]), "ids": flat, "id_off": io, "text": tx, "offs": to, "dec": want_dec, "rt": want_rt,
+            "lists": lists, "texts": texts, "by_id": by_id}
 
 
 def test_round_edges_whole_batch(edge_batch):
@@ -294,8 +300,8 @@ def test_device_path_contract(vocab, form, engines, uploads, side_stream):
 def test_foreign_ids_in_range():
     """One id of a string replaced by a token of another byte length, or by an id inside [id_min, id_max]
     that no token has: decode gives that string status 4 and the round trip 4 or 5 as decode_ref says, every
-    other string its exact result, and nothing is stored outside the output ranges.  (Ids outside the table
-    are not run: the bounds check in dpt_decode.hip is reviewed by reading.)"""
+    other string its exact result, and nothing is stored outside the output ranges.  (Ids outside the table:
+    test_gpu_wave_stride.py::test_decode_capped.)"""
     torch = pytest.importorskip("torch")
     from dptok import Detok, Encoder, Vocab
     t2i = {t: i + (1 if i >= HOLE else 0) for t, i in mc.vocabularies()["base"].items()}

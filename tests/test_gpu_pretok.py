@@ -70,13 +70,14 @@ def test_fixture_batch(which, tables):
 
 # ------------------------------------------------------------------ 2. round edges
 
-def test_edge_length_strings(tables):
+EDGE_CHARS = ["é", "ö", "中", "龍", "😀", "𝄞", "ب", "ي", "€", "…"]          # known and unknown, 2 to 4 bytes
+
+
+def edge_length_strings():
+    """Strings on the kernel's 64-byte round edges, none refused with runs_ok (also run by test_gpu_wave_stride.py)."""
     base = _ascii(1, 200, seed=21)[0].replace(b"<", b"(")
     strings = [base[:L] for L in (0, 1, 63, 64, 65, 127, 128, 129, 200)]
-    chars = ["é", "ö", "中", "龍", "😀", "𝄞", "ب", "ي", "€", "…"]            # known and unknown, 2 to 4 bytes
-    table = tables["runs_ok"][1]
-    assert {(len(c.encode()), ord(c) in table.known) for c in chars} == {(L, k) for L in (2, 3, 4) for k in (True, False)}
-    for c in chars:
+    for c in EDGE_CHARS:
         for at in (61, 62, 63, 125, 126, 127):
             strings.append(b"a" * at + c.encode() + b"bc")
             strings.append(b"a" * at + c.encode())                           # ... and ending the string
@@ -84,6 +85,13 @@ def test_edge_length_strings(tables):
     strings.append(("😀" * 37 + " " + "𝄞é" * 20).encode())
     strings.append(b" ".join([b"x"] * 100))                                  # 3-byte expansions, a word per character
     strings.append(b"\n" * 130)
+    return strings
+
+
+def test_edge_length_strings(tables):
+    strings = edge_length_strings()
+    table = tables["runs_ok"][1]
+    assert {(len(c.encode()), ord(c) in table.known) for c in EDGE_CHARS} == {(L, k) for L in (2, 3, 4) for k in (True, False)}
     st, ln, _, _ = _check(tables["runs_ok"], strings)
     assert not st.any() and int(ln.max()) == 6 + 50 * 24
     _check(tables["no_bos"], strings, pad=1, off0=0, out0=0)
@@ -97,15 +105,21 @@ MALFORMED = [b"a\xc3", b"\xe2\x82", b"ab\xf0\x9f\x98", b"\xf0", b"\xc0\xaf", b"\
              b"\xe2\x82\x28", b"\xf0\x28\x8c\xbc", b"\xf0\x9f\x28\xbc", b"\xf0\x9f\x98\x28"]
 
 
-def test_malformed_and_refused(tables):
+WELL_FORMED = ["é€😀".encode(), b"\xed\x9f\xbf", b"\xee\x80\x80", b"\xf4\x8f\xbf\xbf", b"\xf0\x90\x80\x80", b"\xe0\xa0\x80", b"\xc2\x80"]
+# two spaces: refused only without runs_ok -- inside a round, across its boundary, at the end
+SPACES = [b"a  b", b"a b", b"a" * 63 + b"  b", b"a" * 62 + b"  b", b"ab  ", b"a" * 127 + b"  ", b"a \n b", b"a" * 63 + b" b c"]
+
+
+def malformed_and_refused_strings():
+    """MALFORMED in its paddings, truncated characters before continuation bytes, WELL_FORMED, refused strings and
+    the special-token literals on and off the round edges (also run by test_gpu_wave_stride.py)."""
     strings = []
     for m in MALFORMED:
         strings += [m, b"ok " + m, m + b" ok", b"a" * 62 + m, b"a" * 63 + m + b"z" * 70]
     # a truncated character directly followed by the next string's continuation bytes: never completed
     for a, b in ((b"a\xe2\x82", b"\xac b"), (b"ab\xf0\x9f", b"\x98\x80"), (b"x" * 63 + b"\xc3", b"\xa9"), (b"q\xe2", b"\x82\xac")):
         strings += [a, b, b"fine"]
-    well = ["é€😀".encode(), b"\xed\x9f\xbf", b"\xee\x80\x80", b"\xf4\x8f\xbf\xbf", b"\xf0\x90\x80\x80", b"\xe0\xa0\x80", b"\xc2\x80"]
-    strings += well
+    strings += WELL_FORMED
     # refused though well-formed
     strings += [b" x", b" ", "a▁b".encode(), "▁".encode(), b"x" * 63 + "▁".encode(), b"x" * 62 + "▁".encode()]
     # the literals: at the start, at the end, across a round boundary; a proper prefix at the string's end
@@ -116,14 +130,17 @@ def test_malformed_and_refused(tables):
         for k in range(1, len(x)):
             strings += [b"abc" + x[:k], b"a" * (64 - k) + x[:k], x[:k] + b"<"]
     strings += [b"abc<s", b">x", b"<<s", b"<<s>", b"a < b > c", b"<s >", b"< s>", b"<S>"]
+    return strings
+
+
+def test_malformed_and_refused(tables):
+    strings, well = malformed_and_refused_strings(), WELL_FORMED
     want = _check(tables["runs_ok"], strings)
     st = dict(zip(strings, want[0].tolist()))
     assert all(st[m] == pr.NEEDS_HOST for m in MALFORMED) and all(st[w] == 0 for w in well)
     assert st[b"abc<s"] == 0 and st[b">x"] == 0 and st[b"<<s>"] == 6 and st[b"a" * 126 + b"<unk>"] == 6 and st[b"\xac b"] == 6
-    # two spaces: refused only without runs_ok -- inside a round, across its boundary, at the end
-    spaces = [b"a  b", b"a b", b"a" * 63 + b"  b", b"a" * 62 + b"  b", b"ab  ", b"a" * 127 + b"  ", b"a \n b", b"a" * 63 + b" b c"]
-    assert not _check(tables["runs_ok"], spaces)[0].any()
-    assert _check(tables["no_runs"], spaces)[0].tolist() == [6, 0, 6, 6, 6, 6, 0, 0]
+    assert not _check(tables["runs_ok"], SPACES)[0].any()
+    assert _check(tables["no_runs"], SPACES)[0].tolist() == [6, 0, 6, 6, 6, 6, 0, 0]
 
 
 # ------------------------------------------------------------------ 4. call shapes

@@ -52,7 +52,12 @@ def test_matrix_corpus_spans(vocab, form, encoders):
 
 @pytest.fixture(scope="module")
 def edge_batch():
-    """The strings, the llama-shaped engine, its whole-batch result and the walk's."""
+    return build_edge_batch()
+
+
+def build_edge_batch():
+    """The strings, the llama-shaped engine, its whole-batch result and the walk's (test_gpu_wave_stride.py
+    reorders them)."""
     from dptok import Encoder, Vocab, pack_strings, synth
     t2i = synth.llama_shaped_vocab()
     t, _ = synth.random_ascii_corpus(1, 400, seed=11)
@@ -67,7 +72,7 @@ def edge_batch():
     ref = spans_ref.expected(t2i, "raw", text, offs, None, ids, id_off, st)
     for a in ref:
         a.setflags(write=False)
-    return {"strs": strs, "text": text, "offs": offs, "enc": enc, "got": got, "ref": ref}
+    return {"strs": strs, "text": text, "offs": offs, "enc": enc, "got": got, "ref": ref, "t2i": t2i}
 
 
 def test_chunk_edges_whole_batch(edge_batch):
@@ -190,8 +195,8 @@ def test_device_path_contract(vocab, form, encoders, uploads, side_stream):
 def test_foreign_ids_in_range():
     """One id of a string replaced by a token of another byte length, or by an id inside [id_min, id_max]
     that no token has: that string gets status 4, every other string its exact result, and nothing is
-    stored outside the id ranges.  (Ids outside the table are not run: the bounds check in
-    dpt_spans.hip is reviewed by reading.)"""
+    stored outside the id ranges.  (Ids outside the table:
+    test_gpu_wave_stride.py::test_spans_capped.)"""
     torch = pytest.importorskip("torch")
     from dptok import Encoder, Vocab
     t2i = {t: i + (1 if i >= HOLE else 0) for t, i in mc.vocabularies()["base"].items()}
