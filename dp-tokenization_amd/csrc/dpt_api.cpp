@@ -91,6 +91,12 @@ int dpt::ensure_workspace(dpt_ctx *c, const dpt_vocab *v, uint64_t n_bytes, uint
         e = hipMalloc((void **)&c->ctr, dpt::CTR_ALLOC_BYTES);
         if (e == hipSuccess) e = hipMemset(c->ctr, 0, dpt::CTR_ALLOC_BYTES);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc(ctr)");
+        if (!c->lean_host) {   // the hint's host mirror (dpt_objects.h)
+            e = hipHostMalloc((void **)&c->lean_host, 64, hipHostMallocMapped);
+            if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&c->lean_host_dev, c->lean_host, 0);
+            if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(lean hint)");
+            c->lean_host[0] = 0;
+        }
         fresh = true;
     }
     // the zero state every later call relies on must be in place before a call on any stream (a
@@ -184,6 +190,7 @@ int dpt::encode_impl(dpt_ctx *c, const dpt_vocab *v, const EncodeRequest &r) {
     p.staging = c->staging32; p.staging16 = v->ids16 ? c->staging16 : nullptr; p.counts = c->counts;
     p.retry_list = c->retry_list; p.ctr = c->ctr; p.wsl_scratch = c->wsl_scratch; p.pend = c->pend;
     p.max_blocks = c->max_blocks; p.arena = c->arena; p.arena_cap = c->arena_cap; p.counter_bias = c->counter_bias;
+    p.lean_mirror = c->lean_host_dev;
     flag_regions(c->flags, c->cap_batches, c->flag_parity, &p);
     // padded: the ids go straight to their final place (int32), the counts to the caller's array
     if (padded) { p.staging = r.ids; p.staging16 = nullptr; p.counts = r.padded_counts; }
@@ -220,9 +227,16 @@ int dpt::encode_impl(dpt_ctx *c, const dpt_vocab *v, const EncodeRequest &r) {
         evp = ev;
         c->launches++;
     }
+    // (only the calls the lean route is for count towards the retry: on a context of mixed calls the probe would else
+    // fall on a call that launches no lean kernel)
+    if (c->debug_no_lean)
+        p.lean_skip = true;
+    else if (dpt::lean_eligible(p))
+        p.lean_skip = dpt::lean_plan_skip(c->lean_host ? *static_cast<volatile uint32_t *>(c->lean_host) : 0u, c->lean_skipped);
     hipError_t e = dpt::launch_encode(p, st, evp);
     if (e != hipSuccess) {
         (void)hipMemsetAsync(c->ctr, 0, dpt::CTR_ALLOC_BYTES, st);   // the scan kernel did not reset them
+        if (c->lean_host) c->lean_host[0] = 0;
         (void)hipMemsetAsync(c->flags, 0, flag_words(c->cap_batches) * sizeof(unsigned long long), st);   // nor zero the batch lines
         c->flag_parity = 0;
         return hip_fail(e, "encode launch");
@@ -352,6 +366,7 @@ int dpt_ctx_destroy(dpt_ctx *c) {
     for (void *p : ps)
         if (p) (void)hipFree(p);
     if (c->p_in) (void)hipHostFree(c->p_in);
+    if (c->lean_host) (void)hipHostFree(c->lean_host);
     if (c->p_out) (void)hipHostFree(c->p_out);
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     delete c;
@@ -399,6 +414,24 @@ int dpt_ctx_debug_counter_bias(dpt_ctx *c, uint64_t bias) {
     if (bias >= (1ull << 62)) return fail(DPT_E_ARG, "counter bias too large");
     c->counter_bias = bias;
     return DPT_OK;
+}
+
+int dpt_ctx_debug_no_lean(dpt_ctx *c, int on) {
+    if (!c) return fail(DPT_E_ARG, "null ctx");
+    c->debug_no_lean = on != 0;
+    return DPT_OK;
+}
+
+int dpt_ctx_debug_lean_words(dpt_ctx *c, uint32_t out[4]) {
+    if (!c || !out) return fail(DPT_E_ARG, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = 0;
+    if (!c->ctr) return DPT_OK;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess)
+        e = hipMemcpy(out, reinterpret_cast<const uint8_t *>(c->ctr) + dpt::PART_CTR_OFFSET + dpt::LEAN_LINE * dpt::PART_STRIDE * 4,
+                      3 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    out[3] = c->lean_skipped;
+    return e == hipSuccess ? DPT_OK : hip_fail(e, "lean words");
 }
 
 int dpt_debug_wave_grid(uint64_t n_str, uint32_t waves, uint32_t *blocks) {

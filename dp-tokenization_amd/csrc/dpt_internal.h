@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dpt.h"
+#include "dpt_lean_hint.h"
 
 namespace dpt {
 
@@ -94,6 +95,9 @@ struct EncodeLaunch {
     uint8_t *arena;          // the unbounded pass's scratch: 20 bytes per input byte of the strings it takes
     uint64_t arena_cap;      // input bytes the arena holds
     uint64_t counter_bias;   // test-only (dpt_ctx_debug_counter_bias): the arena and far-pair counters start at it
+    bool lean_skip = false;        // no lean launch: the context's hint is off and this is not a retry call, or the
+                                   //   context's test switch (dpt_ctx_debug_no_lean)
+    uint32_t *lean_mirror = nullptr;   // nullable: the pinned host word the lean kernels mirror LEAN_OFF to
     // vocabulary
     const int2 *slots;
     const int32_t *slot_ids;
@@ -136,6 +140,19 @@ constexpr unsigned FIN_MAX_BINS = 1024;   // histogram bins the finish pass fold
 constexpr unsigned BS_LINE = 16;
 constexpr size_t PART_CTR_OFFSET = 256;
 constexpr size_t CTR_ALLOC_BYTES = PART_CTR_OFFSET + (NPART_MAX + 1) * PART_STRIDE * 4;
+// The lean route's words (raw calls of 16-lane vocabularies, dpt_kernels.hip): the line after the used-up mask's
+// (the first pass uses 16 partition lines and the mask's of the NPART_MAX + 1 allocated).  Zero at allocation and
+// never reset between calls: they are the context's memory of its last calls' text.
+constexpr unsigned LEAN_LINE = 17;
+enum LeanWord {
+    LEAN_OFF = 0,        // the hint: nonzero = the lean waves claim nothing.  Set by a lean wave that deferred too many of its
+                         //   strings; cleared by the probe (the lean launch's first wave, when it finds the hint off: the
+                         //   batch's first strings through prep and phase A, unclaimed, nothing written) when none of them
+                         //   would have been deferred
+    LEAN_DEFERRED = 1,   // the strings the last lean launch deferred (written by the general launch; the tests read it)
+    LEAN_PROBES = 2,     // probes made so far (the tests read it)
+};
+static_assert(LEAN_LINE > 16 && LEAN_LINE <= NPART_MAX, "the lean words' line: past the mask's, inside the block");
 
 // child filter bit of next byte b (slots4[].w, host and device): XOR with b >> 5 permutes the
 // low five bits inside each 32-byte block, so the 26 lowercase letters get distinct bits
@@ -218,12 +235,16 @@ struct LaunchKnobs {
     bool no_solo;         // DPT_NO_SOLO: no one-string calls at all (dpt_api.cpp)
     bool no_mid;          // DPT_NO_MID: the 512-byte pass off
     bool no_small_wpc;    // DPT_NO_SMALL_WPC: the small-call wave rule off (launch_tok)
+    bool no_lean;         // DPT_NO_LEAN: plain RAW calls without the lean launch -- the general kernel alone, as before it
+                          //   (per call: EncodeLaunch::lean_skip)
     int fb_big_per_cu;    // DPT_FB_BIG_PER_CU: 2048-byte blocks per CU of non-raw calls (3; <= 0: the small grid)
     int waves_per_cu;     // DPT_WAVES_PER_CU: the first pass's resident waves per CU (0: by occupancy)
 };
 const LaunchKnobs &launch_knobs();
 
 hipError_t launch_encode(const EncodeLaunch &p, hipStream_t stream, hipEvent_t ev[2]);
+// launch_encode's plan for p takes the lean route unless the hint or DPT_NO_LEAN says otherwise (pure: no HIP call)
+bool lean_eligible(const EncodeLaunch &p);
 size_t wsl_scratch_bytes(unsigned max_blocks);
 size_t pend_scratch_bytes(unsigned max_blocks);
 hipError_t launch_histogram(const uint64_t *id_off, const int32_t *status, uint64_t n_str, int64_t *hist,

@@ -824,6 +824,56 @@ __device__ bool prep_window(GroupLDS<CH, G> &L, uint8_t *gw, const WinRegs<CH> &
     return ballot(bad) == 0;
 }
 
+#ifndef DPT_LEAN_NOSCAN   // A/B knob: the lean prep of a window without '\n' takes its code-point prefixes from the index
+#define DPT_LEAN_NOSCAN 0
+#endif
+constexpr bool LEAN_NOSCAN = DPT_LEAN_NOSCAN != 0;
+#ifndef DPT_LEAN_SETPRIO  // A/B knob: the lean kernel raises its wave priority around lane-mode B and its C1 walk
+#define DPT_LEAN_SETPRIO 0
+#endif
+// The lean first pass's prep (raw mode, 256-byte 16-lane rows; tokenize_body LEAN = 1): the window [pos, pos + wlen) is
+// pure ASCII (the caller tested it), so atom j is byte j -- no aoff[] (the lean readers use the index), no word list,
+// no walk descriptors -- and rec[j] = the end mask all dead | the code-point prefix | the word-start bit as prep_window
+// writes them: a code point per byte, 6 for '\n' ("<0x0A>"), 2 for the string's first byte ('▁' + the byte).
+// One 16-byte store of the lane's four records; the records past the window are never read.
+__device__ __forceinline__ void prep_window_lean(GroupLDS<256, 16> &L, const WinRegs<256> &W, uint64_t pos, unsigned wlen,
+                                                 unsigned lane) {
+    const uint32_t w0 = W.t[0];
+    const unsigned k0 = 4u * lane;
+    const uint32_t nl = eq_bytes(w0, 0x0A0A0A0Au), sp = eq_bytes(w0, 0x20202020u);
+    // the lane's code points before each of its bytes (bytes past the window count too: their records are dead)
+    unsigned cl[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) cl[u] = 1u + 5u * ((nl >> (8 * u + 7)) & 1u);
+    if (pos == 0 && lane == 0) cl[0] = 2u;
+    const unsigned sum = cl[0] + cl[1] + cl[2] + cl[3];
+    unsigned cp;
+    if (LEAN_NOSCAN && !ballot(nl != 0)) cp = k0 + ((pos == 0 && lane > 0) ? 1u : 0u);   // a code point per byte: no scan
+    else cp = wave_incl_scan_add(sum) - sum;
+    uint4 r;
+    r.x = 0xFFFF0000u | cp | ((lane == 0 || (sp & 0x80u)) ? (unsigned)CP_WS : 0u);
+    cp += cl[0];
+    r.y = 0xFFFF0000u | cp | ((sp & 0x8000u) ? (unsigned)CP_WS : 0u);
+    cp += cl[1];
+    r.z = 0xFFFF0000u | cp | ((sp & 0x800000u) ? (unsigned)CP_WS : 0u);
+    cp += cl[2];
+    r.w = 0xFFFF0000u | cp | ((sp & 0x80000000u) ? (unsigned)CP_WS : 0u);
+    cp += cl[3];
+    // the window end's record (atom wlen): in this lane's four, or the next lane's first (lane 64: none, wlen = 256)
+    const unsigned e = wlen - k0;   // (wraps for lanes past the window)
+    const unsigned endrec = 0xFFFF0000u | (unsigned)CP_WS;
+    if (e == 0u) r.x = (r.x & 0x7FFFu) | endrec;
+    if (e == 1u) r.y = (r.y & 0x7FFFu) | endrec;
+    if (e == 2u) r.z = (r.z & 0x7FFFu) | endrec;
+    if (e == 3u) r.w = (r.w & 0x7FFFu) | endrec;
+    if (k0 <= wlen) {
+        *reinterpret_cast<uint4 *>(&L.rec[k0]) = r;
+        *reinterpret_cast<uint32_t *>(&L.bytes[k0]) = w0;
+    }
+    if (wlen == 256u && lane == 63u) reinterpret_cast<uint32_t *>(L.rec)[256] = endrec | cp;
+    wave_sync();
+}
+
 // ------------------------------------------------------------------ the tokenize kernel
 
 constexpr unsigned NPART = 16;   // first-pass work partitions (<= NPART_MAX)
@@ -951,8 +1001,12 @@ __device__ __forceinline__ void reset_counters(uint32_t *ctr, uint64_t *snap = n
 // segment pointer, KREFRESH).
 // The class is the traits of an instantiation (NG, GL, GR, M, GSTR, PLAIN), its view of the wave's LDS (SSr, grp,
 // wsl_of) and the phases that are functions; body() is the driver of a wave's slot loop.
-template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1>
+// LEAN (raw mode's 16-lane first pass; DESIGN.md 4, "the lean pass"): 1 = the lean kernel -- pure-ASCII capless windows
+// only, every other string deferred to a list; 2 = the general kernel launched after it, which takes what the lean
+// waves left of the partitions, then that list
+template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool SOLO = false, int MC = -1, int LEAN = 0>
 struct TokPass {
+    static_assert(LEAN == 0 || (CH == 256 && G == 16 && !BIG && !WIDE && RAW && !SOLO && MC < 0), "the lean route: raw 16-lane rows");
     static constexpr int NG = 64 / G;
     using GL = GroupLDS<CH, G>;
     using GR = Group<G>;
@@ -960,7 +1014,7 @@ struct TokPass {
     static constexpr unsigned GSTR = (unsigned)group_stride<CH, G>();
     // PLAIN: the mode-constant instantiations serve only calls without edges, the uncapped DP or len_only
     // (launch_encode sends those to the runtime-mode kernels): their loop versions are compiled out
-    static constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0) && !SOLO;
+    static constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0 || LEAN == 1) && !SOLO;
 
     // the wave's LDS: slot g's arrays at g * GSTR, then its SlotState (group_stride); its word list in global scratch
     static __device__ __forceinline__ unsigned char *lds() {
@@ -973,6 +1027,22 @@ struct TokPass {
     static __device__ __forceinline__ GL &grp(unsigned g) { return *reinterpret_cast<GL *>(lds() + g * GSTR); }
     static __device__ __forceinline__ uint8_t *wsl_of(ConstKernArgs *kp, unsigned bid, unsigned g) {
         return GL::WSLG ? kp->ea.wsl_scratch + ((size_t)bid * NG + g) * GL::WSL_STRIDE : nullptr;
+    }
+
+    // the lean route's words (dpt_internal.h LeanWord), in the counter block's line after the used-up mask's
+    static __device__ __forceinline__ uint32_t *lean_words(ConstKernArgs *kp) {
+        return kp->ea.part_ctr + LEAN_LINE * PART_STRIDE;
+    }
+    static constexpr unsigned LIST_CLAIM = 0xFFFFFFFFu;   // claim(): the strings are entries of the list, not of a partition
+    // atom j's byte offset and byte length as C2 reads them (the lean kernel's atoms are its windows' bytes: no aoff[])
+    // (auto: aoff[]'s own type where it is read, so the other instantiations compile to what they were)
+    static __device__ __forceinline__ auto aoff_at(const GL &L, unsigned j) {
+        if constexpr (LEAN == 1) return j;
+        else return L.aoff[j];
+    }
+    static __device__ __forceinline__ unsigned alen_at(const GL &L, unsigned j) {
+        if constexpr (LEAN == 1) return 1u;
+        else return L.atom_len(j);
     }
 
     // ---- C0: per-window token counts and validity (row mode)
@@ -1056,7 +1126,7 @@ struct TokPass {
             const bool gv = !len_only && uni(SSr(g).inval) == 0 && uni(SSr(g).status) == 0 && uni(SSr(g).n_atoms) > 0;
             pre[g + 1] = pre[g] + (gv ? uni(SSr(g).wtok) : 0u);
             na_g[g] = uni(SSr(g).n_atoms);
-            firstmask |= ((raw && uni64(SSr(g).pos) == 0 ? 1u : 0u) | (uni(SSr(g).cpw) ? 2u : 0u)) << (2 * g);
+            firstmask |= ((raw && uni64(SSr(g).pos) == 0 ? 1u : 0u) | ((LEAN != 1 && uni(SSr(g).cpw)) ? 2u : 0u)) << (2 * g);
             const uint64_t e0 = uni64(SSr(g).sb) + uni(SSr(g).ntok);
             obase[g] = e0;
         }
@@ -1133,8 +1203,8 @@ struct TokPass {
                     const unsigned jj = (unsigned)L.rec[k].smask;
                     const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
                     const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                    const unsigned p0 = L.aoff[jj];
-                    const unsigned nbytes = (typename GL::Idx)(L.aoff[j1] - p0);
+                    const unsigned p0 = aoff_at(L, jj);
+                    const unsigned nbytes = (typename GL::Idx)(aoff_at(L, j1) - p0);
                     const unsigned fa = q.fw & 1u & (unsigned)(jj == 0);   // (bit 0: raw mode only)
                     uint32_t h = 0, fp = 0;
                     bool hashed;
@@ -1221,8 +1291,8 @@ struct TokPass {
                     const unsigned jj = (unsigned)L.rec[k].smask;
                     const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
                     const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                    const unsigned p0 = L.aoff[jj];
-                    const unsigned nbytes = (uint8_t)(L.aoff[j1] - p0);
+                    const unsigned p0 = aoff_at(L, jj);
+                    const unsigned nbytes = (uint8_t)(aoff_at(L, j1) - p0);
                     const uint32_t *w = reinterpret_cast<const uint32_t *>(L.bytes) + (p0 >> 2);
                     const unsigned two = __builtin_amdgcn_alignbyte(w[1], w[0], p0 & 3u);
                     const unsigned b0 = two & 0xFFu, b1 = (two >> 8) & 0xFFu;
@@ -1296,8 +1366,8 @@ struct TokPass {
                     const unsigned jj = (unsigned)L.rec[k].smask;
                     const unsigned nx = (unsigned)L.rec[k + 1].smask;
                     const unsigned j1 = k + 1 < q.ntk ? nx : q.na;
-                    const unsigned p0 = L.aoff[jj];
-                    const unsigned len = (uint8_t)(L.aoff[j1] - p0);
+                    const unsigned p0 = aoff_at(L, jj);
+                    const unsigned len = (uint8_t)(aoff_at(L, j1) - p0);
                     const unsigned fi = q.fw & 1u & (unsigned)(jj == 0);
                     const unsigned rl = (raw ? 1u : 0u) | (q.fw >> 1);   // raw mode's expansions
                     lng = len > 8u;
@@ -1348,7 +1418,7 @@ struct TokPass {
             const unsigned nx = (unsigned)L.rec[k + 1].smask;   // k + 1 <= ntk < NA
             T.j1 = k + 1 < q.ntk ? nx : q.na;
             T.rl = raw || (q.fw >> 1) != 0u;
-            T.seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[T.jj], L.atom_len(T.jj), 0, q.fw & 1u & (unsigned)(T.jj == 0)), T.rl, T.cnt);
+            T.seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(aoff_at(L, T.jj), alen_at(L, T.jj), 0, q.fw & 1u & (unsigned)(T.jj == 0)), T.rl, T.cnt);
             T.out = q.ob + k;
             return T;
         };
@@ -1391,7 +1461,7 @@ struct TokPass {
                 if (aend & (dn ^ 1u)) {
                     C[w].jj++;
                     const GL &L = *reinterpret_cast<const GL *>(smem + C[w].lbase);
-                    C[w].seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(L.aoff[C[w].jj], L.atom_len(C[w].jj), 0, 0), C[w].rl, C[w].cnt);
+                    C[w].seq = atom_from_info<CH, WIDE>(L.bytes, AInfo<CH>::pack(aoff_at(L, C[w].jj), alen_at(L, C[w].jj), 0, 0), C[w].rl, C[w].cnt);
                 }
             }
             // ---- the trie steps; finished walks write their id and take the next token
@@ -1509,6 +1579,8 @@ struct TokPass {
         const unsigned d = lane % G;         // my back distance - 1
         const uint64_t n_work = BIG ? (uint64_t)(*a.work_count) : a.n_str;
         if constexpr (BIG)
+            // (BIG passes only: the lean route's kernels carry another pointer in hist_zero -- the host's mirror of the
+            // hint, launch_lean_pair -- with n_hist 0; a first-pass kernel must never zero through it)
             if (a.hist_zero && bid == 0)
                 for (uint32_t b = lane; b < a.n_hist; b += 64u) a.hist_zero[b] = 0;
         if (BIG && n_work == 0) return;   // no retries: no counter traffic
@@ -1543,9 +1615,48 @@ struct TokPass {
 #else
 #define WST_CLAIM()
 #endif
+        // The lean route (LEAN != 0).  The lean kernel defers every string it does not take to the list
+        // a.work_list / a.work_count (the first pass's own partitions need neither), and reads the context's hint
+        // at every claim: once it says "off" the wave claims nothing more, and the general kernel launched after it
+        // finds the rest of the partitions.  That kernel (LEAN == 2) goes on from the partitions to the list.
+        // lean_words(): the hint line of the counter block, never reset between calls.
+        [[maybe_unused]] unsigned n_def = 0, n_got = 0;   // LEAN == 1: the wave's deferred / claimed strings
+        [[maybe_unused]] bool from_list = false;          // LEAN == 2: the partitions are used up
+        [[maybe_unused]] bool probe = false;              // LEAN == 1: the hint is off and this wave (the grid's first) tries it
         auto claim = [&](unsigned req, uint64_t &nb, uint64_t &ne, unsigned &cp) {
             for (;;) {
                 WST_CLAIM();
+                if constexpr (LEAN == 1) {
+                    // the hint (dpt_internal.h LeanWord): off since a lean wave deferred too much, in this call or an
+                    // earlier one.  The grid's first wave then makes the probe: the batch's first strings (unclaimed: the
+                    // general launch takes them like every other) through prep and phase A, nothing written, and the
+                    // hint on again if none of them would have been deferred.
+                    unsigned off = 0;
+                    if (lane == 0) off = __hip_atomic_load(lean_words(kp) + LEAN_OFF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (__builtin_amdgcn_readfirstlane(off)) {
+                        nb = ne = 0; cp = 0;
+                        if (bid == 0 && n_got == 0 && !probe) {
+                            probe = true;
+                            const uint64_t p0 = part_size((unsigned)n_work, npart, 0u);
+                            ne = req < p0 ? req : p0;
+                            if (lane == 0) atomicAdd(lean_words(kp) + LEAN_PROBES, 1u);
+                        }
+                        claimed_all = true;
+                        return;
+                    }
+                }
+                if constexpr (LEAN == 2) {
+                    if (from_list) {   // the lean kernel's list: final before this launch began
+                        const uint64_t hi = *a.work_count;
+                        unsigned b = 0;
+                        if (hi != 0 && lane == 0) b = atomicAdd(a.work_next, req);   // (nothing deferred: no counter traffic)
+                        cp = LIST_CLAIM;
+                        nb = (uint32_t)__builtin_amdgcn_readlane(b, 0);
+                        ne = nb < hi ? (nb + req < hi ? nb + req : hi) : nb;
+                        if (nb + req >= hi) claimed_all = true;
+                        return;
+                    }
+                }
                 uint32_t *ctr = BIG ? a.work_next : a.part_ctr + part * PART_STRIDE;
                 const uint64_t hi = BIG ? n_work : part_size((unsigned)n_work, npart, part);
                 unsigned b = 0;
@@ -1574,7 +1685,8 @@ struct TokPass {
                         m = __builtin_amdgcn_readlane(m, 0) | (1u << part);
                         const unsigned all = (npart >= 32u ? 0u : (1u << npart)) - 1u;
                         if ((m & all) == all) {
-                            claimed_all = true;
+                            if constexpr (LEAN == 2) from_list = true;
+                            else claimed_all = true;
                         } else {   // the next unmarked partition after this one
                             const unsigned free = ~m & all;
                             const unsigned hi_free = free & ~((2u << part) - 1u);
@@ -1585,6 +1697,40 @@ struct TokPass {
                 if (ne > nb || claimed_all) return;
             }
         };
+
+        // LEAN == 1: slot S's string is not the lean kernel's (a window with a byte >= 0x80, or one that is not
+        // capless): on the list with it, the slot freed, nothing counted -- the pass that retakes the string starts it
+        // again at its first byte and writes the same staging elements any earlier window of it wrote here.  A wave
+        // that has deferred LEAN_DEF_MIN strings and more than a quarter of what it claimed turns the hint off: this is
+        // not the lean kernel's text (all-Arabic: every wave's first refill; 1 % of the strings: practically never).
+        // (The probe only counts.)
+        constexpr unsigned LEAN_DEF_MIN = 6;
+        // the hint, and its mirror in pinned host memory (a.hist_zero in the lean kernel: launch_lean_pair), which the
+        // host reads when it plans the context's next call
+        [[maybe_unused]] auto set_hint = [&](unsigned off) {
+            __hip_atomic_store(lean_words(kp) + LEAN_OFF, off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t *mirror = reinterpret_cast<uint32_t *>(a.hist_zero);
+            if (mirror) __hip_atomic_store(mirror, off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        };
+        [[maybe_unused]] auto defer_slot = [&](SlotState &S) {
+            if (lane == 0) {
+                if (!probe) const_cast<uint32_t *>(a.work_list)[atomicAdd(const_cast<uint32_t *>(a.work_count), 1u)] = S.s;
+                S.active = 0;
+            }
+            n_def++;
+            if (!probe && n_def >= LEAN_DEF_MIN && 4u * n_def > n_got && lane == 0) set_hint(1u);
+        };
+        if constexpr (LEAN == 2) {
+            // after a lean launch that consumed everything the used-up mask is full: straight to the list (empty:
+            // the wave ends without one atomic -- every wave's atomics on the mask word cost 0.15 ms per call)
+            const unsigned m = __builtin_amdgcn_readfirstlane(
+                __hip_atomic_load(a.part_ctr + (unsigned)NPART * PART_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            const unsigned all = (npart >= 32u ? 0u : (1u << npart)) - 1u;
+            if ((m & all) == all) from_list = true;
+            // (for the tests: what the lean launch deferred, kept past the counters' reset)
+            if (bid == 0 && lane == 0)
+                __hip_atomic_store(lean_words(kp) + LEAN_DEFERRED, *a.work_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
 
         [[maybe_unused]] Stamps st;
         WST_REC(0, WST_NOW());
@@ -1622,7 +1768,8 @@ struct TokPass {
                             const unsigned k = (unsigned)__builtin_popcount(rem & ((1u << lane) - 1u));
                             if (k < got) {
                                 const uint64_t idx = nb + k;
-                                const uint64_t s = BIG ? (uint64_t)a.work_list[idx] : part_string(npart, cp, (unsigned)idx);
+                                const uint64_t s = (BIG || (LEAN == 2 && cp == LIST_CLAIM)) ? (uint64_t)a.work_list[idx]
+                                                                                            : part_string(npart, cp, (unsigned)idx);
                                 uint64_t o0, o1;
                                 if constexpr (!BIG && (DPT_DIAG_PREP & 2)) { o0 = s * 256u; o1 = o0 + 256u; }   // diagnostic (cfg2)
                                 else { o0 = a.str_off[s]; o1 = a.str_off[s + 1]; }
@@ -1639,6 +1786,7 @@ struct TokPass {
                         uint64_t nb = 0, ne = 0;
                         unsigned cp = 0;
                         claim(n_need, nb, ne, cp);
+                        if constexpr (LEAN == 1) n_got += (unsigned)(ne - nb);
                         assign(nb, ne, cp);
                     }
                     if (claimed_all) exhausted = true;
@@ -1666,7 +1814,28 @@ struct TokPass {
                     unsigned wlen = 0, na = 0, nw = 0, cpw = 0;
                     bool ok = status != 2;
                     if (ok) ok = window_bounds<CH>(W[g], slen, pos, mode, lane, wlen);
-                    if (ok) ok = prep_window<CH, G, WIDE>(L, wsl_of(kp, bid, g), W[g], pos, wlen, mode, lane, na, nw, cpw);
+                    if constexpr (LEAN == 1) {
+                        if (ok) {   // a byte >= 0x80 in the window: not this kernel's
+                            const unsigned nv = wlen > 4u * lane ? min(wlen - 4u * lane, 4u) : 0u;   // the lane's bytes in it
+                            const uint32_t hi = W[g].t[0] & (nv >= 4u ? 0x80808080u : ((1u << (8u * nv)) - 1u) & 0x80808080u);
+                            if (ballot(hi != 0)) {
+                                defer_slot(S);
+                                refill = true;
+                                continue;
+                            }
+                            prep_window_lean(L, W[g], pos, wlen, lane);
+                            na = wlen;
+                        }
+                    } else {
+                        if (ok) ok = prep_window<CH, G, WIDE>(L, wsl_of(kp, bid, g), W[g], pos, wlen, mode, lane, na, nw, cpw);
+                    }
+                    if constexpr (LEAN == 1) {
+                        if (probe && !ok) {   // (nothing written; an empty string is anybody's, a long word is not lean text)
+                            if (status != 2) n_def++;
+                            if (lane == 0) S.active = 0;
+                            continue;
+                        }
+                    }
                     if (ok) {
                         if (lane == 0) { S.wlen = wlen; S.n_atoms = na; S.n_words = nw; S.wtok = 0; S.inval = 0; S.capb = 0; S.cpw = (uint8_t)cpw; }
                         prepared |= 1u << g;
@@ -1715,6 +1884,10 @@ struct TokPass {
 #pragma unroll
                         for (int g = 0; g < NG; g++)
                             if (uni(SSr(g).n_atoms) > 0 && uni(SSr(g).cpw)) a0mask |= 1u << g;
+                    } else if constexpr (LEAN == 1) {   // (every prepared window is pure ASCII)
+#pragma unroll
+                        for (int g = 0; g < NG; g++)
+                            if (uni(SSr(g).n_atoms) > 0) a0mask |= 1u << g;
                     } else {
 #pragma unroll
                         for (int g = 0; g < NG; g++) {
@@ -2217,6 +2390,7 @@ struct TokPass {
                         }
                     }
                 }
+                if constexpr (LEAN != 1) {   // (the lean kernel has no window for the generic walker)
                 unsigned pre[NG + 1];
                 pre[0] = 0;
 #pragma unroll
@@ -2316,6 +2490,7 @@ struct TokPass {
                     capm |= (done & (((unsigned)mask & 1u) ^ 1u)) << gsel;
                     active = active && !done;
                 }
+                }   // if constexpr (LEAN != 1)
                 // the slots whose walk found an atom that is no token by itself
 #pragma unroll
                 for (int g = 0; g < NG; g++)
@@ -2323,6 +2498,23 @@ struct TokPass {
             }
             wave_sync();
             STAMP(1);
+            if constexpr (LEAN == 1) {
+                // a window that is not capless (some byte of it is no token by itself): B's row mode is not in this
+                // kernel -- the string is deferred, and its slot goes through the rest of the round empty
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    SlotState &S = SSr(g);
+                    if (uni(S.n_atoms) > 0 && uni(S.capb)) {
+                        defer_slot(S);
+                        if (lane == 0) { S.n_atoms = 0; S.n_words = 0; S.capb = 0; }
+                    }
+                }
+                wave_sync();
+                if (probe) {   // the first strings' first windows are all lean text: the next call's lean waves claim again
+                    if (n_def == 0 && lane == 0) set_hint(0u);
+                    break;
+                }
+            }
 
             // ---------------------------------------------------------- B: forward recurrence
             KREFRESH();
@@ -2899,7 +3091,12 @@ struct TokPass {
                 unsigned capb = 0;
 #pragma unroll
                 for (int g = 0; g < NG; g++) capb |= uni(SSr(g).capb);
-                if (!PLAIN && a.edges) {
+                if constexpr (LEAN == 1) {   // (capless windows only: the others were deferred after A)
+                    if constexpr (DPT_LEAN_SETPRIO != 0) __builtin_amdgcn_s_setprio(DPT_LEAN_SETPRIO);
+                    forward_lanes();
+                    if constexpr (DPT_LEAN_SETPRIO != 0) __builtin_amdgcn_s_setprio(0);
+                    lane_mode = true;
+                } else if (!PLAIN && a.edges) {
                     if (!capb) forward(T_{}, C2_{}); else if (uncapped) forward(T_{}, C1_{}); else forward(T_{}, C0_{});
                 } else {
                     if (!capb) {
@@ -3023,6 +3220,15 @@ template <int CH, int G, bool BIG, bool WIDE, int SW = 0, bool RAW = false, bool
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SOLO ? 1 : ((CH == 256 && G == 16) ? WPE16 : ((CH == 256 && G == 64) ? WPE64 : 1)))))
 tokenize_kernel(KernArgs ka) {
     tokenize_body<CH, G, BIG, WIDE, SW, RAW, SOLO, MC>(blockIdx.x);
+}
+
+// The lean route of plain raw calls (16-lane rows): LEAN = 1, the lean kernel, then LEAN = 2, the general kernel that
+// takes the rest of the partitions and the deferred strings (TokPass).  Kernels of their own: the instantiations of
+// tokenize_kernel are what they were.
+template <int SW, int LEAN>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE16)))
+tokenize_lean_kernel(KernArgs ka) {
+    TokPass<SMALL_CH, 16, false, false, SW, true, false, -1, LEAN>::body(blockIdx.x);
 }
 
 // ------------------------------------------------------------------ compaction
@@ -3452,6 +3658,7 @@ const LaunchKnobs &launch_knobs() {
         k.no_solo = getenv("DPT_NO_SOLO") != nullptr;
         k.no_mid = getenv("DPT_NO_MID") != nullptr;
         k.no_small_wpc = getenv("DPT_NO_SMALL_WPC") != nullptr;
+        k.no_lean = getenv("DPT_NO_LEAN") != nullptr;
         const char *fb = getenv("DPT_FB_BIG_PER_CU"), *wpc = getenv("DPT_WAVES_PER_CU");
         k.fb_big_per_cu = fb ? atoi(fb) : 3;
         k.waves_per_cu = wpc ? atoi(wpc) : 0;
@@ -3486,6 +3693,7 @@ struct PlanKey {   // all the plan depends on: EncodeLaunch's fields of these na
 };
 struct LaunchPlan {
     TokChoice first;
+    bool lean;               // plain raw calls of 16-lane rows: tokenize_lean_kernel<first.sw, 1>, then <first.sw, 2> in first's place
     bool mid, fallback;      // the 512-byte pass / the 2048-byte + unbounded launch run ...
     MidChoice midk;
     FallbackChoice fb;
@@ -3524,7 +3732,10 @@ static LaunchPlan plan_encode(const PlanKey &k, const LaunchKnobs &kn) {
         // the one-string kernel: lane-mode B and its C1 walks over the whole wave (forward_lanes, SOLO)
         if (solo && !wide && !kn.no_solo_wave) pl.first = TokChoice{16, false, 2, raw, true, -1};
         else if (wide) pl.first = TokChoice{16, true, sw, false, false, mc};
-        else if (raw && plain && !kn.generic_raw) pl.first = TokChoice{16, false, sw, true, false, -1};
+        else if (raw && plain && !kn.generic_raw) {
+            pl.first = TokChoice{16, false, sw, true, false, -1};
+            pl.lean = !solo && !kn.no_lean;   // (a solo call with DPT_NO_SOLO_WAVE: its lone wave does the tail too)
+        }
         else pl.first = TokChoice{16, false, sw, false, false, mc};
     } else {
         pl.first = wide ? TokChoice{64, true, 0, false, false, mc} : TokChoice{64, false, 0, raw && plain, false, -1};
@@ -3819,19 +4030,42 @@ static hipError_t launch_tail(const EncodeLaunch &p, const LaunchPlan &plan, hip
     return eh;
 }
 
+// The lean route's two launches in the first pass's place (defined at the end of the file: the lean kernels are named
+// there alone, so they sit after every other kernel in the code object and move none of them).
+static hipError_t launch_lean_pair(int sw, const EncodeLaunch &p, const EncodeArgs &a, const TrieView &tv, hipStream_t stream,
+                                   hipEvent_t ev_start);
+static bool lean_kernels_exist(int sw);
+
+static PlanKey plan_key(const EncodeLaunch &p, bool profiled) {
+    return PlanKey{p.variant, p.mode, p.staging16 != nullptr, p.edges != nullptr, p.solo, p.padded, p.no_fallback,
+                   profiled, p.n_str, p.hist != nullptr, p.hist_overwrite, p.hist_bins};
+}
+
+bool lean_eligible(const EncodeLaunch &p) {
+    LaunchKnobs kn = launch_knobs();
+    kn.no_lean = false;
+    return plan_encode(plan_key(p, false), kn).lean;
+}
+
 hipError_t launch_encode(const EncodeLaunch &p, hipStream_t stream, hipEvent_t ev[2]) {
-    const PlanKey key{p.variant, p.mode, p.staging16 != nullptr, p.edges != nullptr, p.solo, p.padded, p.no_fallback,
-                      ev != nullptr, p.n_str, p.hist != nullptr, p.hist_overwrite, p.hist_bins};
-    const LaunchPlan plan = plan_encode(key, launch_knobs());
+    const PlanKey key = plan_key(p, ev != nullptr);
+    LaunchKnobs kn = launch_knobs();
+    kn.no_lean = kn.no_lean || p.lean_skip;   // (the context's hint, or its test switch: dpt_ctx_debug_no_lean)
+    const LaunchPlan plan = plan_encode(key, kn);
     if (plan.tail == TAIL_EMPTY) return launch_empty(p, plan, stream);
     const EncodeArgs a = first_pass_args(p, plan.tail == TAIL_SOLO);
     const TrieView tv{p.slots, p.slot_ids, p.slots4, p.root_base, p.n_slots, p.pair16};
     // profiling (dpt_ctx_profile): the first pass's dispatch records ev[0], the fallback launch's ev[1]
-    hipError_t e = with_first_kernel(plan.first, [&](auto k) {
-        const bool g16 = plan.first.g == 16;
-        const uint64_t n_units = plan.first.solo ? 1 : g16 ? (p.n_str + 3) / 4 : p.n_str;   // 16-lane rows: 4 strings per wave
-        return launch_tok(k, g16, a, tv, n_units, p.max_blocks / 64, stream, ev ? ev[0] : nullptr);
-    });
+    hipError_t e;
+    if (plan.lean) {
+        e = launch_lean_pair(plan.first.sw, p, a, tv, stream, ev ? ev[0] : nullptr);
+    } else {
+        e = with_first_kernel(plan.first, [&](auto k) {
+            const bool g16 = plan.first.g == 16;
+            const uint64_t n_units = plan.first.solo ? 1 : g16 ? (p.n_str + 3) / 4 : p.n_str;   // 16-lane rows: 4 strings per wave
+            return launch_tok(k, g16, a, tv, n_units, p.max_blocks / 64, stream, ev ? ev[0] : nullptr);
+        });
+    }
     if (e != hipSuccess) return e;
     if (plan.tail == TAIL_SOLO) return hipGetLastError();
     if (plan.mid && (e = launch_mid(p, plan, a, tv, stream)) != hipSuccess) return e;
@@ -3845,6 +4079,7 @@ extern "C" int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int 
     if (!out) return DPT_E_ARG;
     LaunchKnobs kn = {};
     kn.generic_ps = knobs & 1u; kn.generic_raw = knobs & 2u; kn.no_solo_wave = knobs & 4u; kn.no_mid = knobs & 8u;
+    kn.no_lean = knobs & 16u;
     const LaunchPlan pl = plan_encode(PlanKey{variant, mode_flags, st16 != 0, edges != 0, solo != 0, padded != 0, no_fallback != 0,
                                               profiled != 0, n_str, hist != 0, hist == 2, hist_bins}, kn);
     const int32_t v[DPT_LAUNCH_PLAN_INTS] = {
@@ -3854,9 +4089,22 @@ extern "C" int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int 
     for (int q = 0; q < DPT_LAUNCH_PLAN_INTS; q++) out[q] = v[q];
     auto exists = [](auto) { return hipSuccess; };   // every kernel the plan names must be instantiated
     const bool ok = pl.tail == TAIL_EMPTY || (with_first_kernel(pl.first, exists) == hipSuccess &&
+                                              (!pl.lean || lean_kernels_exist(pl.first.sw)) &&
                                               (!pl.mid || with_mid_kernel(pl.midk, exists) == hipSuccess) &&
                                               (!pl.fallback || with_fallback_kernel(pl.fb, exists) == hipSuccess));
     return ok ? DPT_OK : DPT_E_ARG;
+}
+
+extern "C" int dpt_debug_launch_plan_lean(int variant, int mode_flags, int st16, int edges, int solo, int padded, uint64_t n_str,
+                                          unsigned knobs, int32_t *lean) {
+    if (!lean) return DPT_E_ARG;
+    LaunchKnobs kn = {};
+    kn.generic_ps = knobs & 1u; kn.generic_raw = knobs & 2u; kn.no_solo_wave = knobs & 4u; kn.no_mid = knobs & 8u;
+    kn.no_lean = knobs & 16u;
+    const LaunchPlan pl = plan_encode(PlanKey{variant, mode_flags, st16 != 0, edges != 0, solo != 0, padded != 0, false, false,
+                                              n_str, false, false, 0}, kn);
+    *lean = pl.lean;
+    return !pl.lean || lean_kernels_exist(pl.first.sw) ? DPT_OK : DPT_E_ARG;
 }
 
 size_t pend_scratch_bytes(unsigned max_blocks) { return (size_t)max_blocks * 64 * sizeof(uint4); }
@@ -3920,5 +4168,33 @@ extern "C" int dpt_debug_wstamps(unsigned long long *out, int reset) {
 }
 extern "C" int dpt_debug_wstamps_dims(unsigned *maxw, unsigned *n) { *maxw = WST_MAXW; *n = WST_N; return 0; }
 #endif
+
+// ------------------------------------------------------------------ the lean route's kernels
+// (the only place that names an instantiation of tokenize_lean_kernel: see launch_lean_pair's declaration)
+template <class F> static hipError_t with_lean_kernels(int sw, F &&f) {   // f(lean, general) of a staged id width
+    constexpr int lds = block_lds_bytes<SMALL_CH, 16>();
+    if (sw == 1) return f(Kern<tokenize_lean_kernel<1, 1>, lds>{}, Kern<tokenize_lean_kernel<1, 2>, lds>{});
+    if (sw == 2) return f(Kern<tokenize_lean_kernel<2, 1>, lds>{}, Kern<tokenize_lean_kernel<2, 2>, lds>{});
+    return hipErrorNotSupported;
+}
+
+static bool lean_kernels_exist(int sw) {
+    return with_lean_kernels(sw, [](auto, auto) { return hipSuccess; }) == hipSuccess;
+}
+
+static hipError_t launch_lean_pair(int sw, const EncodeLaunch &p, const EncodeArgs &a, const TrieView &tv, hipStream_t stream,
+                                   hipEvent_t ev_start) {
+    // the lean kernel defers to the list no other pass of a raw call uses; the general kernel reads it after its
+    // partitions (the stream orders the two launches: the list is final when the second begins)
+    EncodeArgs la = a;
+    la.work_list = retry_list_of(p, LIST_BIG_AFTER_MID); la.work_count = &p.ctr->mid_retry_count; la.work_next = &p.ctr->mid_work;
+    // (hist_zero is the 2048-byte pass's: the lean kernel finds the host's mirror of the hint in it)
+    la.hist_zero = reinterpret_cast<unsigned long long *>(p.lean_mirror);
+    return with_lean_kernels(sw, [&](auto lean, auto general) {
+        const uint64_t n_units = (p.n_str + 3) / 4;   // 16-lane rows: 4 strings per wave
+        const hipError_t e1 = launch_tok(lean, true, la, tv, n_units, p.max_blocks / 64, stream, ev_start);
+        return e1 != hipSuccess ? e1 : launch_tok(general, true, la, tv, n_units, p.max_blocks / 64, stream, nullptr);
+    });
+}
 
 }  // namespace dpt

@@ -90,6 +90,13 @@ struct dpt_ctx {
     // test-only (dpt_ctx_debug_counter_bias): every call starts the unbounded pass's arena counter and the
     // far-pair counter at this value, the arena and far pointers passed down shifted by it
     uint64_t counter_bias = 0;
+    // The lean route's hint as the host sees it (dpt_internal.h LeanWord): lean_host[0] mirrors LEAN_OFF -- the lean
+    // kernels store it to this pinned word as well -- and is read without a synchronise when a call is planned: while it
+    // says "off" only every LEAN_RETRY-th call launches the lean kernel (whose probe may turn the hint on again), the
+    // others run the general kernel alone, as before the lean route.  A stale read costs one call the better route.
+    uint32_t *lean_host = nullptr, *lean_host_dev = nullptr;
+    uint32_t lean_skipped = 0;   // calls planned without the lean launch since the hint went off
+    bool debug_no_lean = false;  // test-only (dpt_ctx_debug_no_lean): no call of this context takes the lean route
 };
 
 namespace dpt {

@@ -84,6 +84,9 @@ CALLS = {
     "dpt_ctx_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), PU64]),
     "dpt_ctx_debug_counter_bias": (I32, [P, U64]),
     "dpt_debug_launch_plan": (I32, [I32] * 8 + [U64, I32, U32, U32, ctypes.POINTER(I32)]),
+    "dpt_debug_launch_plan_lean": (I32, [I32] * 6 + [U64, U32, ctypes.POINTER(I32)]),
+    "dpt_ctx_debug_lean_words": (I32, [P, ctypes.POINTER(U32)]),
+    "dpt_ctx_debug_no_lean": (I32, [P, I32]),
     "dpt_debug_vocab_table": (I32, [P, P, P, U32, I32, P, U64, PU64]),
     "dpt_debug_host_layout": (I32, [I32, U64, U64, U64, I32, U64, PU64]),
     "dpt_debug_wave_grid": (I32, [U64, U32, ctypes.POINTER(U32)]),

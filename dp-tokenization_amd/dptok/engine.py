@@ -271,6 +271,17 @@ class Encoder:
                          stream: int = 0) -> None:
         check(_lib.lib().dpt_token_histogram(idoff_ptr, status_ptr, n_str, hist_ptr, n_bins, stream), "dpt_token_histogram")
 
+    def debug_no_lean(self, on: bool) -> None:
+        """TEST-ONLY (dpt_ctx_debug_no_lean): this engine's calls without the lean launch."""
+        check(_lib.lib().dpt_ctx_debug_no_lean(self.handle, 1 if on else 0), "dpt_ctx_debug_no_lean")
+
+    def debug_lean_words(self):
+        """TEST-ONLY (dpt_ctx_debug_lean_words): (hint off, strings the last lean launch deferred, probes so far, calls without
+        the lean launch since the hint went off)."""
+        out = (ctypes.c_uint32 * 4)()
+        check(_lib.lib().dpt_ctx_debug_lean_words(self.handle, out), "dpt_ctx_debug_lean_words")
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
     def debug_counter_bias(self, bias: int) -> None:
         """TEST-ONLY (dpt_ctx_debug_counter_bias): later calls start the unbounded pass's arena and far-pair
         counters at ``bias`` (results unchanged; its kernels' offsets become >= bias)."""

@@ -553,10 +553,23 @@ int dpt_ctx_debug_counter_bias(dpt_ctx *c, uint64_t bias);
  * list the 2048-byte pass reads (0 / 2: the first / 512-byte pass's); [14] the tail: 0 memsets, 1 nothing
  * (solo), 2 reset_kernel, 3 scan + finish, 4 fold finish, 5 one-batch finish; [15] finish width in bits;
  * [16..19] the histogram is folded into the finish pass, stored by it, zeroed by (0 nobody, 1 the 2048-byte
- * pass, 2 the scan, 3 a memset), the separate pass follows.  DPT_E_ARG: a kernel it names does not exist. */
+ * pass, 2 the scan, 3 a memset), the separate pass follows.  DPT_E_ARG: a kernel it names does not exist.
+ * One more knob: 16 DPT_NO_LEAN (it changes none of these ints: dpt_debug_launch_plan_lean). */
 #define DPT_LAUNCH_PLAN_INTS 20
 int dpt_debug_launch_plan(int variant, int mode_flags, int st16, int edges, int solo, int padded, int no_fallback,
                           int profiled, uint64_t n_str, int hist, uint32_t hist_bins, unsigned knobs, int32_t *out);
+/* TEST-ONLY, needs no device.  *lean = 1 when such a call takes the lean route: the lean kernel, then the general
+ * one fed the deferred strings, in the first pass's place (tests/test_launch_plan_lean.py). */
+int dpt_debug_launch_plan_lean(int variant, int mode_flags, int st16, int edges, int solo, int padded, uint64_t n_str,
+                               unsigned knobs, int32_t *lean);
+/* TEST-ONLY.  The context's lean-route words after its last call (waits for the device): out[0] the hint (nonzero:
+ * the lean waves claim nothing), out[1] the strings the last lean launch deferred, out[2] the probes made so far,
+ * out[3] the calls planned without the lean launch since the hint went off (the host's side of it).  A context
+ * that has made no call yet: zeros. */
+int dpt_ctx_debug_lean_words(dpt_ctx *c, uint32_t out[4]);
+/* TEST-ONLY.  on != 0: the context's calls run without the lean launch (as the whole process does with DPT_NO_LEAN set
+ * when it starts), and do not count for the hint; 0: back to the plan's choice. */
+int dpt_ctx_debug_no_lean(dpt_ctx *c, int on);
 
 /* TEST-ONLY, needs no device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  The bytes dpt_vocab_create
  * would upload for this vocabulary (its first four arguments), built on the host

@@ -39,15 +39,21 @@ def run_pass(counter: str, n: int, out: str, rerun: bool = True, lib: str = None
     if rerun:
         with open(out + ".log", "w") as log:
             subprocess.run(cmd, check=True, stdout=log, stderr=subprocess.STDOUT, env=env, timeout=600)
-    vals = []
+    # the first pass only: tokenize_kernel<256, ...>, or -- plain raw calls -- the lean route's pair
+    # tokenize_lean_kernel<SW, 1> (lean) + <SW, 2> (general, list-fed), summed per call
+    total, calls = 0.0, 0
     for f in glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row.get("Kernel_Name", "")
-            if "tokenize_kernel<256" in name and row["Counter_Name"] == counter:   # the first pass only
-                vals.append(float(row["Counter_Value"]))
-    if not vals:
+            if row["Counter_Name"] != counter:
+                continue
+            m = re.search(r"tokenize_lean_kernel<\d+, *(\d+)>", name)
+            if "tokenize_kernel<256" in name or m:
+                total += float(row["Counter_Value"])
+                calls += 0 if (m and m.group(1) == "2") else 1
+    if not calls:
         raise RuntimeError("no %s samples for the tokenize kernel" % counter)
-    return sum(vals) / len(vals) * 1024.0   # KB -> bytes
+    return total / calls * 1024.0   # KB -> bytes
 
 
 def main():
