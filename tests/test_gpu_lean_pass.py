@@ -6,9 +6,9 @@ DPT_HIST_OVERWRITE histogram: ids, offsets, status and histogram must be identic
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from lean_routes import both_routes as _both_routes, device_call as _device_call
 
-N_BINS = 64
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -21,45 +21,6 @@ def engines(vocabs):
 def oracles(vocabs):
     from oracle import oracle
     return {k: oracle.OracleVocab(v) for k, v in vocabs.items()}
-
-
-def _device_call(enc, text, offs):
-    import torch
-    n = len(offs) - 1
-    cap = max(len(text), 1)
-    dt = torch.from_numpy(np.array(text) if len(text) else np.zeros(1, np.uint8)).cuda()
-    do = torch.from_numpy(offs.astype(np.uint64).view(np.int64)).cuda()
-    ids = torch.full((cap,), -7, dtype=torch.int32, device="cuda")
-    id_off = torch.empty(n + 1, dtype=torch.int64, device="cuda")
-    st = torch.empty(n, dtype=torch.int32, device="cuda")
-    capped = torch.empty(n, dtype=torch.int32, device="cuda")
-    hist = torch.full((N_BINS + 8,), -3, dtype=torch.int64, device="cuda")
-    enc.set_histogram(hist.data_ptr(), N_BINS, overwrite=True)
-    enc.encode_device(dt.data_ptr(), len(text), do.data_ptr(), n, ids.data_ptr(), cap, id_off.data_ptr(), st.data_ptr(),
-                      capped_ptr=capped.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    off_h = id_off.cpu().numpy().view(np.uint64)
-    return ids[: int(off_h[-1])].cpu().numpy(), off_h, st.cpu().numpy(), capped.cpu().numpy(), hist.cpu().numpy()
-
-
-def _both_routes(enc, orc, text, offs):
-    """lean on, lean off (the launch knob), both against the oracle; returns the oracle's (ids, off, status, capped)"""
-    lean = _device_call(enc, text, offs)
-    enc.debug_no_lean(True)
-    try:
-        plain = _device_call(enc, text, offs)
-    finally:
-        enc.debug_no_lean(False)
-    for k, (x, y) in enumerate(zip(lean, plain)):
-        assert np.array_equal(x, y), ("lean route differs from the general kernel alone", k)
-    ref = orc.encode_csr(text, offs)
-    for k in range(4):   # ids, offsets, status, capped
-        assert np.array_equal(lean[k], ref[k]), (k, np.nonzero(np.asarray(lean[k][:len(ref[k])]) != ref[k][:len(lean[k])])[0][:10])
-    counts = np.diff(ref[1].astype(np.int64))
-    assert lean[4][N_BINS] == counts.sum() and lean[4][N_BINS + 1] == len(counts)
-    # the ids tile [0, n_tok): every string once
-    assert int(ref[1][-1]) == len(lean[0]) and np.all(np.diff(lean[1].astype(np.int64)) >= 0)
-    return ref
 
 
 def _pack(texts):

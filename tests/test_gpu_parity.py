@@ -4,6 +4,7 @@ seeded random inputs at larger sizes."""
 import numpy as np
 import pytest
 
+import raw_corpora
 from conftest import CORPUS_FIXTURES, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -87,15 +88,7 @@ def test_s2orc_and_arabic_vs_oracle(engines, oracles):
 def test_long_words_big_window(engines, oracles):
     """Words longer than the 256-byte window take the 2048-byte pass; longer ones the unbounded
     pass (dpt_long.hip).  Every length is exact -- the reference has no length limit."""
-    rng = np.random.default_rng(5)
-    texts = []
-    for L in (255, 256, 257, 300, 700, 1500, 2047, 2048, 2049, 3000, 5000, 20000):
-        w = "".join(chr(c) for c in rng.integers(0x21, 0x7F, size=L))
-        texts.append(w)
-        texts.append("ab cd " + w + " ef")
-        texts.append(w + " " + w[: L // 2])
-        texts.append(("\n" + w[:L // 3] + " x\n").join([w[:100], w[100:]]))
-    text, offs = _csr(texts)
+    text, offs = raw_corpora.long_words_corpus()
     got = engines["llama32k"].encode_csr(text, offs)
     ref = oracles["llama32k"].encode_csr(text, offs)
     _cmp_csr(got, ref)
@@ -412,15 +405,9 @@ def test_tie_heavy_long_words_vs_oracle():
     """Lane-mode B + C1 (chunks cut inside words) on tie-heavy capless vocabularies over {a,b,c}:
     long words, many equal-cost tokenizations, several L*-length tokens per word (the chance-flag
     re-walk), batches that fill every row of every wave."""
-    from dptok import Encoder, Vocab, pack_strings
+    from dptok import Encoder, Vocab
     from oracle import oracle
-    from test_lane_model import tie_heavy_case
-    rng = np.random.default_rng(21)
-    for _ in range(30):
-        vocab, _ = tie_heavy_case(rng)
-        t2i = {t: i for i, t in enumerate(vocab)}
-        texts = [tie_heavy_case(rng, max_len=256)[1] for _ in range(400)]
-        text, offs = pack_strings(texts)
+    for t2i, text, offs in raw_corpora.tie_heavy_cases(30, 400):
         got = Encoder(Vocab(t2i, 0)).encode_csr(text, offs)
         ref = oracle.OracleVocab(t2i).encode_csr(text, offs)
         _cmp_csr(got, ref)
@@ -432,14 +419,7 @@ def test_ascii_windows_phase_a0(engines, oracles):
     '\\n' next to spaces, runs of spaces, words cut by the 256-byte windows (later windows start
     with a space), on the 32k vocabulary (capless windows: lane-mode B/C1) and the toy vocabulary
     (many atoms are not tokens: the row recurrence), against the C oracle."""
-    rng = np.random.default_rng(23)
-    pool = [chr(c) for c in range(0x20, 0x7F)] * 3 + ["\n", "\t", "\x01", "\x7f", "  ", " \n", "\n "]
-    texts = []
-    for k in range(3000):
-        n = int(rng.integers(0, 900)) if k % 4 else int(rng.integers(200, 320))
-        texts.append("".join(rng.choice(pool, size=n)))
-    texts += ["\n" * 300, " " * 300, "a" * 600, ("ab " * 200), "\t" * 257]
-    text, offs = _csr(texts)
+    text, offs = raw_corpora.a0_corpus()
     for name in ("llama32k", "toy1k"):
         got = engines[name].encode_csr(text, offs)
         ref = oracles[name].encode_csr(text, offs)
@@ -455,32 +435,9 @@ def test_ascii_walker_and_token_hash(seed):
     first atom; tokens with a newline atom and longer ones left to the walkers) on a vocabulary of
     long letter tokens and newline-bearing tokens, over multi-window strings, against the C oracle.
     Seed 32 leaves '\u2581' itself out of the vocabulary (a word start is then no token)."""
-    from dptok import Encoder, Vocab, pack_strings
+    from dptok import Encoder, Vocab
     from oracle import oracle
-    rng = np.random.default_rng(seed)
-    letters = "etaoinsh"
-    vocab = set(letters) | {"\u2581" + c for c in letters} | {"<0x0A>", "\n"}
-    if seed == 31:
-        vocab.add("\u2581")
-    for _ in range(3000):
-        L = int(rng.integers(2, 17))
-        w = "".join(rng.choice(list(letters), size=L))
-        r = rng.random()
-        if r < 0.3:
-            w = "\u2581" + w[:15]
-        elif r < 0.4:
-            k = int(rng.integers(0, len(w)))
-            w = (w[:k] + "<0x0A>" + w[k:])[:16]
-        vocab.add(w)
-    vocab = sorted(vocab)
-    t2i = {t: i for i, t in enumerate(vocab)}
-    texts = []
-    for k in range(2500):
-        n = int(rng.integers(1, 700))
-        ch = rng.choice(list(letters) + [" "] * 2 + ["\n"] * (1 if k % 3 else 0), size=n)
-        texts.append("".join(ch))
-    texts += ["\n" + "etao" * 50, " " + "e" * 300, "\n\n\n", "e\ne\ne", " \nabc"]
-    text, offs = pack_strings(texts)
+    t2i, text, offs = raw_corpora.walker_case(seed)
     got = Encoder(Vocab(t2i, 0)).encode_csr(text, offs)
     ref = oracle.OracleVocab(t2i).encode_csr(text, offs)
     _cmp_csr(got, ref)
@@ -657,12 +614,7 @@ def test_dp_host_without_far_list_reports_status_3():
 
 def _long_word_texts():
     """test_long_words_big_window's inputs: words of 255..20000 bytes (the 2048-byte and unbounded passes)."""
-    rng = np.random.default_rng(5)
-    texts = []
-    for L in (255, 256, 257, 300, 700, 1500, 2047, 2048, 2049, 3000, 5000, 20000):
-        w = "".join(chr(c) for c in rng.integers(0x21, 0x7F, size=L))
-        texts += [w, "ab cd " + w + " ef", w + " " + w[: L // 2], ("\n" + w[:L // 3] + " x\n").join([w[:100], w[100:]])]
-    return texts
+    return raw_corpora.long_word_texts()
 
 
 @pytest.mark.parametrize("bias", [0x80000000 + 12345, (3 << 32) | 0xFFFFF000])
@@ -743,15 +695,7 @@ def test_work_partitions_vs_oracle(n, engines, oracles):
     4 strings, a used-up mask): batch sizes at and around the partition-count steps, ragged strings
     (uneven work, so waves leave their first partition), three calls on one ctx (the counters and
     the mask are reset by the finish kernel's last block) -- every string exactly once, vs the oracle."""
-    from dptok import synth
-    rng = np.random.default_rng(n)
-    text, offs = synth.random_ascii_corpus(n, 64, seed=n)
-    cut = rng.integers(0, 65, size=n)
-    cut[rng.random(n) < 0.02] = 0
-    parts = [text[i * 64:i * 64 + int(cut[i])].tobytes() for i in range(n)]
-    offs = np.zeros(n + 1, np.uint64)
-    offs[1:] = np.cumsum([len(p) for p in parts])
-    text = np.frombuffer(b"".join(parts) + b"\0", np.uint8)
+    text, offs = raw_corpora.work_partition_corpus(n)
     ref = oracles["llama32k"].encode_csr(text, offs)
     for _ in range(3):
         _cmp_csr(engines["llama32k"].encode_csr(text, offs), ref)
@@ -875,39 +819,18 @@ def test_mid_pass_words_257_to_512_bytes(engines, oracles):
     does not fit the first pass's 256-byte window: words of 200..530 bytes (its lane-mode B has chunks of up to 33
     boundaries), mixed with short ones, with and without '▁' markers, in PRESPLIT and ATOMS mode -- against the
     oracle; words over 512 bytes go on to the 2048-byte pass."""
-    from dptok.engine import pack_word_atoms
     from oracle import oracle
-    rng = np.random.default_rng(41)
-    alpha = [chr(c) for c in range(0x21, 0x7F)]
-    strings = []
-    for k in range(600):
-        words = []
-        for _ in range(int(rng.integers(1, 4))):
-            L = int(rng.integers(200, 531)) if rng.random() < 0.6 else int(rng.integers(1, 40))
-            w = "".join(rng.choice(alpha, size=L))
-            words.append(("▁" + w) if (words and k % 2) else w)
-        strings.append(words)
+    strings = raw_corpora.mid_pass_strings()
     enc, ov = engines["llama32k"], oracles["llama32k"]
     # PRESPLIT: words as UTF-8 text + a word-start mask
-    parts, cuts = [], []
-    for words in strings:
-        b = bytearray(); c = bytearray()
-        for w in words:
-            e = w.encode("utf-8")
-            c += b"\x01" + b"\x00" * (len(e) - 1)
-            b += e
-        parts.append(bytes(b)); cuts.append(bytes(c))
-    offs = np.zeros(len(parts) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint64)
-    text = np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
-    cut = np.frombuffer(b"".join(cuts), dtype=np.uint8).copy()
+    text, offs, cut = raw_corpora.mid_pass_presplit(strings)
     got = enc.encode_csr(text, offs, mode="presplit", cut_mask=cut)
     ref = ov.encode_csr(text, offs, mode=oracle.PRESPLIT, cut_mask=cut)
     _cmp_csr(got, ref)
     assert np.array_equal(got[3], ref[3])
     assert (got[2] == 0).sum() > 500
     # ATOMS: the same words, every code point an atom
-    t2, o2, c2 = pack_word_atoms([[list(w) for w in words] for words in strings])
+    t2, o2, c2 = raw_corpora.mid_pass_atoms(strings)
     got = enc.encode_csr(t2, o2, mode="atoms", cut_mask=c2)
     ref = ov.encode_csr(t2, o2, mode=oracle.ATOMS, cut_mask=c2)
     _cmp_csr(got, ref)
