@@ -566,6 +566,41 @@ int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts,
     return DPT_OK;
 }
 
+int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint64_t n_str, const dpt_collate_pair_opts *opts,
+                     void *input_ids, void *attention_mask, void *labels, void *token_type_ids, uint32_t *lengths,
+                     uint32_t *b_start, void *hip_stream) {
+    if (!a) return fail(DPT_E_ARG, "null a");
+    if (!b) return fail(DPT_E_ARG, "null b");
+    if (!a->ids) return fail(DPT_E_ARG, "null a->ids");
+    if (!a->off) return fail(DPT_E_ARG, "null a->off");
+    if (!b->ids) return fail(DPT_E_ARG, "null b->ids");
+    if (!b->off) return fail(DPT_E_ARG, "null b->off");
+    if (!opts) return fail(DPT_E_ARG, "null opts");
+    if (!input_ids) return fail(DPT_E_ARG, "null input_ids");
+    const uint32_t known = DPT_COLLATE_BOS | DPT_COLLATE_EOS | DPT_COLLATE_PAD_LEFT | DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64 |
+                           DPT_COLLATE_SEP | DPT_COLLATE_MASK_A | DPT_COLLATE_TRIM_A_FIRST;
+    if (opts->flags & ~known) return fail(DPT_E_ARG, "unknown bits in opts->flags");
+    const uint32_t n_special = ((opts->flags & DPT_COLLATE_BOS) ? 1u : 0u) + ((opts->flags & DPT_COLLATE_SEP) ? 1u : 0u) +
+                               ((opts->flags & DPT_COLLATE_EOS) ? 1u : 0u);
+    if (opts->row_len == 0) return fail(DPT_E_ARG, "opts->row_len is 0");
+    if (opts->row_len < n_special) return fail(DPT_E_ARG, "opts->row_len holds fewer elements than the BOS / SEP / EOS asked for");
+    if (opts->row_len > (1u << 31)) return fail(DPT_E_ARG, "opts->row_len over 2^31");
+    if (opts->row_stride && opts->row_stride < opts->row_len) return fail(DPT_E_ARG, "opts->row_stride under row_len");
+    if (n_str == 0) return DPT_OK;
+    dpt::CollatePairLaunch p{};
+    p.a = {a->ids, a->off, a->counts, a->status};
+    p.b = {b->ids, b->off, b->counts, b->status};
+    p.n_str = n_str;
+    p.row_len = opts->row_len; p.row_stride = opts->row_stride ? opts->row_stride : opts->row_len;
+    p.pad_id = opts->pad_id; p.bos_id = opts->bos_id; p.sep_id = opts->sep_id; p.eos_id = opts->eos_id; p.ignore_id = opts->ignore_id;
+    p.max_a = opts->max_a; p.max_b = opts->max_b; p.flags = opts->flags;
+    p.input_ids = input_ids; p.mask = attention_mask; p.labels = labels; p.token_type = token_type_ids;
+    p.lengths = lengths; p.b_start = b_start;
+    const hipError_t e = dpt::launch_collate_pair(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "collate pair launch");
+    return DPT_OK;
+}
+
 int dpt_ctx_set_histogram_ex(dpt_ctx *c, int64_t *hist, uint32_t n_bins, int flags) {
     if (!c) return fail(DPT_E_ARG, "null ctx");
     if (hist && (n_bins < 2 || n_bins > DPT_HIST_MAX_BINS)) return fail(DPT_E_ARG, "n_bins outside 2..DPT_HIST_MAX_BINS");

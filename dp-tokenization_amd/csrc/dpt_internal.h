@@ -338,6 +338,31 @@ struct CollateLaunch {
 };
 hipError_t launch_collate(const CollateLaunch &p, hipStream_t stream);
 
+// One launch of the pair collate kernel (dpt_collate.hip; include/dpt.h dpt_collate_pair): rows of two segments, each
+// side described as CollateLaunch's first four members; the options already checked.
+struct CollateSide {
+    const int32_t *ids;
+    const uint64_t *off;       // n_str + 1
+    const uint64_t *counts;    // nullable: the token counts come from off
+    const int32_t *status;     // nullable: all 0
+};
+struct CollatePairLaunch {
+    CollateSide a, b;
+    uint64_t n_str;
+    uint32_t row_len;
+    uint64_t row_stride;       // elements, >= row_len
+    int32_t pad_id, bos_id, sep_id, eos_id, ignore_id;
+    uint32_t max_a, max_b;     // per-side caps, 0: none
+    uint32_t flags;            // DPT_COLLATE_*
+    void *input_ids;           // int32, or int64 with DPT_COLLATE_I64 (and the next three)
+    void *mask;                // nullable
+    void *labels;              // nullable
+    void *token_type;          // nullable
+    uint32_t *lengths;         // nullable
+    uint32_t *b_start;         // nullable
+};
+hipError_t launch_collate_pair(const CollatePairLaunch &p, hipStream_t stream);
+
 // Pre-tokenization table of a vocabulary (dpt_pretok.cpp build_pretok_tables; include/dpt.h dpt_pretok_create), as
 // host bytes exactly as dpt_pretok_create uploads them.
 constexpr uint32_t PRETOK_BMP_WORDS = 2048;   // the known set below U+10000, one bit per code point

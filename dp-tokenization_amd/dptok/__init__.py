@@ -6,7 +6,8 @@ Public surface:
     Pretok                  llama mode's pre-split text made on the device (pretok.py)
     ByteLevelSplit          the BLOOM adapter's ATOMS input made on the device (bytelevel.py)
     collate                 padded model inputs from an encoded batch, on the device (collate.py: the
-                            ``collate_device`` / ``model_inputs`` calls; imported on demand, it needs torch)
+                            ``collate_device`` / ``model_inputs`` calls and their source + target forms
+                            ``collate_pair_device`` / ``pair_model_inputs``; imported on demand, it needs torch)
     pack_strings, TokenSpans  host arrays in and out of the engine (pack.py, pure numpy)
     dp_tokenize_batch       List[str] -> List[List[int]] for a t2i vocabulary
     synth                   synthetic vocabularies/corpora of the BASELINE configs

@@ -48,6 +48,21 @@ class CollateOpts(ctypes.Structure):
 
 
 COLLATE_BOS, COLLATE_EOS, COLLATE_PAD_LEFT, COLLATE_TRUNC_LEFT, COLLATE_I64 = 1, 2, 4, 8, 16
+COLLATE_SEP, COLLATE_MASK_A, COLLATE_TRIM_A_FIRST = 32, 64, 128   # dpt_collate_pair only
+
+
+class CollateSide(ctypes.Structure):
+    """dpt_collate_side: device addresses (0 = NULL)"""
+    _fields_ = [("ids", ctypes.c_void_p), ("off", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+class CollatePairOpts(ctypes.Structure):
+    """dpt_collate_pair_opts"""
+    _fields_ = [("row_len", ctypes.c_uint32), ("row_stride", ctypes.c_uint64), ("pad_id", ctypes.c_int32),
+                ("bos_id", ctypes.c_int32), ("sep_id", ctypes.c_int32), ("eos_id", ctypes.c_int32),
+                ("ignore_id", ctypes.c_int32), ("max_a", ctypes.c_uint32), ("max_b", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
 
 _lib = None
 P = ctypes.c_void_p
@@ -105,6 +120,8 @@ CALLS = {
     "dpt_debug_detok_table": (I32, [P, P, P, U32, I32, P, U32, I32, P, U64, PU64]),
     # model-input batches
     "dpt_collate": (I32, [P, P, P, P, U64, ctypes.POINTER(CollateOpts), P, P, P, P, P]),
+    "dpt_collate_pair": (I32, [ctypes.POINTER(CollateSide), ctypes.POINTER(CollateSide), U64, ctypes.POINTER(CollatePairOpts),
+                               P, P, P, P, P, P, P]),
     # llama-mode pre-tokenization on the device
     "dpt_pretok_create": (I32, [P, P, U32, P, U32, P, P, U32, I32, PP]),
     "dpt_pretok_destroy": (I32, [P]),
@@ -126,9 +143,10 @@ EXPORTED = sorted(CALLS)
 # the decode calls: name -> argument types
 DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and name != "dpt_debug_host_layout"}
 # Also within ABI 6 and probed for like OPTIONAL's (a set of its own: OPTIONAL less the layout call is, by
-# tests/test_pack.py, exactly the decode calls); ``collate.collate_device`` raises without it (has_collate).
+# tests/test_pack.py, exactly the decode calls); ``collate.collate_device`` raises without it (has_collate),
+# ``collate.collate_pair_device`` without dpt_collate_pair (has_collate_pair).
 # dpt_debug_wave_grid is test-only: ``wave_grid`` below raises without it.
-OPTIONAL_LATER = {"dpt_collate", "dpt_debug_wave_grid"}
+OPTIONAL_LATER = {"dpt_collate", "dpt_collate_pair", "dpt_debug_wave_grid"}
 # Likewise the pre-tokenization calls: name -> argument types; ``pretok.Pretok`` raises without them (has_pretok).
 PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name}
 OPTIONAL_PRETOK = set(PRETOK_CALLS)
@@ -171,6 +189,11 @@ def has_decode() -> bool:
 def has_collate() -> bool:
     """The loaded library exports dpt_collate."""
     return hasattr(lib(), "dpt_collate")
+
+
+def has_collate_pair() -> bool:
+    """The loaded library exports dpt_collate_pair."""
+    return hasattr(lib(), "dpt_collate_pair")
 
 
 def has_pretok() -> bool:

@@ -2,15 +2,19 @@
 ``input_ids`` / ``attention_mask`` / ``labels`` rows -- what the reference's ``llama_preprocessing_function``
 (main_analyze_s2orc.py:61-93) and the Trainer's collator produce on the host.
 
-``collate_device`` is the raw call over device addresses; ``model_inputs`` the same over torch tensors."""
+``collate_device`` is the raw call over device addresses; ``model_inputs`` the same over torch tensors.
+
+``collate_pair_device`` / ``pair_model_inputs`` are the two-segment form (dpt_collate_pair): each row is a source
+followed by a target -- what the reference's translation driver builds with ``apply_tokenizer`` and
+``ShortcutDataCollatorForSeq2Seq`` (main_biomed_translation.py:138-145, :104-124)."""
 from __future__ import annotations
 
 import ctypes
 from typing import Dict, Optional
 
 from . import _lib
-from ._lib import (COLLATE_BOS, COLLATE_EOS, COLLATE_I64, COLLATE_PAD_LEFT, COLLATE_TRUNC_LEFT, CollateOpts, DptError,
-                   check)
+from ._lib import (COLLATE_BOS, COLLATE_EOS, COLLATE_I64, COLLATE_MASK_A, COLLATE_PAD_LEFT, COLLATE_SEP, COLLATE_TRIM_A_FIRST,
+                   COLLATE_TRUNC_LEFT, CollateOpts, CollatePairOpts, CollateSide, DptError, check)
 
 
 def collate_flags(bos_id=None, eos_id=None, pad_left=False, trunc_left=False, int64=True) -> int:
@@ -99,4 +103,122 @@ def model_inputs(ids, off, status=None, counts=None, *, padding: str = "longest"
                        pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, ignore_id=ignore_id,
                        pad_left=padding_side == "left", trunc_left=truncation_side == "left", int64=int64,
                        stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def collate_pair_flags(bos_id=None, sep_id=None, eos_id=None, pad_left=False, trunc_left=False, int64=True, mask_a=False,
+                       trim_a_first=False) -> int:
+    return (collate_flags(bos_id, eos_id, pad_left, trunc_left, int64) | (COLLATE_SEP if sep_id is not None else 0)
+            | (COLLATE_MASK_A if mask_a else 0) | (COLLATE_TRIM_A_FIRST if trim_a_first else 0))
+
+
+def collate_pair_device(a, b, n_str: int, input_ids_ptr: int, row_len: int, *, mask_ptr: int = 0, labels_ptr: int = 0,
+                        token_type_ptr: int = 0, lengths_ptr: int = 0, b_start_ptr: int = 0, row_stride: int = 0,
+                        pad_id: int = 0, bos_id: Optional[int] = None, sep_id: Optional[int] = None,
+                        eos_id: Optional[int] = None, ignore_id: int = -100, max_a: int = 0, max_b: int = 0,
+                        pad_left: bool = False, trunc_left: bool = False, int64: bool = True, mask_a: bool = False,
+                        trim_a_first: bool = False, stream: int = 0) -> None:
+    """dpt_collate_pair over device addresses (0 = NULL): stream-ordered, no sync.  ``a`` / ``b``: each side as
+    ``(ids_ptr, off_ptr, counts_ptr, status_ptr)`` -- ``counts_ptr`` 0: ``off`` is dpt_encode's id_off, else
+    dpt_encode_padded's str_off and counts; ``status_ptr`` 0: all 0.  ``bos_id`` / ``sep_id`` / ``eos_id`` None: no such
+    special.  Rows are int64, or int32 with ``int64=False``; ``lengths`` and ``b_start`` are uint32."""
+    if not _lib.has_collate_pair():
+        raise DptError("this libdpt.so has no dpt_collate_pair")
+    sides = [CollateSide(*(int(x) or None for x in side)) for side in (a, b)]
+    opts = CollatePairOpts(row_len, row_stride, pad_id, bos_id or 0, sep_id or 0, eos_id or 0, ignore_id, max_a, max_b,
+                           collate_pair_flags(bos_id, sep_id, eos_id, pad_left, trunc_left, int64, mask_a, trim_a_first))
+    check(_lib.lib().dpt_collate_pair(ctypes.byref(sides[0]), ctypes.byref(sides[1]), n_str, ctypes.byref(opts), input_ids_ptr,
+                                      mask_ptr, labels_ptr, token_type_ptr, lengths_ptr, b_start_ptr, stream),
+          "dpt_collate_pair")
+
+
+def _check_side(torch, side, name):
+    """One side of ``pair_model_inputs`` as (ids, off, status, counts), validated like ``model_inputs``' arguments."""
+    ids, off, status, counts = (tuple(side) + (None, None))[:4]
+    for t in (ids, off, status, counts):
+        if t is not None and (not t.is_contiguous() or t.device != ids.device):
+            raise ValueError("%s: ids, off, status and counts must be contiguous tensors on one device" % name)
+    if ids.dtype != torch.int32 or off.element_size() != 8 or (counts is not None and counts.element_size() != 8) \
+            or (status is not None and status.dtype != torch.int32):
+        raise ValueError("%s: ids / status must be int32, off / counts 8-byte integers" % name)
+    return ids, off, status, counts
+
+
+def pair_model_inputs(a, b, *, padding: str = "longest", max_length: Optional[int] = None,
+                      pad_to_multiple_of: Optional[int] = None, max_source: Optional[int] = None,
+                      max_target: Optional[int] = None, labels: bool = False, mask_source: bool = False,
+                      token_type_ids: bool = False, trim: str = "target", pad_id: int = 0, bos_id: Optional[int] = None,
+                      sep_id: Optional[int] = None, eos_id: Optional[int] = None, ignore_id: int = -100,
+                      padding_side: str = "right", truncation_side: str = "right", int64: bool = True) -> Dict[str, object]:
+    """Two encoded batches of the same n_str strings -> ``{"input_ids", "attention_mask", "lengths", "b_start"[,
+    "labels"][, "token_type_ids"]}``: row s is ``[bos] + a's string s + [sep] + b's string s + [eos]``, filled on torch's
+    current stream by one dpt_collate_pair launch (include/dpt.h has the rule).
+
+    Each side is ``(ids, off[, status[, counts]])`` as ``model_inputs`` takes them, in either layout independently (the
+    two may be views of one encode's buffers).  ``max_source`` / ``max_target`` cap a side's tokens; a row longer than the
+    row length loses tokens of ``trim`` ("target" or "source") first.  ``mask_source``: the labels are ``ignore_id`` on
+    the bos, the source and the sep.  ``padding="longest"``: the row length is the longest capped pair plus the
+    specials, read back from the counts or offsets (that one scalar is the only synchronisation), capped by
+    ``max_length``; ``"max_length"`` synchronises nothing.  ``b_start`` (int32 per row) is the column of the target's
+    first position."""
+    import torch
+    if padding not in ("longest", "max_length"):
+        raise ValueError("padding must be 'longest' or 'max_length'")
+    if padding_side not in ("left", "right") or truncation_side not in ("left", "right"):
+        raise ValueError("padding_side / truncation_side must be 'left' or 'right'")
+    if trim not in ("target", "source"):
+        raise ValueError("trim must be 'target' or 'source'")
+    sides = [_check_side(torch, a, "a"), _check_side(torch, b, "b")]
+    n_str = sides[0][1].numel() - 1
+    if n_str < 0 or sides[1][1].numel() - 1 != n_str:
+        raise ValueError("both off tensors need the same n_str + 1 entries")
+    dev = sides[0][0].device
+    if sides[1][0].device != dev:
+        raise ValueError("both sides must be on one device")
+    for _, _, status, counts in sides:
+        if (status is not None and status.numel() < n_str) or (counts is not None and counts.numel() < n_str):
+            raise ValueError("status / counts need n_str entries")
+    caps = [int(max_source or 0), int(max_target or 0)]
+    n_special = (bos_id is not None) + (sep_id is not None) + (eos_id is not None)
+    if padding == "max_length":
+        if max_length is None:
+            raise ValueError("padding='max_length' needs max_length")
+        row_len = int(max_length)
+    else:
+        row_len = 0
+        if n_str:
+            total = 0
+            for (_, off, status, counts), cap in zip(sides, caps):
+                n = counts.view(torch.int64)[:n_str] if counts is not None else off.view(torch.int64).diff()
+                if status is not None:   # a failed row is all pad
+                    n = n.masked_fill(status[:n_str] != 0, -(1 << 40))
+                total = total + (n.clamp(max=cap) if cap else n)
+            row_len = max(int(total.max()), 0) + n_special
+        if max_length is not None:
+            row_len = min(row_len, int(max_length))
+    row_len = max(row_len, n_special, 1)
+    if pad_to_multiple_of:
+        row_len = -(-row_len // pad_to_multiple_of) * pad_to_multiple_of
+    dtype = torch.int64 if int64 else torch.int32
+    rows = ["input_ids", "attention_mask"] + (["labels"] if labels else []) + (["token_type_ids"] if token_type_ids else [])
+    out = {k: torch.empty((n_str, row_len), dtype=dtype, device=dev) for k in rows}
+    out["lengths"] = torch.empty(n_str, dtype=torch.int32, device=dev)
+    out["b_start"] = torch.empty(n_str, dtype=torch.int32, device=dev)
+    if n_str == 0:
+        return out
+    ptrs = []
+    for ids, off, status, counts in sides:
+        if ids.numel() == 0:   # (an empty tensor has no address; no id is read)
+            ids = torch.zeros(1, dtype=torch.int32, device=dev)
+        ptrs.append((ids, (ids.data_ptr(), off.data_ptr(), counts.data_ptr() if counts is not None else 0,
+                           status.data_ptr() if status is not None else 0)))
+    with torch.cuda.device(dev):
+        collate_pair_device(ptrs[0][1], ptrs[1][1], n_str, out["input_ids"].data_ptr(), row_len,
+                            mask_ptr=out["attention_mask"].data_ptr(), labels_ptr=out["labels"].data_ptr() if labels else 0,
+                            token_type_ptr=out["token_type_ids"].data_ptr() if token_type_ids else 0,
+                            lengths_ptr=out["lengths"].data_ptr(), b_start_ptr=out["b_start"].data_ptr(), pad_id=pad_id,
+                            bos_id=bos_id, sep_id=sep_id, eos_id=eos_id, ignore_id=ignore_id, max_a=caps[0], max_b=caps[1],
+                            pad_left=padding_side == "left", trunc_left=truncation_side == "left", int64=int64,
+                            mask_a=mask_source, trim_a_first=trim == "source",
+                            stream=torch.cuda.current_stream(dev).cuda_stream)
     return out

@@ -34,6 +34,9 @@ MI355X engine.  Same names, argument meaning and error behaviour:
 * ``dp_tokenize.batch_model_inputs(List[str], ...) -> dict``: the batch as padded ``input_ids`` /
   ``attention_mask`` / ``labels`` / ``lengths`` tensors on the GPU (dpt_encode_padded + dpt_collate; what
   reference main_analyze_s2orc.py:61-93 and the collator build on the host); see its docstring.
+* ``dp_tokenize.batch_pair_model_inputs(sources, targets, ...) -> dict``: source + target rows as padded
+  ``input_ids`` / ``attention_mask`` / ``labels`` tensors on the GPU (one dpt_encode_padded + one dpt_collate_pair;
+  what reference main_biomed_translation.py:138-145 and its collator, :104-124, build on the host); see its docstring.
 * ``decode_dp_tokenization.batch(List[List[int]]) -> List[str]`` and ``dp_tokenize.batch_roundtrip(List[str])
   -> List[Optional[int]]``: the tokenizer's own decode of a batch, and the caller's round-trip assert
   (reference main_analyze_s2orc.py:84-87), each in one GPU launch; ``decode_dp_tokenization`` itself stays
@@ -261,6 +264,24 @@ around the kept ids (in llama mode the BOS piece ``tokenizer.encode`` adds is al
 failed string's row is all pad with mask 0 and length 0, and ``status`` (int32 per string) is returned too."""
 
 
+_PAIR_INPUTS_DOC = """``dp_tokenize.batch_pair_model_inputs(sources, targets, max_length=None, padding="longest",
+pad_to_multiple_of=None, max_source=None, max_target=None, add_bos=False, sep_id=None, add_eos=False, labels=True,
+mask_source=False, token_type_ids=False, trim="target", ignore_id=None, padding_side="right", truncation_side="right",
+errors="raise") -> dict``: source + target rows as model inputs on the GPU -- what the reference's translation driver
+builds with apply_tokenizer (main_biomed_translation.py:138-145) and ShortcutDataCollatorForSeq2Seq (:104-124).
+``sources + targets`` go up as one packed batch, one dpt_encode_padded and one dpt_collate_pair run back to back (the
+targets are the same buffers from string ``len(sources)`` on), and nothing comes back but the statuses (and, for
+``padding="longest"``, the row length).  Row i is ``[bos] + source i + [sep] + target i + [eos]``; the defaults are the
+reference collator's tensors: no specials, right padding to the longest pair, int64, ``labels`` equal to the padded
+``input_ids`` (``ignore_id`` None: the pad id).  ``max_source`` / ``max_target`` cap a side's ids; a row longer than
+``max_length`` loses ids of ``trim`` ("target" or "source") first.  ``mask_source``: the labels are ``ignore_id`` on the
+source (pass e.g. ``ignore_id=-100``); ``token_type_ids``: 0 on the source, 1 on the target.  Also returned: ``lengths``
+and ``b_start`` (the column of the target's first position), int32 per row.  ``errors="raise"``: what
+``dp_tokenize.batch`` raises, for the first failed string in row order, a row's source before its target; ``"mask"``:
+a row with a failed side is all pad, and ``status_source`` / ``status_target`` (int32 per row) are returned too.
+ValueError when the two lists differ in length."""
+
+
 def _special_ids(tokenizer):
     """(bos, eos, pad) ids of a tokenizer object: bos / eos None when it has none; pad is its ``pad_token_id``,
     else its ``eos_token_id``, else 0."""
@@ -271,19 +292,14 @@ def _special_ids(tokenizer):
 
 
 def _model_inputs_surface(engine, tokenizer, pack_batch):
-    """``batch_model_inputs`` over one adapter's packing: ``pack_batch(texts) -> (text, offs, mode, cut, none,
+    """(``batch_model_inputs``, ``batch_pair_model_inputs``) over one adapter's packing: ``pack_batch(texts) -> (text, offs, mode, cut, none,
     outcome)``, the buffers of its ``batch`` call with ``none`` / ``outcome`` as ``_batch_spans`` takes them."""
 
-    def batch_model_inputs(texts, max_length=None, padding="longest", pad_to_multiple_of=None, add_bos=False,
-                           add_eos=False, padding_side="right", truncation_side="right", labels=False, errors="raise"):
+    def encode_padded(texts):
+        """One dpt_encode_padded over the adapter's packing of ``texts`` -> (dev, ids, d_offs, st, counts, offs): the
+        device tensors ``model_inputs`` takes (st and counts of len(texts) entries, the statuses fixed up as ``batch``
+        sees them) and the host offsets."""
         import torch
-        from dptok.collate import model_inputs
-        if errors not in ("raise", "mask"):
-            raise ValueError("errors must be 'raise' or 'mask'")
-        texts = list(texts)
-        bos, eos, pad = _special_ids(tokenizer)
-        if (add_bos and bos is None) or (add_eos and eos is None):
-            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
         text, offs, mode, cut, none, outcome = pack_batch(texts)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         n, b0 = len(offs) - 1, int(offs[0])
@@ -314,7 +330,21 @@ def _model_inputs_surface(engine, tokenizer, pack_batch):
                 d_none = torch.from_numpy(np.ascontiguousarray(none, dtype=bool)).to(dev)
                 st = st.masked_fill(d_none, _dpt.STATUS_OK)
                 counts = counts[:n].masked_fill(d_none, 0)
-            out = model_inputs(ids, d_offs, st, counts[:n].contiguous(), padding=padding, max_length=max_length,
+        return dev, ids, d_offs, st, counts[:n].contiguous(), offs
+
+    def batch_model_inputs(texts, max_length=None, padding="longest", pad_to_multiple_of=None, add_bos=False,
+                           add_eos=False, padding_side="right", truncation_side="right", labels=False, errors="raise"):
+        import torch
+        from dptok.collate import model_inputs
+        if errors not in ("raise", "mask"):
+            raise ValueError("errors must be 'raise' or 'mask'")
+        texts = list(texts)
+        bos, eos, pad = _special_ids(tokenizer)
+        if (add_bos and bos is None) or (add_eos and eos is None):
+            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
+        dev, ids, d_offs, st, counts, _ = encode_padded(texts)
+        with torch.cuda.device(dev):
+            out = model_inputs(ids, d_offs, st, counts, padding=padding, max_length=max_length,
                                pad_to_multiple_of=pad_to_multiple_of, labels=labels, pad_id=pad,
                                bos_id=bos if add_bos else None, eos_id=eos if add_eos else None,
                                padding_side=padding_side, truncation_side=truncation_side)
@@ -325,11 +355,47 @@ def _model_inputs_surface(engine, tokenizer, pack_batch):
                 raise_for_status(int(st[i]), texts[i])
         return out
 
+    def batch_pair_model_inputs(sources, targets, max_length=None, padding="longest", pad_to_multiple_of=None,
+                                max_source=None, max_target=None, add_bos=False, sep_id=None, add_eos=False, labels=True,
+                                mask_source=False, token_type_ids=False, trim="target", ignore_id=None,
+                                padding_side="right", truncation_side="right", errors="raise"):
+        import torch
+        from dptok.collate import pair_model_inputs
+        if errors not in ("raise", "mask"):
+            raise ValueError("errors must be 'raise' or 'mask'")
+        sources, targets = list(sources), list(targets)
+        if len(sources) != len(targets):
+            raise ValueError("%d sources for %d targets" % (len(sources), len(targets)))
+        bos, eos, pad = _special_ids(tokenizer)
+        if (add_bos and bos is None) or (add_eos and eos is None):
+            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
+        n = len(sources)
+        dev, ids, d_offs, st, counts, offs = encode_padded(sources + targets)
+        first_b = int(offs[n] - offs[0])   # side B: the same buffers from string n on (its ids start at str_off[n])
+        with torch.cuda.device(dev):
+            out = pair_model_inputs((ids, d_offs[:n + 1], st[:n], counts[:n]), (ids[first_b:], d_offs[n:], st[n:], counts[n:]),
+                                    padding=padding, max_length=max_length, pad_to_multiple_of=pad_to_multiple_of,
+                                    max_source=max_source, max_target=max_target, labels=labels, mask_source=mask_source,
+                                    token_type_ids=token_type_ids, trim=trim, pad_id=pad, bos_id=bos if add_bos else None,
+                                    sep_id=sep_id, eos_id=eos if add_eos else None,
+                                    ignore_id=pad if ignore_id is None else ignore_id, padding_side=padding_side,
+                                    truncation_side=truncation_side)
+            if errors == "mask":
+                out["status_source"], out["status_target"] = st[:n], st[n:]
+                return out
+            st_h = st.cpu().numpy()
+            for i in np.flatnonzero(st_h[:n] | st_h[n:]).tolist()[:1]:   # sources before targets of the same row
+                if st_h[i]:
+                    raise_for_status(int(st_h[i]), sources[i])
+                raise_for_status(int(st_h[n + i]), targets[i])
+        return out
+
     batch_model_inputs.__doc__ = _MODEL_INPUTS_DOC
-    return batch_model_inputs
+    batch_pair_model_inputs.__doc__ = _PAIR_INPUTS_DOC
+    return batch_model_inputs, batch_pair_model_inputs
 
 
-def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, inputs_many, decode_batch,
+def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, inputs_surface, decode_batch,
                     batch_roundtrip, whose, **extra):
     """Hang the batch calls, the engine and ``extra`` on the two closures of an adapter and return the pair;
     ``whose``: the decode that ``decode_batch`` is (for its docstring)."""
@@ -339,7 +405,7 @@ def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, sp
     dp_tokenize.batch_roundtrip = batch_roundtrip
     dp_tokenize.batch = encode_many
     dp_tokenize.batch_spans = spans_many
-    dp_tokenize.batch_model_inputs = inputs_many
+    dp_tokenize.batch_model_inputs, dp_tokenize.batch_pair_model_inputs = inputs_surface
     dp_tokenize.engine = engine
     for name, value in extra.items():
         setattr(dp_tokenize, name, value)

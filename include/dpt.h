@@ -29,6 +29,9 @@
  *                        :176-179, and the caller's round-trip assert, main_analyze_s2orc.py:84-87
  *   dpt_collate        <- llama_preprocessing_function's model inputs, reference main_analyze_s2orc.py:61-93
  *                        (input_ids, attention_mask = [1] * len(ids), truncation; the collator's padding)
+ *   dpt_collate_pair   <- the BLOOM translation driver's model inputs, reference main_biomed_translation.py:138-145
+ *                        (a source and a target per example) and :104-124 (the collator: source ids + target ids,
+ *                        right-padded, returned as input_ids and labels)
  *   dpt_hist_allreduce <- SURVEY.md §8(b)/(e): the one collective of a sharded corpus (the
  *                        reference is single-process, llama_s2orc.sh:10; no call site there)
  *
@@ -382,6 +385,71 @@ typedef struct {
 int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts, const int32_t *status,
                 uint64_t n_str, const dpt_collate_opts *opts, void *input_ids, void *attention_mask,
                 void *labels, uint32_t *lengths, void *hip_stream);
+
+/*
+ * Source + target model-input batches: rows of two segments -- what the reference's BLOOM translation driver
+ * feeds its model.  There apply_tokenizer (main_biomed_translation.py:138-145) tokenizes a source and a target per
+ * example, and ShortcutDataCollatorForSeq2Seq (:104-124) builds each row as the source ids followed by the target
+ * ids, right-pads the batch with the pad id and returns that tensor as both input_ids and labels.  Added within
+ * ABI 6 (DPT_ABI_VERSION unchanged): a binding that may meet an older libdpt.so probes for the symbol.
+ *
+ * Each side (a: the source, b: the target) is described like the first four arguments of the one-sequence call
+ * above, independently of the other: ids (int32), off (uint64, n_str + 1 entries, off[0] need not be 0 and ids
+ * corresponds to it), counts (nullable; NULL: off is an id_off and n = off[s+1] - off[s], else off is a str_off
+ * and n = counts[s]) and status (nullable: all 0).  Both sides may point into the buffers of one encode, e.g. the
+ * sources at strings [0, n) and the targets at [n, 2n) of one padded encode.  With L = row_len, n_special = the
+ * number of DPT_COLLATE_BOS / DPT_COLLATE_SEP / DPT_COLLATE_EOS set, room = L - n_special and nA, nB the two token
+ * counts, a row s whose statuses are both 0 gives
+ *   caps      cA = max_a ? min(nA, max_a) : nA, and cB from max_b likewise
+ *   overflow  over = max(0, cA + cB - room); B gives up tokens first: dB = min(over, cB), dA = over - dB; with
+ *             DPT_COLLATE_TRIM_A_FIRST A does: dA = min(over, cA), dB = over - dA
+ *   kept      kA = cA - dA, kB = cB - dB; a side keeps its first k tokens, or with DPT_COLLATE_TRUNC_LEFT the
+ *             last k of its n
+ *   seq  = [bos_id] + A_kept + [sep_id] + B_kept + [eos_id] (the specials survive truncation),
+ *   len  = kA + kB + n_special
+ *   input_ids, attention_mask: as in the one-sequence call (padding side, row_stride, element width, sign extension)
+ *   labels:           the row of input_ids with ignore_id at pad positions; with DPT_COLLATE_MASK_A ignore_id also
+ *                     on the bos, every A token and the sep (the loss is on B and the eos only)
+ *   token_type_ids:   0 on bos / A / sep and on pad, 1 on B and eos (same element type)
+ *   lengths[s] = len
+ *   b_start[s] = the row column of B's first position: start + bos + kA + sep, with start = L - len under
+ *                DPT_COLLATE_PAD_LEFT and 0 otherwise; written when kB = 0 too
+ * and a row where either status is non-zero is all pad_id, mask 0, labels ignore_id, type 0, lengths[s] = 0 and
+ * b_start[s] = 0, whatever its off ranges or counts hold: no id of it is read.  Ids pass through unvalidated.
+ * attention_mask, labels, token_type_ids, lengths and b_start are nullable.  Elements [row_len, row_stride) of a row
+ * and everything outside the n_str rows are never written.  Outputs must not overlap inputs and need their
+ * element's alignment only.
+ * DPT_E_ARG, before any device work (also with n_str == 0): null a, b, a->ids, a->off, b->ids, b->off, opts or
+ * input_ids; row_len 0, < n_special or > 2^31; row_stride non-zero and < row_len; unknown flags.  n_str == 0
+ * launches nothing.
+ * DEVICE pointers on the current device; stream-ordered on hip_stream, never synchronises, allocates nothing and
+ * needs no dpt_ctx and no vocabulary: any number of calls may be in flight.  No host-buffer form.  The
+ * reference's collator is the case without specials, right padding, ignore_id = pad_id (its labels are the
+ * padded input_ids themselves) and DPT_COLLATE_I64.
+ */
+typedef struct {            /* one side of the pair */
+    const int32_t *ids;
+    const uint64_t *off;
+    const uint64_t *counts; /* nullable */
+    const int32_t *status;  /* nullable */
+} dpt_collate_side;
+#define DPT_COLLATE_SEP 32          /* sep_id between the sides */
+#define DPT_COLLATE_MASK_A 64       /* labels = ignore_id on bos + A + sep */
+#define DPT_COLLATE_TRIM_A_FIRST 128
+typedef struct {
+    uint32_t row_len;      /* L: elements per row */
+    uint64_t row_stride;   /* elements between row starts (0: row_len) */
+    int32_t pad_id;
+    int32_t bos_id;        /* read with DPT_COLLATE_BOS */
+    int32_t sep_id;        /* read with DPT_COLLATE_SEP */
+    int32_t eos_id;        /* read with DPT_COLLATE_EOS */
+    int32_t ignore_id;
+    uint32_t max_a, max_b; /* per-side caps, 0 = none */
+    uint32_t flags;        /* DPT_COLLATE_* (BOS, EOS, PAD_LEFT, TRUNC_LEFT, I64 as above) */
+} dpt_collate_pair_opts;
+int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint64_t n_str,
+                     const dpt_collate_pair_opts *opts, void *input_ids, void *attention_mask, void *labels,
+                     void *token_type_ids, uint32_t *lengths, uint32_t *b_start, void *hip_stream);
 
 /*
  * Llama-mode pre-tokenization on the device: text in, DPT_MODE_PRESPLIT input (text + cut mask) out -- what the
