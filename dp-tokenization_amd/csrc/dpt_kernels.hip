@@ -1015,6 +1015,10 @@ struct TokPass {
     // PLAIN: the mode-constant instantiations serve only calls without edges, the uncapped DP or len_only
     // (launch_encode sends those to the runtime-mode kernels): their loop versions are compiled out
     static constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0 || LEAN == 1) && !SOLO;
+    // LITM: phase B records the edge masks as include/dpt.h words them (forward, below).  Not in the raw-mode first
+    // passes, which plan_encode never picks for a call with edges (their edge loop versions are never run, and stay
+    // as they were so that the kernels stay the same code)
+    static constexpr bool LITM = !(RAW && !SOLO && !BIG);
 
     // the wave's LDS: slot g's arrays at g * GSTR, then its SlotState (group_stride); its word list in global scratch
     static __device__ __forceinline__ unsigned char *lds() {
@@ -2551,6 +2555,7 @@ struct TokPass {
                         unsigned sk = d == 0 ? SK0 : 0u;
                         unsigned x = d == 0 ? rec32[0] : 0xFFFF0000u;
                         unsigned wsh = 0;                    // word start << 16
+                        [[maybe_unused]] unsigned tr = d == 0 ? 1u : 0u;      // edges, capm 0 / 1: a path of tokens reaches candidate j
                         uint32_t nx = rec32[1];
                         // one step; (sk, x) in, (sk', x') out -- called alternately on two register sets
                         // so the DPP shifts need no copies
@@ -2560,7 +2565,8 @@ struct TokPass {
                             const unsigned span = (cur - xI) & 0x7FFFu;  // cp(j..i); borrows only move up
                             unsigned kv = (skI | 0x7FFFu) - span;
                             kv = skI < kv ? skI : kv;
-                            const unsigned key = kv | (unsigned)__builtin_amdgcn_sbfe((int)cur, sbit, 1);
+                            const unsigned dead = (unsigned)__builtin_amdgcn_sbfe((int)cur, sbit, 1);
+                            const unsigned key = kv | dead;
                             unsigned r = row_min_u32(key);
                             if constexpr (capm == 0) {
                                 const unsigned capkey = ((i << 16) | 0xFFFFu) - wsh;
@@ -2568,6 +2574,17 @@ struct TokPass {
                             }
                             const uint64_t gmb = ballot(key == r);
                             const uint64_t emb = ballot((key ^ r) < 0x8000u);
+                            // The recorded mask (include/dpt.h): the starts a path of tokens reaches whose cost + 1
+                            // is cost[i].  emb is that only while r is a candidate's key on such a path: where the
+                            // cap or "inf" is all r holds it lists the unreachable starts (or every dead lane), and
+                            // it leaves out a reachable start whose capped cost no path attains.
+                            uint64_t smb = emb;
+                            [[maybe_unused]] unsigned trn = 0;
+                            if constexpr (edges && capm != 2 && LITM) {
+                                const bool live = dead == 0u && tr != 0u;
+                                smb = ballot(live && ((key ^ r) >> 16) == 0u);
+                                trn = ((unsigned)(ballot(live) >> (16u * mg)) & 0xFFFFu) != 0u ? 1u : 0u;
+                            }
                             if (d == 0) {
                                 const unsigned sh = 16u * mg;
                                 const unsigned gs = (unsigned)(gmb >> sh), es = (unsigned)(emb >> sh);
@@ -2577,9 +2594,13 @@ struct TokPass {
                                 L.fin[i].v = (uint8_t)(dg | (de << 4));
                                 L.rec[i].smask = Wfin<G>::pack(r);   // rec[i] was consumed at step i-1
                                 if constexpr (edges)
-                                    if (i <= na) a.edges[SSr(mg).sb + SSr(mg).abase + i - 1] = es & 0xFFFFu;
+                                    if (i <= na) {
+                                        if constexpr (LITM) a.edges[SSr(mg).sb + SSr(mg).abase + i - 1] = (unsigned)(smb >> sh) & 0xFFFFu;
+                                        else a.edges[SSr(mg).sb + SSr(mg).abase + i - 1] = es & 0xFFFFu;
+                                    }
                             }
                             const bool wend = (int16_t)cur < 0;     // CP_WS: word starts and the window end
+                            if constexpr (edges && capm != 2 && LITM) tr = row_shift_in(tr, wend ? 1u : trn);
                             wsh = wend ? (i << 16) : wsh;
                             unsigned nxt = r + 0x10000u;
                             if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;   // unreachable: cost stays inf
@@ -2596,6 +2617,7 @@ struct TokPass {
                     } else {
                         const uint64_t m0 = na > 0 ? L.rec[0].smask : 0ull;
                         unsigned mlo = d == 0 ? (unsigned)m0 : 0u, mhi = d == 0 ? (unsigned)(m0 >> 32) : 0u;
+                        [[maybe_unused]] unsigned tr = d == 0 ? 1u : 0u;      // edges, capm 0 / 1: a path of tokens reaches candidate j
                         for (unsigned i = 1; i <= imax; i++) {
                             const unsigned cur = L.rec[i].cpos;
                             const uint64_t mi = L.rec[i].smask;
@@ -2612,15 +2634,26 @@ struct TokPass {
                             }
                             const uint64_t gmb = ballot(key == r);
                             const uint64_t emb = ballot((key ^ r) < 0x8000u);
+                            uint64_t smb = emb;              // the recorded mask: see the 16-lane rows above
+                            [[maybe_unused]] unsigned trn = 0;
+                            if constexpr (edges && capm != 2 && LITM) {
+                                const bool live = bit != 0u && tr != 0u;
+                                smb = ballot(live && ((key ^ r) >> 16) == 0u);
+                                trn = ballot(live) != 0ull ? 1u : 0u;
+                            }
                             if (lane == 0) {
                                 const unsigned dg = gmb ? (unsigned)__builtin_ctzll(gmb) : 64u;
                                 const unsigned de = emb ? (unsigned)__builtin_ctzll(emb) : 64u;
                                 L.fin[i].d = dg | (de << 8);
                                 L.fin[i].w = Wfin<G>::pack(r);
                                 if constexpr (edges)
-                                    if (i <= na) a.edges[SSr(0).sb + SSr(0).abase + i - 1] = emb;
+                                    if (i <= na) {
+                                        if constexpr (LITM) a.edges[SSr(0).sb + SSr(0).abase + i - 1] = smb;
+                                        else a.edges[SSr(0).sb + SSr(0).abase + i - 1] = emb;
+                                    }
                             }
                             const bool wend = (cur & CP_WS) != 0;
+                            if constexpr (edges && capm != 2 && LITM) tr = wave_shift_in(tr, wend ? 1u : trn);
                             ws = wend ? i : ws;
                             unsigned nxt = (r ^ 0x7FFFu) + 0x10000u;
                             if constexpr (capm == 1) nxt = r >= 0xFFFE0000u ? 0xFFFF8000u : nxt;

@@ -315,6 +315,18 @@ __device__ __forceinline__ void long_body(const Args &a) {
             if (lane == 0) { mlo = S.rec[0].z; mhi = S.rec[0].w; }
             unsigned ws = 0;
             uint4 prev = S.rec[0];
+            // The recorded masks and far pairs (include/dpt.h) list the starts a path of tokens reaches whose cost + 1
+            // is cost[i].  Uncapped, an unreachable start is NONE and the key comparison is that already; capped (lit)
+            // the cap gives every start a cost, so reachability travels with the candidates: tr per lane, and for the
+            // far starts bit 30 of the stored state's low word (TRB: always set in a key, G and the spans are < 2^30).
+            const bool lit = a.edges != nullptr && !uncapped;
+            constexpr unsigned TRB = 0x40000000u;
+            unsigned tr = lane == 0 ? 1u : 0u;
+            auto far_state = [&](unsigned jj, bool &trj) -> uint64_t {
+                const uint4 rj = S.rec[jj];
+                trj = (rj.y & WS) != 0 || (rj.w & TRB) != 0;
+                return (rj.y & WS) ? SK0 : (((uint64_t)(uint32_t)S.stg[jj] << 32) | rj.w | TRB);
+            };
             for (unsigned i = 1; i <= na; i++) {
                 const uint4 cur = i < na ? S.rec[i] : make_uint4(S.slen, S.cp_tot | WS, 0u, 0u);
                 const unsigned cpi = cur.y & CPM;
@@ -329,6 +341,7 @@ __device__ __forceinline__ void long_body(const Args &a) {
                 // tokens of more than 64 atoms ending at i (rare): scan the far starts
                 uint64_t rl = NONE;
                 unsigned jgl = 0, jel = 0;
+                bool fartr = false;   // lit: a far token ending at i starts at a reachable atom
                 if (prev.y & LONG_END) {
                     phase_sync();   // the states of the far starts were stored by earlier steps
                     // a token of B bytes spans at most B atoms
@@ -337,15 +350,16 @@ __device__ __forceinline__ void long_body(const Args &a) {
                     for (unsigned jb = i - 65; i >= 65 + lo; jb -= 64) {
                         const unsigned jj = jb - lane;
                         uint64_t key = NONE;
+                        bool trj = false;
                         if (lane <= jb - lo && span_is_token(a, S, jj, i)) {
-                            const uint64_t st = (S.rec[jj].y & WS) ? SK0
-                                : (((uint64_t)(uint32_t)S.stg[jj] << 32) | S.rec[jj].w);
+                            const uint64_t st = far_state(jj, trj);
                             if (st != NONE) {
                                 const unsigned span = (cpi - (S.rec[jj].y & CPM)) & CPM;
                                 const uint64_t k2 = (st | 0x7FFFFFFFull) - span;
                                 key = st < k2 ? st : k2;
                             }
                         }
+                        if (lit) fartr |= ballot(key != NONE && trj) != 0ull;
                         const uint64_t rc = wave_min64(key);
                         if (rc != NONE) {
                             const uint64_t gm = ballot(key == rc), em = ballot(key != NONE && (key >> 31) == (rc >> 31));
@@ -372,45 +386,51 @@ __device__ __forceinline__ void long_body(const Args &a) {
                 if (emb) de = (unsigned)__builtin_ctzll(emb);
                 else if (rl != NONE && (rl >> 31) == (r >> 31)) de = i - 1 - jel;
                 const bool wend = (cur.y & WS) != 0;
+                uint64_t smb = emb;   // the recorded mask
+                bool tri = false;
+                if (lit) {
+                    const bool live = bit != 0u && sk != NONE && tr != 0u;
+                    smb = ballot(live && (kv >> 32) == (r >> 32));
+                    tri = ballot(live) != 0ull || fartr;
+                }
                 if (lane == 0) {
                     S.rec[i - 1].z = (dg & 0xFFFFu) | (de << 16);
-                    if (a.edges) a.edges[sb + i - 1] = emb;
+                    if (a.edges) a.edges[sb + i - 1] = smb;
                 }
-                if (a.edges && rl != NONE && (rl >> 31) == (r >> 31)) {
-                    // E(i) has starts more than 64 atoms back, which the 64-bit edge mask cannot
-                    // hold: list every one of them as an (end, back distance) pair (the far scan
-                    // again, against the final key), or report status 3 without a far list
-                    if (!a.far) {
-                        status = 3;
-                    } else {
-                        const unsigned lo = (i > a.max_tok_bytes && i - a.max_tok_bytes > ws) ? i - a.max_tok_bytes : ws;
-                        for (unsigned jb = i - 65; i >= 65 + lo; jb -= 64) {
-                            const unsigned jj = jb - lane;
-                            bool hit = false;
-                            if (lane <= jb - lo && span_is_token(a, S, jj, i)) {
-                                const uint64_t st = (S.rec[jj].y & WS) ? SK0
-                                    : (((uint64_t)(uint32_t)S.stg[jj] << 32) | S.rec[jj].w);
-                                if (st != NONE) {
-                                    const unsigned span = (cpi - (S.rec[jj].y & CPM)) & CPM;
-                                    const uint64_t k2 = (st | 0x7FFFFFFFull) - span;
-                                    hit = (((st < k2 ? st : k2) ^ r) >> 31) == 0;
-                                }
+                if (a.edges && (lit ? (prev.y & LONG_END) != 0 : (rl != NONE && (rl >> 31) == (r >> 31)))) {
+                    // Starts more than 64 atoms back, which the 64-bit edge mask cannot hold: list every one
+                    // that belongs to it as an (end, back distance) pair (the far scan again, against the
+                    // final key), or report status 3 without a far list
+                    const unsigned lo = (i > a.max_tok_bytes && i - a.max_tok_bytes > ws) ? i - a.max_tok_bytes : ws;
+                    for (unsigned jb = i - 65; i >= 65 + lo; jb -= 64) {
+                        const unsigned jj = jb - lane;
+                        bool hit = false;
+                        if (lane <= jb - lo && span_is_token(a, S, jj, i)) {
+                            bool trj = false;
+                            const uint64_t st = far_state(jj, trj);
+                            if (st != NONE) {
+                                const unsigned span = (cpi - (S.rec[jj].y & CPM)) & CPM;
+                                const uint64_t k2 = (st | 0x7FFFFFFFull) - span;
+                                const uint64_t k = st < k2 ? st : k2;
+                                hit = lit ? ((k >> 32) == (r >> 32) && trj) : (((k ^ r) >> 31) == 0);
                             }
-                            const uint64_t hm = ballot(hit);
-                            if (hm) {
-                                unsigned long long base = 0;
-                                if (lane == 0) base = atomicAdd(a.far_count, (unsigned long long)__builtin_popcountll(hm));
-                                // (each half through uint32_t: readfirstlane returns int, whose sign would extend)
-                                base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) << 32) |
-                                       (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)base);
-                                const uint64_t k = base + __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0u));
-                                if (hit && k < a.far_cap) {
-                                    a.far[2 * k] = sb + i - 1;
-                                    a.far[2 * k + 1] = i - 1 - jj;
-                                }
-                            }
-                            if (jb < lo + 64) break;
                         }
+                        const uint64_t hm = ballot(hit);
+                        if (hm && !a.far) {
+                            status = 3;
+                        } else if (hm) {
+                            unsigned long long base = 0;
+                            if (lane == 0) base = atomicAdd(a.far_count, (unsigned long long)__builtin_popcountll(hm));
+                            // (each half through uint32_t: readfirstlane returns int, whose sign would extend)
+                            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(base >> 32)) << 32) |
+                                   (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)base);
+                            const uint64_t k = base + __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0u));
+                            if (hit && k < a.far_cap) {
+                                a.far[2 * k] = sb + i - 1;
+                                a.far[2 * k + 1] = i - 1 - jj;
+                            }
+                        }
+                        if (jb < lo + 64) break;
                     }
                 }
                 // state of position i in key form; "inf" (no candidate, uncapped) stays inf
@@ -425,8 +445,10 @@ __device__ __forceinline__ void long_body(const Args &a) {
                     ws = i;
                 } else if (a.long_span && lane == 0) {
                     S.stg[i] = (int32_t)(uint32_t)(st_i >> 32);
-                    S.rec[i].w = (unsigned)st_i;   // rec[i].w (mask hi of start i) is in `cur` already
+                    // rec[i].w (mask hi of start i) is in `cur` already
+                    S.rec[i].w = (lit && !tri) ? (unsigned)st_i & ~TRB : (unsigned)st_i;
                 }
+                tr = wave_shift_in(tr, (wend || tri) ? 1u : 0u);
                 sk = shift_in64(sk, st_i);
                 cpj = wave_shift_in(cpj, cpi);
                 mlo = wave_shift_in(mlo, cur.z);

@@ -6,8 +6,9 @@
   atoms (DPT_MODE_ATOMS) and returns, per atom end i, the reachable part of the
   optimal-predecessor set ``segment_index_dp[i-1]``; the host then lists every shortest
   tokenization in the reference's DFS order (largest predecessor popped first, a subtree
-  finished before its siblings, dp_tokenize.py:49-69).  Dead ends (unreachable
-  predecessors, which the reference explores and drops) are never entered, so the list
+  finished before its siblings, dp_tokenize.py:49-69).  Unreachable predecessors
+  (which the reference explores and drops) are never entered; a reachable one whose
+  capped cost no path attains is entered and dropped as in the reference, so the list
   and its order are the reference's.  The second value is ``len_dp[-1]`` (capped DP).
   Raises IndexError on an empty input like the reference (dp_tokenize.py:49).
 * ``obtain_longest_token(tokenizations)`` (dp_tokenize.py:72-84): the first tokenization

@@ -189,7 +189,13 @@ int dpt_encode_host(dpt_ctx *c, const dpt_vocab *v, int mode, const uint8_t *tex
  * the string) edges[str_off[s]-str_off[0] + i - 1] has bit d set iff atom i-1-d .. i-1 is a
  * token, cost[i-1-d] + 1 == cost[i] and i-1-d is reachable -- the reference's
  * segment_index_dp[i-1] restricted to reachable starts (dp_tokenize.py:40-46), from which the
- * host enumerates every shortest tokenization in the reference's DFS order.
+ * host enumerates every shortest tokenization in the reference's DFS order.  Reachable: a path of
+ * tokens leads from the word's start to the atom boundary (the start itself is), under the capped and
+ * the uncapped DP alike; cost is the DP's own (capped: min(atoms since the word's start, ...)), so
+ * an unreachable end has an empty mask, and under the cap a reachable start may appear whose capped
+ * cost no path attains -- a dead end for the walk, as in the reference.  Entries of edges that are no
+ * atom end of a string (the tail of a string whose atoms have several bytes, a string of status 2) are
+ * unspecified.
  */
 int dpt_dp_host(dpt_ctx *c, const dpt_vocab *v, int mode_flags, const uint8_t *text, uint64_t n_bytes,
                 const uint64_t *str_off, const uint8_t *cut_mask, uint64_t n_str, int32_t *status,
