@@ -299,6 +299,24 @@ static int decode_launch(const dpt::DecodeLaunch &p, const dpt_detok *d, void *h
     return DPT_OK;
 }
 
+// The option checks of dpt_collate and dpt_collate_pair and the launch members both have (Opts: either call's options).
+// ``specials``: the flags that each put one special into a row, ``words`` their names; ``others``: the call's other flags.
+// Returns 0 with *r filled, or the error.
+constexpr uint32_t COLLATE_SIDES = DPT_COLLATE_PAD_LEFT | DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64;   // (flags of both calls)
+template <class Opts>
+static int collate_rows(dpt::CollateRows *r, const Opts *opts, uint32_t specials, const char *words, uint32_t others, uint64_t n_str,
+                        void *input_ids, void *mask, void *labels, uint32_t *lengths) {
+    const uint32_t row_len = opts->row_len, n_special = (uint32_t)__builtin_popcount(opts->flags & specials);
+    if (opts->flags & ~(specials | others)) return fail(DPT_E_ARG, "unknown bits in opts->flags");
+    if (row_len == 0) return fail(DPT_E_ARG, "opts->row_len is 0");
+    if (row_len < n_special) return fail(DPT_E_ARG, std::string("opts->row_len holds fewer elements than the ") + words + " asked for");
+    if (row_len > (1u << 31)) return fail(DPT_E_ARG, "opts->row_len over 2^31");
+    if (opts->row_stride && opts->row_stride < row_len) return fail(DPT_E_ARG, "opts->row_stride under row_len");
+    *r = {n_str, row_len, opts->row_stride ? opts->row_stride : row_len, opts->pad_id, opts->bos_id, opts->eos_id, opts->ignore_id,
+          opts->flags, input_ids, mask, labels, lengths};
+    return DPT_OK;
+}
+
 extern "C" {
 
 const char *dpt_last_error(void) { return g_err.c_str(); }
@@ -547,20 +565,12 @@ int dpt_collate(const int32_t *ids, const uint64_t *off, const uint64_t *counts,
     if (!off) return fail(DPT_E_ARG, "null off");
     if (!opts) return fail(DPT_E_ARG, "null opts");
     if (!input_ids) return fail(DPT_E_ARG, "null input_ids");
-    const uint32_t known = DPT_COLLATE_BOS | DPT_COLLATE_EOS | DPT_COLLATE_PAD_LEFT | DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64;
-    if (opts->flags & ~known) return fail(DPT_E_ARG, "unknown bits in opts->flags");
-    const uint32_t n_special = ((opts->flags & DPT_COLLATE_BOS) ? 1u : 0u) + ((opts->flags & DPT_COLLATE_EOS) ? 1u : 0u);
-    if (opts->row_len == 0) return fail(DPT_E_ARG, "opts->row_len is 0");
-    if (opts->row_len < n_special) return fail(DPT_E_ARG, "opts->row_len holds fewer elements than the BOS / EOS asked for");
-    if (opts->row_len > (1u << 31)) return fail(DPT_E_ARG, "opts->row_len over 2^31");
-    if (opts->row_stride && opts->row_stride < opts->row_len) return fail(DPT_E_ARG, "opts->row_stride under row_len");
-    if (n_str == 0) return DPT_OK;
     dpt::CollateLaunch p{};
-    p.ids = ids; p.off = off; p.counts = counts; p.status = status; p.n_str = n_str;
-    p.row_len = opts->row_len; p.row_stride = opts->row_stride ? opts->row_stride : opts->row_len;
-    p.pad_id = opts->pad_id; p.bos_id = opts->bos_id; p.eos_id = opts->eos_id; p.ignore_id = opts->ignore_id;
-    p.flags = opts->flags;
-    p.input_ids = input_ids; p.mask = attention_mask; p.labels = labels; p.lengths = lengths;
+    if (const int rc = collate_rows(&p.r, opts, DPT_COLLATE_BOS | DPT_COLLATE_EOS, "BOS / EOS", COLLATE_SIDES, n_str, input_ids,
+                                    attention_mask, labels, lengths))
+        return rc;
+    if (n_str == 0) return DPT_OK;
+    p.src = {ids, off, counts, status};
     const hipError_t e = dpt::launch_collate(p, (hipStream_t)hip_stream);
     if (e != hipSuccess) return hip_fail(e, "collate launch");
     return DPT_OK;
@@ -577,25 +587,16 @@ int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint6
     if (!b->off) return fail(DPT_E_ARG, "null b->off");
     if (!opts) return fail(DPT_E_ARG, "null opts");
     if (!input_ids) return fail(DPT_E_ARG, "null input_ids");
-    const uint32_t known = DPT_COLLATE_BOS | DPT_COLLATE_EOS | DPT_COLLATE_PAD_LEFT | DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64 |
-                           DPT_COLLATE_SEP | DPT_COLLATE_MASK_A | DPT_COLLATE_TRIM_A_FIRST;
-    if (opts->flags & ~known) return fail(DPT_E_ARG, "unknown bits in opts->flags");
-    const uint32_t n_special = ((opts->flags & DPT_COLLATE_BOS) ? 1u : 0u) + ((opts->flags & DPT_COLLATE_SEP) ? 1u : 0u) +
-                               ((opts->flags & DPT_COLLATE_EOS) ? 1u : 0u);
-    if (opts->row_len == 0) return fail(DPT_E_ARG, "opts->row_len is 0");
-    if (opts->row_len < n_special) return fail(DPT_E_ARG, "opts->row_len holds fewer elements than the BOS / SEP / EOS asked for");
-    if (opts->row_len > (1u << 31)) return fail(DPT_E_ARG, "opts->row_len over 2^31");
-    if (opts->row_stride && opts->row_stride < opts->row_len) return fail(DPT_E_ARG, "opts->row_stride under row_len");
-    if (n_str == 0) return DPT_OK;
     dpt::CollatePairLaunch p{};
+    if (const int rc = collate_rows(&p.r, opts, DPT_COLLATE_BOS | DPT_COLLATE_SEP | DPT_COLLATE_EOS, "BOS / SEP / EOS",
+                                    COLLATE_SIDES | DPT_COLLATE_MASK_A | DPT_COLLATE_TRIM_A_FIRST, n_str, input_ids, attention_mask,
+                                    labels, lengths))
+        return rc;
+    if (n_str == 0) return DPT_OK;
     p.a = {a->ids, a->off, a->counts, a->status};
     p.b = {b->ids, b->off, b->counts, b->status};
-    p.n_str = n_str;
-    p.row_len = opts->row_len; p.row_stride = opts->row_stride ? opts->row_stride : opts->row_len;
-    p.pad_id = opts->pad_id; p.bos_id = opts->bos_id; p.sep_id = opts->sep_id; p.eos_id = opts->eos_id; p.ignore_id = opts->ignore_id;
-    p.max_a = opts->max_a; p.max_b = opts->max_b; p.flags = opts->flags;
-    p.input_ids = input_ids; p.mask = attention_mask; p.labels = labels; p.token_type = token_type_ids;
-    p.lengths = lengths; p.b_start = b_start;
+    p.sep_id = opts->sep_id; p.max_a = opts->max_a; p.max_b = opts->max_b;
+    p.token_type = token_type_ids; p.b_start = b_start;
     const hipError_t e = dpt::launch_collate_pair(p, (hipStream_t)hip_stream);
     if (e != hipSuccess) return hip_fail(e, "collate pair launch");
     return DPT_OK;

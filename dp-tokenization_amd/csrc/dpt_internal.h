@@ -319,46 +319,37 @@ struct DecodeLaunch {
 };
 hipError_t launch_decode(const DecodeLaunch &p, hipStream_t stream);
 
-// One launch of the collate kernel (dpt_collate.hip; include/dpt.h dpt_collate): every pointer a device pointer,
-// the options already checked (row_len >= the specials asked for, row_stride >= row_len, known flags).
-struct CollateLaunch {
+// The launches of the collate kernel (dpt_collate.hip; include/dpt.h dpt_collate, dpt_collate_pair): every pointer a
+// device pointer, the options already checked (row_len >= the specials asked for, row_stride >= row_len, known flags).
+struct CollateSide {           // one source: the ids of an encoded batch
     const int32_t *ids;
     const uint64_t *off;       // n_str + 1
     const uint64_t *counts;    // nullable: the token counts come from off
     const int32_t *status;     // nullable: all 0
+};
+struct CollateRows {           // the rows and the outputs every launch has
     uint64_t n_str;
     uint32_t row_len;
     uint64_t row_stride;       // elements, >= row_len
     int32_t pad_id, bos_id, eos_id, ignore_id;
     uint32_t flags;            // DPT_COLLATE_*
-    void *input_ids;           // int32, or int64 with DPT_COLLATE_I64 (and the next two)
+    void *input_ids;           // int32, or int64 with DPT_COLLATE_I64 (and every other row output)
     void *mask;                // nullable
     void *labels;              // nullable
     uint32_t *lengths;         // nullable
+};
+struct CollateLaunch {
+    CollateSide src;
+    CollateRows r;
 };
 hipError_t launch_collate(const CollateLaunch &p, hipStream_t stream);
 
-// One launch of the pair collate kernel (dpt_collate.hip; include/dpt.h dpt_collate_pair): rows of two segments, each
-// side described as CollateLaunch's first four members; the options already checked.
-struct CollateSide {
-    const int32_t *ids;
-    const uint64_t *off;       // n_str + 1
-    const uint64_t *counts;    // nullable: the token counts come from off
-    const int32_t *status;     // nullable: all 0
-};
-struct CollatePairLaunch {
+struct CollatePairLaunch {     // rows of two segments
     CollateSide a, b;
-    uint64_t n_str;
-    uint32_t row_len;
-    uint64_t row_stride;       // elements, >= row_len
-    int32_t pad_id, bos_id, sep_id, eos_id, ignore_id;
+    CollateRows r;
+    int32_t sep_id;
     uint32_t max_a, max_b;     // per-side caps, 0: none
-    uint32_t flags;            // DPT_COLLATE_*
-    void *input_ids;           // int32, or int64 with DPT_COLLATE_I64 (and the next three)
-    void *mask;                // nullable
-    void *labels;              // nullable
     void *token_type;          // nullable
-    uint32_t *lengths;         // nullable
     uint32_t *b_start;         // nullable
 };
 hipError_t launch_collate_pair(const CollatePairLaunch &p, hipStream_t stream);

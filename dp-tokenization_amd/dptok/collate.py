@@ -38,6 +38,73 @@ def collate_device(ids_ptr: int, off_ptr: int, n_str: int, input_ids_ptr: int, r
                                  mask_ptr, labels_ptr, lengths_ptr, stream), "dpt_collate")
 
 
+def _check_padding(padding, padding_side, truncation_side):
+    if padding not in ("longest", "max_length"):
+        raise ValueError("padding must be 'longest' or 'max_length'")
+    if padding_side not in ("left", "right") or truncation_side not in ("left", "right"):
+        raise ValueError("padding_side / truncation_side must be 'left' or 'right'")
+
+
+def _check_side(torch, side, name=""):
+    """One source as (ids, off, status, counts) tensors, validated (``name``: the side, for the messages) -> the four
+    and n_str (-1: ``off`` is empty, which the caller reports)."""
+    ids, off, status, counts = (tuple(side) + (None, None))[:4]
+    name = name and name + ": "
+    for t in (ids, off, status, counts):
+        if t is not None and (not t.is_contiguous() or t.device != ids.device):
+            raise ValueError(name + "ids, off, status and counts must be contiguous tensors on one device")
+    if ids.dtype != torch.int32 or off.element_size() != 8 or (counts is not None and counts.element_size() != 8) \
+            or (status is not None and status.dtype != torch.int32):
+        raise ValueError(name + "ids / status must be int32, off / counts 8-byte integers")
+    n_str = off.numel() - 1
+    if (status is not None and status.numel() < n_str) or (counts is not None and counts.numel() < n_str):
+        raise ValueError("status / counts need n_str entries")
+    return (ids, off, status, counts), n_str
+
+
+def _row_len(torch, sides, caps, n_str, n_special, padding, max_length, pad_to_multiple_of):
+    """The row length of both calls: ``max_length``, or (``padding="longest"``) the longest row's kept tokens -- each
+    side's count under its cap (0: none), summed -- plus the specials, capped by ``max_length``; then at least
+    max(the specials, 1) and rounded up to ``pad_to_multiple_of``.  A failed string's row is all pad: it adds nothing."""
+    if padding == "max_length":
+        if max_length is None:
+            raise ValueError("padding='max_length' needs max_length")
+        row_len = int(max_length)
+    else:
+        row_len = 0
+        if n_str:
+            total = 0
+            for (_, off, status, counts), cap in zip(sides, caps):
+                n = counts.view(torch.int64)[:n_str] if counts is not None else off.view(torch.int64).diff()
+                if status is not None:
+                    n = n.masked_fill(status[:n_str] != 0, -(1 << 40))
+                total = total + (n.clamp(max=cap) if cap else n)
+            row_len = max(int(total.max()), 0) + n_special
+        if max_length is not None:
+            row_len = min(row_len, int(max_length))
+    row_len = max(row_len, n_special, 1)
+    if pad_to_multiple_of:
+        row_len = -(-row_len // pad_to_multiple_of) * pad_to_multiple_of
+    return row_len
+
+
+def _alloc(torch, rows, per_row, n_str, row_len, int64, dev):
+    """the [n_str, row_len] tensors named in ``rows`` and the int32 per-string ones named in ``per_row``"""
+    out = {k: torch.empty((n_str, row_len), dtype=torch.int64 if int64 else torch.int32, device=dev) for k in rows}
+    out.update((k, torch.empty(n_str, dtype=torch.int32, device=dev)) for k in per_row)
+    return out
+
+
+def _side_ptrs(torch, side):
+    """(ids, off, counts, status) device addresses of a validated side, 0 for None, and the tensor that keeps the ids'
+    address alive"""
+    ids, off, status, counts = side
+    if ids.numel() == 0:   # (an empty tensor has no address; no id is read)
+        ids = torch.zeros(1, dtype=torch.int32, device=off.device)
+    return (ids.data_ptr(), off.data_ptr(), counts.data_ptr() if counts is not None else 0,
+            status.data_ptr() if status is not None else 0), ids
+
+
 def model_inputs(ids, off, status=None, counts=None, *, padding: str = "longest", max_length: Optional[int] = None,
                  pad_to_multiple_of: Optional[int] = None, labels: bool = False, pad_id: int = 0,
                  bos_id: Optional[int] = None, eos_id: Optional[int] = None, ignore_id: int = -100,
@@ -53,52 +120,20 @@ def model_inputs(ids, off, status=None, counts=None, *, padding: str = "longest"
     ``pad_to_multiple_of`` and is at least max(the specials, 1).  Rows are int64 (``int64=False``: int32),
     ``lengths`` int32 per string."""
     import torch
-    if padding not in ("longest", "max_length"):
-        raise ValueError("padding must be 'longest' or 'max_length'")
-    if padding_side not in ("left", "right") or truncation_side not in ("left", "right"):
-        raise ValueError("padding_side / truncation_side must be 'left' or 'right'")
-    n_str = off.numel() - 1
+    _check_padding(padding, padding_side, truncation_side)
+    side, n_str = _check_side(torch, (ids, off, status, counts))
     if n_str < 0:
         raise ValueError("off needs n_str + 1 entries")
-    for t in (ids, off, status, counts):
-        if t is not None and (not t.is_contiguous() or t.device != ids.device):
-            raise ValueError("ids, off, status and counts must be contiguous tensors on one device")
-    if ids.dtype != torch.int32 or off.element_size() != 8 or (counts is not None and counts.element_size() != 8) \
-            or (status is not None and status.dtype != torch.int32):
-        raise ValueError("ids / status must be int32, off / counts 8-byte integers")
     n_special = (bos_id is not None) + (eos_id is not None)
-    if padding == "max_length":
-        if max_length is None:
-            raise ValueError("padding='max_length' needs max_length")
-        row_len = int(max_length)
-    else:
-        row_len = 0
-        if n_str:
-            n = counts.view(torch.int64)[:n_str] if counts is not None else off.view(torch.int64).diff()
-            if status is not None:
-                n = n.masked_fill(status[:n_str] != 0, -n_special)   # a failed string's row is all pad
-            row_len = int(n.max()) + n_special
-        if max_length is not None:
-            row_len = min(row_len, int(max_length))
-    row_len = max(row_len, n_special, 1)
-    if pad_to_multiple_of:
-        row_len = -(-row_len // pad_to_multiple_of) * pad_to_multiple_of
-    dtype = torch.int64 if int64 else torch.int32
+    row_len = _row_len(torch, [side], [0], n_str, n_special, padding, max_length, pad_to_multiple_of)
     dev = ids.device
-    out = {"input_ids": torch.empty((n_str, row_len), dtype=dtype, device=dev),
-           "attention_mask": torch.empty((n_str, row_len), dtype=dtype, device=dev),
-           "lengths": torch.empty(n_str, dtype=torch.int32, device=dev)}
-    if labels:
-        out["labels"] = torch.empty((n_str, row_len), dtype=dtype, device=dev)
+    out = _alloc(torch, ["input_ids", "attention_mask"] + (["labels"] if labels else []), ["lengths"], n_str, row_len, int64, dev)
     if n_str == 0:
         return out
-    if ids.numel() == 0:   # (an empty tensor has no address; no id is read)
-        ids = torch.zeros(1, dtype=torch.int32, device=dev)
+    (ids_ptr, off_ptr, counts_ptr, status_ptr), _keep = _side_ptrs(torch, side)
     with torch.cuda.device(dev):
-        collate_device(ids.data_ptr(), off.data_ptr(), n_str, out["input_ids"].data_ptr(), row_len,
-                       counts_ptr=counts.data_ptr() if counts is not None else 0,
-                       status_ptr=status.data_ptr() if status is not None else 0,
-                       mask_ptr=out["attention_mask"].data_ptr(),
+        collate_device(ids_ptr, off_ptr, n_str, out["input_ids"].data_ptr(), row_len, counts_ptr=counts_ptr,
+                       status_ptr=status_ptr, mask_ptr=out["attention_mask"].data_ptr(),
                        labels_ptr=out["labels"].data_ptr() if labels else 0, lengths_ptr=out["lengths"].data_ptr(),
                        pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, ignore_id=ignore_id,
                        pad_left=padding_side == "left", trunc_left=truncation_side == "left", int64=int64,
@@ -132,18 +167,6 @@ def collate_pair_device(a, b, n_str: int, input_ids_ptr: int, row_len: int, *, m
           "dpt_collate_pair")
 
 
-def _check_side(torch, side, name):
-    """One side of ``pair_model_inputs`` as (ids, off, status, counts), validated like ``model_inputs``' arguments."""
-    ids, off, status, counts = (tuple(side) + (None, None))[:4]
-    for t in (ids, off, status, counts):
-        if t is not None and (not t.is_contiguous() or t.device != ids.device):
-            raise ValueError("%s: ids, off, status and counts must be contiguous tensors on one device" % name)
-    if ids.dtype != torch.int32 or off.element_size() != 8 or (counts is not None and counts.element_size() != 8) \
-            or (status is not None and status.dtype != torch.int32):
-        raise ValueError("%s: ids / status must be int32, off / counts 8-byte integers" % name)
-    return ids, off, status, counts
-
-
 def pair_model_inputs(a, b, *, padding: str = "longest", max_length: Optional[int] = None,
                       pad_to_multiple_of: Optional[int] = None, max_source: Optional[int] = None,
                       max_target: Optional[int] = None, labels: bool = False, mask_source: bool = False,
@@ -162,58 +185,25 @@ def pair_model_inputs(a, b, *, padding: str = "longest", max_length: Optional[in
     ``max_length``; ``"max_length"`` synchronises nothing.  ``b_start`` (int32 per row) is the column of the target's
     first position."""
     import torch
-    if padding not in ("longest", "max_length"):
-        raise ValueError("padding must be 'longest' or 'max_length'")
-    if padding_side not in ("left", "right") or truncation_side not in ("left", "right"):
-        raise ValueError("padding_side / truncation_side must be 'left' or 'right'")
+    _check_padding(padding, padding_side, truncation_side)
     if trim not in ("target", "source"):
         raise ValueError("trim must be 'target' or 'source'")
-    sides = [_check_side(torch, a, "a"), _check_side(torch, b, "b")]
-    n_str = sides[0][1].numel() - 1
-    if n_str < 0 or sides[1][1].numel() - 1 != n_str:
+    (side_a, n_str), (side_b, n_b) = _check_side(torch, a, "a"), _check_side(torch, b, "b")
+    if n_str < 0 or n_b != n_str:
         raise ValueError("both off tensors need the same n_str + 1 entries")
-    dev = sides[0][0].device
-    if sides[1][0].device != dev:
+    dev = side_a[0].device
+    if side_b[0].device != dev:
         raise ValueError("both sides must be on one device")
-    for _, _, status, counts in sides:
-        if (status is not None and status.numel() < n_str) or (counts is not None and counts.numel() < n_str):
-            raise ValueError("status / counts need n_str entries")
     caps = [int(max_source or 0), int(max_target or 0)]
     n_special = (bos_id is not None) + (sep_id is not None) + (eos_id is not None)
-    if padding == "max_length":
-        if max_length is None:
-            raise ValueError("padding='max_length' needs max_length")
-        row_len = int(max_length)
-    else:
-        row_len = 0
-        if n_str:
-            total = 0
-            for (_, off, status, counts), cap in zip(sides, caps):
-                n = counts.view(torch.int64)[:n_str] if counts is not None else off.view(torch.int64).diff()
-                if status is not None:   # a failed row is all pad
-                    n = n.masked_fill(status[:n_str] != 0, -(1 << 40))
-                total = total + (n.clamp(max=cap) if cap else n)
-            row_len = max(int(total.max()), 0) + n_special
-        if max_length is not None:
-            row_len = min(row_len, int(max_length))
-    row_len = max(row_len, n_special, 1)
-    if pad_to_multiple_of:
-        row_len = -(-row_len // pad_to_multiple_of) * pad_to_multiple_of
-    dtype = torch.int64 if int64 else torch.int32
+    row_len = _row_len(torch, [side_a, side_b], caps, n_str, n_special, padding, max_length, pad_to_multiple_of)
     rows = ["input_ids", "attention_mask"] + (["labels"] if labels else []) + (["token_type_ids"] if token_type_ids else [])
-    out = {k: torch.empty((n_str, row_len), dtype=dtype, device=dev) for k in rows}
-    out["lengths"] = torch.empty(n_str, dtype=torch.int32, device=dev)
-    out["b_start"] = torch.empty(n_str, dtype=torch.int32, device=dev)
+    out = _alloc(torch, rows, ["lengths", "b_start"], n_str, row_len, int64, dev)
     if n_str == 0:
         return out
-    ptrs = []
-    for ids, off, status, counts in sides:
-        if ids.numel() == 0:   # (an empty tensor has no address; no id is read)
-            ids = torch.zeros(1, dtype=torch.int32, device=dev)
-        ptrs.append((ids, (ids.data_ptr(), off.data_ptr(), counts.data_ptr() if counts is not None else 0,
-                           status.data_ptr() if status is not None else 0)))
+    (ptrs_a, _keep_a), (ptrs_b, _keep_b) = _side_ptrs(torch, side_a), _side_ptrs(torch, side_b)
     with torch.cuda.device(dev):
-        collate_pair_device(ptrs[0][1], ptrs[1][1], n_str, out["input_ids"].data_ptr(), row_len,
+        collate_pair_device(ptrs_a, ptrs_b, n_str, out["input_ids"].data_ptr(), row_len,
                             mask_ptr=out["attention_mask"].data_ptr(), labels_ptr=out["labels"].data_ptr() if labels else 0,
                             token_type_ptr=out["token_type_ids"].data_ptr() if token_type_ids else 0,
                             lengths_ptr=out["lengths"].data_ptr(), b_start_ptr=out["b_start"].data_ptr(), pad_id=pad_id,

@@ -332,16 +332,21 @@ def _model_inputs_surface(engine, tokenizer, pack_batch):
                 counts = counts[:n].masked_fill(d_none, 0)
         return dev, ids, d_offs, st, counts[:n].contiguous(), offs
 
+    def checked_specials(errors, add_bos, add_eos):
+        """the prelude of both calls: ``errors`` checked, and the tokenizer's (bos, eos, pad) ids with those asked for present"""
+        if errors not in ("raise", "mask"):
+            raise ValueError("errors must be 'raise' or 'mask'")
+        bos, eos, pad = _special_ids(tokenizer)
+        if (add_bos and bos is None) or (add_eos and eos is None):
+            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
+        return bos, eos, pad
+
     def batch_model_inputs(texts, max_length=None, padding="longest", pad_to_multiple_of=None, add_bos=False,
                            add_eos=False, padding_side="right", truncation_side="right", labels=False, errors="raise"):
         import torch
         from dptok.collate import model_inputs
-        if errors not in ("raise", "mask"):
-            raise ValueError("errors must be 'raise' or 'mask'")
+        bos, eos, pad = checked_specials(errors, add_bos, add_eos)
         texts = list(texts)
-        bos, eos, pad = _special_ids(tokenizer)
-        if (add_bos and bos is None) or (add_eos and eos is None):
-            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
         dev, ids, d_offs, st, counts, _ = encode_padded(texts)
         with torch.cuda.device(dev):
             out = model_inputs(ids, d_offs, st, counts, padding=padding, max_length=max_length,
@@ -361,14 +366,10 @@ def _model_inputs_surface(engine, tokenizer, pack_batch):
                                 padding_side="right", truncation_side="right", errors="raise"):
         import torch
         from dptok.collate import pair_model_inputs
-        if errors not in ("raise", "mask"):
-            raise ValueError("errors must be 'raise' or 'mask'")
+        bos, eos, pad = checked_specials(errors, add_bos, add_eos)
         sources, targets = list(sources), list(targets)
         if len(sources) != len(targets):
             raise ValueError("%d sources for %d targets" % (len(sources), len(targets)))
-        bos, eos, pad = _special_ids(tokenizer)
-        if (add_bos and bos is None) or (add_eos and eos is None):
-            raise ValueError("the tokenizer has no %s id to add" % ("BOS" if add_bos and bos is None else "EOS"))
         n = len(sources)
         dev, ids, d_offs, st, counts, offs = encode_padded(sources + targets)
         first_b = int(offs[n] - offs[0])   # side B: the same buffers from string n on (its ids start at str_off[n])

@@ -8,42 +8,18 @@ import numpy as np
 import pytest
 
 import matrix_corpus as mc
+from collate_harness import (BOS_ID, EOS_ID, IGNORE, OOV, PAD_ID, SENT, TEXTS, Out, Side, _llama_fixture, as_numpy, assert_equal,
+                             random_batch)
+from collate_harness import raw_reference as make_raw_reference
 from collate_ref import BOS, EOS, I64, PAD_LEFT, TRUNC_LEFT, collate_ref
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64   # elements; a multiple of 16 bytes for both widths, so ``base`` below is the offset from a 16-byte boundary
-SENT = -0x5A5A5A5B
-PAD_ID, BOS_ID, EOS_ID, IGNORE = -7, 40001, 40002, -100
 ALL16 = [b | e | p | t for b in (0, BOS) for e in (0, EOS) for p in (0, PAD_LEFT) for t in (0, TRUNC_LEFT)]
 
 
 def n_special(flags):
     return bool(flags & BOS) + bool(flags & EOS)
-
-
-class Out:
-    """[n_str, L] rows of ``stride`` elements inside a sentinel-filled tensor, ``base`` elements past GUARD."""
-
-    def __init__(self, torch, n_str, L, stride, dtype, base=0):
-        self.n_str, self.L, self.stride, self.base = n_str, L, stride or L, base
-        self.span = (n_str - 1) * self.stride + L if n_str else 0
-        self.whole = torch.full((GUARD + base + self.span + GUARD,), SENT, dtype=dtype, device="cuda")
-        assert self.whole.data_ptr() % 16 == 0
-
-    def ptr(self):
-        return self.whole.data_ptr() + (GUARD + self.base) * self.whole.element_size()
-
-    def rows(self):
-        """the rows as a numpy [n_str, L] array, after asserting that nothing else was written"""
-        w = self.whole.cpu().numpy()
-        lo = GUARD + self.base
-        assert (w[:lo] == SENT).all() and (w[lo + self.span:] == SENT).all(), "guard zone written"
-        full = np.full(self.n_str * self.stride, SENT, dtype=w.dtype)
-        full[:self.span] = w[lo:lo + self.span]
-        full = full.reshape(self.n_str, self.stride)
-        assert (full[:, self.L:] == SENT).all(), "row gap written"
-        return full[:, :self.L]
 
 
 def run_collate(torch, ids, off, L, flags, *, counts=None, status=None, stride=0, base=0, ids_shift=0,
@@ -53,18 +29,13 @@ def run_collate(torch, ids, off, L, flags, *, counts=None, status=None, stride=0
     from dptok import collate
     n_str = len(off) - 1
     dtype = torch.int64 if flags & I64 else torch.int32
-    d_ids = torch.zeros(max(len(ids), 1) + ids_shift, dtype=torch.int32, device="cuda")
-    d_ids[ids_shift:ids_shift + len(ids)] = torch.from_numpy(np.asarray(ids, dtype=np.int32))
-    d_off = torch.from_numpy(np.asarray(off, dtype=np.uint64).view(np.int64)).cuda()
-    d_cnt = None if counts is None else torch.from_numpy(np.asarray(counts, dtype=np.uint64).view(np.int64)).cuda()
-    d_st = None if status is None or "status" in null else torch.from_numpy(np.asarray(status, dtype=np.int32)).cuda()
+    src = Side(torch, ids, off, counts, None if "status" in null else status, shift=ids_shift)
+    ids_ptr, off_ptr, counts_ptr, status_ptr = src.ptrs()
     o_ids = Out(torch, n_str, L, stride, dtype, base)
     o_mask = None if "mask" in null else Out(torch, n_str, L, stride, dtype, base)
     o_lab = None if "labels" in null else Out(torch, n_str, L, stride, dtype, base)
     o_len = None if "lengths" in null else Out(torch, 1, n_str, 0, torch.int32, 1)
-    collate.collate_device(d_ids.data_ptr() + 4 * ids_shift, d_off.data_ptr(), n_str, o_ids.ptr(), L,
-                           counts_ptr=d_cnt.data_ptr() if d_cnt is not None else 0,
-                           status_ptr=d_st.data_ptr() if d_st is not None else 0,
+    collate.collate_device(ids_ptr, off_ptr, n_str, o_ids.ptr(), L, counts_ptr=counts_ptr, status_ptr=status_ptr,
                            mask_ptr=o_mask.ptr() if o_mask else 0, labels_ptr=o_lab.ptr() if o_lab else 0,
                            lengths_ptr=o_len.ptr() if o_len else 0, row_stride=stride, pad_id=PAD_ID,
                            bos_id=BOS_ID if flags & BOS else None, eos_id=EOS_ID if flags & EOS else None, ignore_id=IGNORE,
@@ -75,29 +46,10 @@ def run_collate(torch, ids, off, L, flags, *, counts=None, status=None, stride=0
            o_len.rows()[0] if o_len else None)
     if check:
         want = collate_ref(np.asarray(ids).tolist(), [int(x) for x in off], None if counts is None else [int(x) for x in counts],
-                           None if d_st is None else np.asarray(status).tolist(), row_len=L, pad_id=PAD_ID, bos_id=BOS_ID, eos_id=EOS_ID,
+                           None if src.d_st is None else np.asarray(status).tolist(), row_len=L, pad_id=PAD_ID, bos_id=BOS_ID, eos_id=EOS_ID,
                            ignore_id=IGNORE, flags=flags)
         assert_equal(got, want, (L, flags, stride, base))
     return got
-
-
-def assert_equal(got, want, what):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if g is None:
-            continue
-        w = np.array(w, dtype=np.int64).reshape(g.shape)
-        assert g.dtype in (np.int32, np.int64)
-        bad = np.argwhere(g != w)
-        assert not len(bad), (what, "output %d" % k, bad[:5].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
-
-
-def random_batch(rng, counts, first=0):
-    """CSR (ids, off) of strings with the given token counts; off starts at ``first``."""
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64) + np.uint64(first)
-    ids = rng.integers(0, 50000, size=int(off[-1] - off[0]), dtype=np.int64).astype(np.int32)
-    if len(ids) > 3:
-        ids[1], ids[3] = -1, -2 ** 31
-    return ids, off
 
 
 @pytest.fixture(scope="module")
@@ -211,14 +163,7 @@ def test_long_rows(L, flags, torch):
 @pytest.fixture(scope="module")
 def raw_reference():
     """vocab -> (Encoder, ids, id_off, status) of the RAW corpus through the host path, computed once."""
-    from dptok import Encoder, Vocab
-    text, offs, _ = mc.form("raw")
-    out = {}
-    for name in ("base", "long+40000"):
-        enc = Encoder(Vocab(mc.vocabularies()[name], 0))
-        ids, id_off, st, _ = enc.encode_csr(text, offs)
-        out[name] = (enc, ids, id_off, st)
-    return out
+    return make_raw_reference(("base", "long+40000"))
 
 
 @pytest.mark.parametrize("vocab", ["base", "long+40000"])
@@ -309,13 +254,8 @@ def test_model_inputs(torch):
     assert empty["input_ids"].shape == (0, 8) and empty["lengths"].shape == (0,)
 
 
-OOV = "hello 字 world"   # raw mode: a word no vocabulary here tokenizes (status 1, ValueError in ``batch``)
-TEXTS = ["the weather is nice", "hello world", "a", "optimal length tokenization of a longer sentence here", "x y", "it's 7:45"]
-
-
 def _as_numpy(out):
-    return (out["input_ids"].cpu().numpy(), out["attention_mask"].cpu().numpy(),
-            out["labels"].cpu().numpy() if "labels" in out else None, out["lengths"].cpu().numpy())
+    return as_numpy(out, ("input_ids", "attention_mask", "labels", "lengths"))
 
 
 def _check_adapter(torch, dp_tokenize, tokenizer, texts, bad_text=None):
@@ -363,17 +303,6 @@ def _check_adapter(torch, dp_tokenize, tokenizer, texts, bad_text=None):
     assert (out["input_ids"][2] == pad).all() and not out["attention_mask"][2].any() and int(out["lengths"][2]) == 0
     keep = [0, 1] + list(range(3, len(mixed)))
     assert torch.equal(out["input_ids"][keep], masked["input_ids"]) and torch.equal(out["attention_mask"][keep], masked["attention_mask"])
-
-
-def _llama_fixture():
-    from fake_llama import FakeLlamaTokenizer
-
-    class Tok(FakeLlamaTokenizer):   # the fixture plus the special-token attributes of a transformers tokenizer
-        bos_token_id, eos_token_id, pad_token_id = 1, 2, None
-
-    t2i = mc.vocabularies()["base"]
-    assert t2i["<s>"] == 1 and t2i["</s>"] == 2
-    return Tok(t2i)
 
 
 def test_adapter_raw(torch):

@@ -9,13 +9,13 @@ import numpy as np
 import pytest
 
 import matrix_corpus as mc
+from collate_harness import (BOS_ID, EOS_ID, IGNORE, OOV, PAD_ID, SENT, SEP_ID, TEXTS, Out, Side, _llama_fixture, as_numpy, assert_equal,
+                             random_batch)
+from collate_harness import raw_reference as make_raw_reference
 from collate_pair_ref import (BOS, EOS, I64, MASK_A, PAD_LEFT, SEP, TRIM_A_FIRST, TRUNC_LEFT, collate_pair_ref, n_special)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64   # elements; a multiple of 16 bytes for both widths, so ``base`` below is the offset from a 16-byte boundary
-SENT = -0x5A5A5A5B
-PAD_ID, BOS_ID, SEP_ID, EOS_ID, IGNORE = -7, 40001, 40003, 40002, -100
 SEVEN = (BOS, EOS, PAD_LEFT, TRUNC_LEFT, SEP, MASK_A, TRIM_A_FIRST)
 ALL128 = [sum(f for f, on in zip(SEVEN, bits) if on) for bits in itertools.product((0, 1), repeat=7)]
 ROW_OUTPUTS = ("input_ids", "mask", "labels", "types")
@@ -25,55 +25,6 @@ ROW_OUTPUTS = ("input_ids", "mask", "labels", "types")
 def torch():
     import torch
     return torch
-
-
-class Out:
-    """[n_str, L] rows of ``stride`` elements inside a sentinel-filled tensor, ``base`` elements past GUARD."""
-
-    def __init__(self, torch, n_str, L, stride, dtype, base=0):
-        self.n_str, self.L, self.stride, self.base = n_str, L, stride or L, base
-        self.span = (n_str - 1) * self.stride + L if n_str else 0
-        self.whole = torch.full((GUARD + base + self.span + GUARD,), SENT, dtype=dtype, device="cuda")
-        assert self.whole.data_ptr() % 16 == 0
-
-    def ptr(self):
-        return self.whole.data_ptr() + (GUARD + self.base) * self.whole.element_size()
-
-    def rows(self):
-        """the rows as a numpy [n_str, L] array, after asserting that nothing else was written"""
-        w = self.whole.cpu().numpy()
-        lo = GUARD + self.base
-        assert (w[:lo] == SENT).all() and (w[lo + self.span:] == SENT).all(), "guard zone written"
-        full = np.full(self.n_str * self.stride, SENT, dtype=w.dtype)
-        full[:self.span] = w[lo:lo + self.span]
-        full = full.reshape(self.n_str, self.stride)
-        assert (full[:, self.L:] == SENT).all(), "row gap written"
-        return full[:, :self.L]
-
-
-class Side:
-    """One side's host arrays, uploaded once: CSR (``counts`` None) or the counts layout; ``shift``: the ids start
-    that many elements into their tensor (a 4-byte aligned ids pointer)."""
-
-    def __init__(self, torch, ids, off, counts=None, status=None, shift=0):
-        self.ids, self.off, self.counts, self.status = np.asarray(ids, dtype=np.int32), np.asarray(off, dtype=np.uint64), counts, status
-        self.n_str = len(off) - 1
-        self.d_ids = torch.zeros(max(len(ids), 1) + shift, dtype=torch.int32, device="cuda")
-        self.d_ids[shift:shift + len(ids)] = torch.from_numpy(self.ids)
-        self.ids_ptr = self.d_ids.data_ptr() + 4 * shift
-        self.d_off = torch.from_numpy(self.off.view(np.int64)).cuda()
-        self.d_cnt = None if counts is None else torch.from_numpy(np.asarray(counts, dtype=np.uint64).view(np.int64)).cuda()
-        self.d_st = None if status is None else torch.from_numpy(np.asarray(status, dtype=np.int32)).cuda()
-
-    def ptrs(self, status=True):
-        return (self.ids_ptr, self.d_off.data_ptr(), self.d_cnt.data_ptr() if self.d_cnt is not None else 0,
-                self.d_st.data_ptr() if status and self.d_st is not None else 0)
-
-    def lists(self, status=True):
-        """the side as collate_pair_ref takes it; a failed string's count is not handed over (it may be poison)"""
-        st = None if not status or self.status is None else np.asarray(self.status).tolist()
-        cnt = None if self.counts is None else [int(c) if not (st and st[s]) else 0 for s, c in enumerate(self.counts)]
-        return self.ids.tolist(), [int(x) for x in self.off], cnt, st
 
 
 def run_pair(torch, a, b, L, flags, *, max_a=0, max_b=0, stride=0, base=0, null=(), stream=0, check=True):
@@ -102,25 +53,6 @@ def run_pair(torch, a, b, L, flags, *, max_a=0, max_b=0, stride=0, base=0, null=
                                 bos_id=BOS_ID, sep_id=SEP_ID, eos_id=EOS_ID, ignore_id=IGNORE, max_a=max_a, max_b=max_b, flags=flags)
         assert_equal(got, want, (L, flags, max_a, max_b, stride, base, null))
     return got
-
-
-def assert_equal(got, want, what):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if g is None:
-            continue
-        w = np.array(w, dtype=np.int64).reshape(g.shape)
-        assert g.dtype in (np.int32, np.int64)
-        bad = np.argwhere(g != w)
-        assert not len(bad), (what, "output %d" % k, bad[:5].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
-
-
-def random_batch(rng, counts, first=0, lo=0):
-    """CSR (ids, off) of strings with the given token counts; off starts at ``first``; ids from ``lo`` up."""
-    off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64) + np.uint64(first)
-    ids = rng.integers(lo, lo + 50000, size=int(off[-1] - off[0]), dtype=np.int64).astype(np.int32)
-    if len(ids) > 3:
-        ids[1], ids[3] = -1, -2 ** 31
-    return ids, off
 
 
 def pair_sides(torch, rng, counts_a, counts_b, **kw):
@@ -311,11 +243,7 @@ def test_empty_b_equals_dpt_collate(torch):
 @pytest.fixture(scope="module")
 def raw_reference():
     """(Encoder, ids, id_off, status) of the RAW corpus through the host path, computed once."""
-    from dptok import Encoder, Vocab
-    text, offs, _ = mc.form("raw")
-    enc = Encoder(Vocab(mc.vocabularies()["base"], 0))
-    ids, id_off, st, _ = enc.encode_csr(text, offs)
-    return enc, ids, id_off, st
+    return make_raw_reference(("base",))["base"]
 
 
 def test_encode_then_collate_pair_both_layouts(raw_reference, torch):
@@ -384,8 +312,7 @@ def test_encode_then_collate_pair_both_layouts(raw_reference, torch):
 # ------------------------------------------------------------------ 8. the Python surface
 
 def _as_numpy(out):
-    return tuple(out[k].cpu().numpy() if k in out else None
-                 for k in ("input_ids", "attention_mask", "labels", "token_type_ids", "lengths", "b_start"))
+    return as_numpy(out, ("input_ids", "attention_mask", "labels", "token_type_ids", "lengths", "b_start"))
 
 
 def test_pair_model_inputs(torch):
@@ -430,8 +357,7 @@ def test_pair_model_inputs(torch):
         collate.pair_model_inputs(A, B, trim="both")
 
 
-OOV = "hello 字 world"   # raw mode: a word no vocabulary here tokenizes (status 1, ValueError in ``batch``)
-SOURCES = ["the weather is nice", "hello world", "a", "optimal length tokenization of a longer sentence here", "x y", "it's 7:45"]
+SOURCES = TEXTS
 TARGETS = ["nice weather", "x", "a longer target sentence for the shortest source", "b", "hello hello world", "y"]
 
 
@@ -489,15 +415,6 @@ def _check_pair_adapter(torch, dp_tokenize, tokenizer, sources, targets, bad_tex
         assert (out["input_ids"][r] == pad).all() and not out["attention_mask"][r].any() and int(out["lengths"][r]) == 0
         assert (out["labels"][r] == pad).all() and int(out["b_start"][r]) == 0
     assert torch.equal(out["input_ids"][0], masked["input_ids"][0]) and torch.equal(out["input_ids"][4:], masked["input_ids"][3:])
-
-
-def _llama_fixture():
-    from fake_llama import FakeLlamaTokenizer
-
-    class Tok(FakeLlamaTokenizer):   # the fixture plus the special-token attributes of a transformers tokenizer
-        bos_token_id, eos_token_id, pad_token_id = 1, 2, None
-
-    return Tok(mc.vocabularies()["base"])
 
 
 def test_adapter_raw(torch):
