@@ -128,6 +128,22 @@ __device__ __forceinline__ unsigned gshr(unsigned x, unsigned fill) {
     }
 }
 
+// x behind an empty asm (no instruction): the optimizer cannot see through it, so a select on a loaded value is not
+// turned back into an exec-mask branch (a load that only one side of a select needs is sunk under a branch of its own)
+__device__ __forceinline__ unsigned opaque(unsigned x) {
+    asm("" : "+v"(x));
+    return x;
+}
+// max over the 64 lanes, wave-uniform (an SGPR): row_shr maxima, then the rows' last lanes
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true));
+    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true));
+    return uni(max(max((unsigned)__builtin_amdgcn_readlane((int)v, 15), (unsigned)__builtin_amdgcn_readlane((int)v, 31)),
+                   max((unsigned)__builtin_amdgcn_readlane((int)v, 47), (unsigned)__builtin_amdgcn_readlane((int)v, 63))));
+}
+
 // 64-bit inclusive add-scan over the wave (ds_bpermute shifts)
 __device__ __forceinline__ uint64_t wave_incl_scan_add64(uint64_t v, unsigned lane) {
 #pragma unroll
@@ -898,6 +914,15 @@ __device__ __forceinline__ unsigned part_string(unsigned npart, unsigned p, unsi
 constexpr bool NEAR_CUT = DPT_NEAR_CUT != 0;
 // (the 64-lane push recurrence keeps the next cut: nearest measured 0.9 % slower on BLOOM, r05e)
 constexpr bool NEAR_CUT64 = false;
+// A/B knobs: the shape of lane-mode B's loops (forward_lanes, G = 16; DESIGN.md 4, "the shape of the lane loops")
+#ifndef DPT_CUT_SEL     // the cut-point pass without a branch per boundary: a clamped read and a predicated min / mask
+#define DPT_CUT_SEL 1   // update, so the reads of the unrolled steps are in flight together (0: `if (i <= c1)`)
+#endif
+constexpr bool CUT_SEL = DPT_CUT_SEL != 0;
+#ifndef DPT_LOOP_UNI    // the recurrence and C1 walk loops count the wave's longest lane down in an SGPR: their state
+#define DPT_LOOP_UNI 1  // is then not copied across the loop edge (0: the ballot of the lanes' own guard per step)
+#endif
+constexpr bool LOOP_UNI = DPT_LOOP_UNI != 0;
 #ifndef DPT_A0_SWAR     // A/B knob: phase A0's per-byte flags four bytes per VALU op (bit 7 of each byte)
 #define DPT_A0_SWAR 1
 #endif
@@ -2709,10 +2734,20 @@ struct TokPass {
                     using CutM = std::conditional_t<(CMAX > 32u), uint64_t, uint32_t>;
                     unsigned mloc = 0xFFFFu;
                     CutM lcut = 0;
+                    // the branch-free pass where it costs no registers: not in the 512-byte pass (33 reads in flight:
+                    // 136 -> 194 VGPRs) nor in the lean pair's list-fed general kernel (2 more VGPR spills)
+                    constexpr bool CUT_FLAT = CUT_SEL && CMAX <= 32u && LEAN != 2;
 #pragma unroll 4
                     for (int k = (int)CMAX - 1; k >= 0; k--) {
                         const unsigned i = c0 + 1u + (unsigned)k;
-                        if (i <= c1) {
+                        if constexpr (CUT_FLAT) {
+                            // every lane reads (an end past the chunk reads rec[c1], c1 <= na), so the reads of the
+                            // unrolled steps do not wait for one another: 17 dependent LDS round trips become 3
+                            const unsigned in = i <= c1 ? 1u : 0u;
+                            const unsigned hb = 31u - (unsigned)__builtin_clz((~opaque(rec32[min(i, c1)]) >> 16) | 1u);
+                            mloc = in ? min(mloc, i - 1u - hb) : mloc;
+                            lcut |= (CutM)(in & (mloc >= i - 1u ? 1u : 0u)) << k;
+                        } else if (i <= c1) {
                             const unsigned hb = 31u - (unsigned)__builtin_clz((~rec32[i] >> 16) | 1u);   // bit 0 is set in a capless window
                             mloc = min(mloc, i - 1u - hb);
                             if (mloc >= i - 1u) lcut |= (CutM)1 << k;   // boundary p = i-1 = c0+k < c1
@@ -2773,7 +2808,9 @@ struct TokPass {
                     unsigned T = 0;                  // tokens of the chunk: the pieces' costs
                     // (reading the next position's first candidates a step ahead, or two candidates per inner
                     // iteration, measured slower: r03y, r03)
-                    while (ballot(i < re)) {
+                    unsigned nrec = 0;   // LOOP_UNI: the wave's longest chunk
+                    if constexpr (LOOP_UNI) nrec = wave_umax(re - min(rs, re));   // (rs <= re: the chunks tile (0, na])
+                    while (LOOP_UNI ? nrec-- != 0u : ballot(i < re) != 0ull) {
                         if (i < re) {
                             i++;
                             const unsigned r = nxt;
@@ -2803,7 +2840,7 @@ struct TokPass {
                             rec32[i] = (best << 16) | (r & 0x87FFu) | ((30u - (best & 31u)) << 11);
                             L.fin[i].v = (uint8_t)(dg | (de << 4));
                             const bool wend = (r & CP_WS) != 0;
-                            if (wend) {
+                            if (wend) {   // (as selects: nothing on cfg2, DESIGN.md 9, rec-a)
                                 T += best >> 6;
                                 if (!pe) pe = i;
                             }
@@ -2898,10 +2935,14 @@ struct TokPass {
                         unsigned ii = re, k = walk ? tb + T : tb, A = left_of_q ? ls1 : 0u, Ls = ls1;
                         unsigned pend = rec32[re] & 0x7FFu;
                         bool inp1 = true;
-                        while (ballot(k > tb)) {
+                        unsigned nst = 0;   // LOOP_UNI: the wave's longest walk
+                        if constexpr (LOOP_UNI) nst = wave_umax(k - tb);
+                        while (LOOP_UNI ? nst-- != 0u : ballot(k > tb) != 0ull) {
                             if (k > tb) {
                                 const unsigned rr = rec32[ii];
                                 const unsigned cpi = rr & 0x7FFu;
+                                // (the word-end case as mask arithmetic, with fin[ii] read beside rec[ii]: a straight
+                                // 42-instruction step, and measured slower -- DESIGN.md 9, walk-a / walk-b)
                                 if (ii < re && (rr & CP_WS)) {   // into the word ending at ii
                                     Ls = ((rr >> 11) & 15u) + 1u;
                                     A = 0;

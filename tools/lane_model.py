@@ -34,7 +34,12 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
     a fix-up loop over every end of (rs, lim] that rewrites fin[] before the walks; kept so that
     the equivalence stays testable (tests/test_lane_fold_model.py).  stats (a dict, fold=True):
     "walk_steps", "fold_changed" (steps where the rule picked de over a different dg) and "g1"
-    (every value the recurrence or the word-end update wrote) are accumulated into it."""
+    (every value the recurrence or the word-end update wrote) are accumulated into it, and a census of the
+    situations the walk loops meet (tests/test_lane_walk_census.py): "wend_mid_walk" (walk steps that enter a
+    word ending inside the chunk), "re_ws" (non-empty chunks that end on a word start), "not_p1in" (chunks whose
+    first piece is not P1), "rewalk" (de-mode re-walks of P1 taken) with "rewalk_steps", "t0_t15_rows" (rows
+    holding a chunk with T == 0 beside one with T >= 15) and "nl_span" (selected tokens of two or more atoms
+    with a '\\n' atom among them: the code-point prefix jumps by 6 inside the span)."""
     atoms, wsf, cpos = window(text)
     na = len(atoms)
     # end masks: bit d of em[i] = atoms i-1-d .. i-1 form a token (within a word)
@@ -109,6 +114,12 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
         if not re_ws: T += sprev >> 6
         gl1 = 31 - ((key[re] if re_ws else sprev) & 31)
         l.update(pe=pe, T=T, sprev=sprev, re_ws=re_ws, p1in=p1in, gl1=gl1)
+        if stats is not None:
+            stats["re_ws"] = stats.get("re_ws", 0) + int(re_ws)
+            stats["not_p1in"] = stats.get("not_p1in", 0) + int(not p1in)
+    if stats is not None:
+        ts = [l["T"] for l in lanes]
+        stats["t0_t15_rows"] = stats.get("t0_t15_rows", 0) + int(min(ts) == 0 and max(ts) >= 15)
     # transfer scan (left to right)
     inn = FRESH
     for d, l in enumerate(lanes):
@@ -155,6 +166,8 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
         while k > tbd:
             if ii < re and wsf[ii]:
                 Ls = lstar[ii]; A = 0; pend = cpos[ii]; inp1 = False
+                if stats is not None:
+                    stats["wend_mid_walk"] = stats.get("wend_mid_walk", 0) + 1
             n1 += inp1
             f = fin[ii]
             sp = pend - cpos[ii]; A = max(A, sp)
@@ -165,6 +178,8 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
                 if tie and A < Ls and (f & 15) != (f >> 4):
                     stats["fold_changed"] = stats.get("fold_changed", 0) + 1
             j = ii - 1 - dd
+            if stats is not None and dd >= 1 and any(cpos[q + 1] - cpos[q] == 6 for q in range(j, ii)):
+                stats["nl_span"] = stats.get("nl_span", 0) + 1
             k -= 1; starts[k] = j
             pend = cpos[ii]; ii = j
         assert ii == rs, (d, ii, rs)
@@ -180,6 +195,9 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
         l["fin_in"] = f
         if f and not l["left"] and (not l["p1in"] or l["gin"] < l["ls1"]):
             ii = l["re"]; k = l["tb"] + l["T"]
+            if stats is not None:
+                stats["rewalk"] = stats.get("rewalk", 0) + 1
+                stats["rewalk_steps"] = stats.get("rewalk_steps", 0) + l["n1"]
             for c in range(l["n1"]):
                 j = ii - 1 - (fin[ii] >> 4)
                 k -= 1; starts[k] = j; ii = j
