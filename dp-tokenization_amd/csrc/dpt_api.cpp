@@ -491,6 +491,26 @@ int dpt_token_spans(const dpt_vocab *v, int mode, const uint8_t *text, uint64_t 
     return DPT_OK;
 }
 
+int dpt_bpe_encode(const dpt_bpe *b, const dpt_vocab *v, const uint8_t *text, uint64_t n_bytes, const uint64_t *str_off,
+                   const uint8_t *cut_mask, uint64_t n_str, int32_t *ids, uint64_t ids_cap, uint64_t *counts, int32_t *status,
+                   uint32_t *tok_word, void *hip_stream) {
+    if (!b || !v) return fail(DPT_E_ARG, "null bpe / vocab");
+    if (!str_off || !counts || !status) return fail(DPT_E_ARG, "null str_off / counts / status");
+    if (n_bytes && (!text || !cut_mask || !ids)) return fail(DPT_E_ARG, "null text / cut_mask / ids");
+    if (ids_cap < n_bytes) return fail(DPT_E_ARG, "ids_cap < n_bytes");
+    if (b->device != v->device) return fail(DPT_E_ARG, "pair table and vocabulary on different devices");
+    if (n_str == 0) return DPT_OK;
+    dpt::BpeLaunch p{};
+    p.text = text; p.str_off = str_off; p.cut_mask = cut_mask; p.n_str = n_str; p.ids = ids; p.counts = counts;
+    p.status = status; p.tok_word = tok_word;
+    p.entries = b->d_entries; p.header = dpt::BpeHeader{b->n_buckets, b->seed};
+    p.slots4 = v->d_slots4; p.n_slots = v->stats.n_slots; p.root_base = v->root_base;
+    DeviceGuard g(v->device);
+    const hipError_t e = dpt::launch_bpe(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "bpe launch");
+    return DPT_OK;
+}
+
 int dpt_detok_create(const uint8_t *utf8_blob, const uint64_t *tok_off, const int32_t *ids, uint32_t n_tok, int rule,
                      const int32_t *skip_ids, uint32_t n_skip, int device, dpt_detok **out) {
     if (!out || !tok_off || (!utf8_blob && n_tok && tok_off[n_tok] != tok_off[0]) || (n_skip && !skip_ids))

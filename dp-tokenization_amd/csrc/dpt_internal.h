@@ -1,6 +1,6 @@
 // Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp,
-// dpt_pretok.cpp, dpt_bytelevel.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip, dpt_collate.hip,
-// dpt_pretok.hip, dpt_bytelevel.hip).
+// dpt_pretok.cpp, dpt_bytelevel.cpp, dpt_bpe.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip,
+// dpt_collate.hip, dpt_pretok.hip, dpt_bytelevel.hip, dpt_bpe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/dpt.h"
+#include "dpt_bpe_table.h"
 #include "dpt_lean_hint.h"
 
 namespace dpt {
@@ -373,6 +374,7 @@ const char *build_pretok_tables(const uint8_t *blob, const uint64_t *off, uint32
 // every pointer a device pointer.
 struct PretokLaunch {
     bool write;                  // false: the sizes pass
+    bool atoms;                  // write: the mask is an ATOMS mask (dpt_pretok_write_atoms)
     const uint8_t *text;
     const uint64_t *str_off;
     uint64_t n_str;
@@ -428,6 +430,36 @@ struct ByteLevelLaunch {
     uint8_t *cut_mask;
 };
 hipError_t launch_bytelevel(const ByteLevelLaunch &p, hipStream_t stream);
+
+// Pair table of a greedy BPE merge (dpt_bpe.cpp build_bpe_tables; include/dpt.h dpt_bpe_create), as host bytes
+// exactly as dpt_bpe_create uploads them (dpt_bpe_table.h has the format and the probe).
+struct BpeTables {
+    BpeHeader header{0, 0};
+    std::vector<uint4> entries;     // 2 * header.n_buckets
+};
+// returns 0 or an error message (DPT_E_ARG); calls no HIP function
+const char *build_bpe_tables(const int32_t *left, const int32_t *right, const int32_t *merged, const uint32_t *rank,
+                             uint64_t n_pairs, BpeTables *out);
+
+// One launch of the merge kernel (dpt_bpe.hip; include/dpt.h dpt_bpe_encode): every pointer a device pointer.
+struct BpeLaunch {
+    const uint8_t *text;
+    const uint64_t *str_off;
+    const uint8_t *cut_mask;
+    uint64_t n_str;
+    int32_t *ids;
+    uint64_t *counts;
+    int32_t *status;
+    uint32_t *tok_word;          // nullable
+    // the pair table
+    const uint4 *entries;
+    BpeHeader header;
+    // the vocabulary's trie (slots4: {base | TERM | LEAF, check, id, child filter})
+    const int4 *slots4;
+    uint32_t n_slots;
+    int32_t root_base;
+};
+hipError_t launch_bpe(const BpeLaunch &p, hipStream_t stream);
 
 // host double-array trie over token bytes (dpt_vocab.cpp)
 struct DoubleArray {

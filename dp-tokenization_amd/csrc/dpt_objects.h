@@ -50,6 +50,13 @@ struct dpt_bytelevel {
     uint64_t ascii[2] = {0, 0};
 };
 
+// The device copy of a BPE pair table (dpt_bpe.cpp build_bpe_tables; the format is in dpt_bpe_table.h).
+struct dpt_bpe {
+    int device = 0;
+    uint4 *d_entries = nullptr;     // 2 * n_buckets entries {left, right, merged, rank}
+    uint32_t n_buckets = 0, seed = 0;
+};
+
 struct dpt_ctx {
     int device = 0;
     // workspace of the device path (ensure_workspace)

@@ -200,4 +200,16 @@ int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *s
                       out_off, cut_mask, hip_stream);
 }
 
+static int pretok_launch_atoms(const dpt_pretok *t, PretokLaunch p, void *hip_stream) {
+    p.atoms = true;
+    return pretok_launch(t, p, hip_stream);
+}
+
+int dpt_pretok_write_atoms(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                           const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
+                           void *hip_stream) {
+    return split_call(p, "null pretok", pretok_launch_atoms, true, text, str_off, n_str, nullptr, const_cast<int32_t *>(pre_status),
+                      out_text, out_off, cut_mask, hip_stream);
+}
+
 }  // extern "C"

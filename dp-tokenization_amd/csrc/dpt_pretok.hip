@@ -1,4 +1,5 @@
-// dpt_pretok.hip -- llama mode's pre-split text made on the device (dpt_pretok_sizes, dpt_pretok_write).
+// dpt_pretok.hip -- llama mode's pre-split text made on the device (dpt_pretok_sizes, dpt_pretok_write,
+// dpt_pretok_write_atoms).
 //
 // The rule is in include/dpt.h (dpt_pretok_create): a certified string's pre-split form is a per-character function
 // of its text -- ' ' becomes U+2581 opening a word, a character that is a piece of its own stays, any other
@@ -111,7 +112,9 @@ __device__ __forceinline__ bool literal_at(const PretokLaunch &a, bool cand, uns
     return ballot(hit) != 0;
 }
 
-template <bool WRITE>
+// ATOMS (write alone): the mask is an ATOMS mask -- 3 where the plain mask has 1, 2 at the first byte of every other atom
+// (a character that stays, each <0xNN> of an expansion); the text is the same.
+template <bool WRITE, bool ATOMS = false>
 __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
     const unsigned lane = lane_id();
     const uint64_t wave = (uint64_t)blockIdx.x * WAVES + uni(threadIdx.x >> 6);
@@ -170,7 +173,7 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
                     const unsigned sa = lane_read(cur, src & 63u), sb = lane_read(nxt, src & 63u);
                     const unsigned c = src < 64u ? sa : sb;
                     unsigned out;
-                    bool opens = false;
+                    bool opens = false, atom = false;
                     if (o < pfx) {
                         out = a.prefix[o];
                         opens = o == a.bos_len;
@@ -179,14 +182,17 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
                         opens = k == 0;
                     } else if (kind == K_COPY) {
                         out = c;
+                        atom = k == 0;
                     } else {
                         const unsigned q = k - 6u * j;
                         const unsigned h = q == 3 ? (c >> 4) & 15u : c & 15u;
                         const unsigned hx = h < 10u ? '0' + h : 'A' + h - 10u;
                         out = q == 0 ? '<' : q == 1 ? '0' : q == 2 ? 'x' : q == 5 ? '>' : hx;
+                        atom = q == 0;
                     }
                     *outp = out;
-                    *mask = opens || g == 0 ? 1 : 0;   // (the string's first byte opens a word too)
+                    const bool word = opens || g == 0;   // (the string's first byte opens a word too)
+                    *mask = ATOMS ? (word ? 3 : atom ? 2 : 0) : (word ? 1 : 0);
                 });
             }
             cur = nxt;
@@ -200,7 +206,7 @@ __global__ void __launch_bounds__(WAVES * 64) pretok_kernel(PretokLaunch a) {
 }  // namespace pre
 
 hipError_t launch_pretok(const PretokLaunch &p, hipStream_t stream) {
-    return txt::launch_split(pre::pretok_kernel<false>, pre::pretok_kernel<true>, p, stream);
+    return txt::launch_split(pre::pretok_kernel<false>, p.atoms ? pre::pretok_kernel<true, true> : pre::pretok_kernel<true, false>, p, stream);
 }
 
 }  // namespace dpt

@@ -5,6 +5,7 @@ Public surface:
     Detok                   ids back to bytes and the round-trip check (detok.py)
     Pretok                  llama mode's pre-split text made on the device (pretok.py)
     ByteLevelSplit          the BLOOM adapter's ATOMS input made on the device (bytelevel.py)
+    Bpe                     the tokenizer's own greedy-BPE ids of an ATOMS input, on the device (bpe.py)
     collate                 padded model inputs from an encoded batch, on the device (collate.py: the
                             ``collate_device`` / ``model_inputs`` calls and their source + target forms
                             ``collate_pair_device`` / ``pair_model_inputs``; imported on demand, it needs torch)
@@ -15,13 +16,14 @@ The reference-compatible names (dp_tokenize_llama, compute_shortest_tokenization
 live in the sibling ``packages`` / ``inspect_tokenizer`` modules of this directory.
 """
 from ._lib import DptError, RT_DIFFERS, RT_EQUAL, STATUS_EMPTY_WORD, STATUS_INTERNAL, STATUS_NO_TOKENIZATION, STATUS_OK, STATUS_TOO_LONG
+from .bpe import Bpe
 from .bytelevel import BLOOM_SEPARATORS, ByteLevelSplit
 from .detok import Detok
 from .engine import Encoder, Vocab, raise_and_collect, raise_for_status
 from .pack import TokenSpans, pack_strings
 from .pretok import Pretok
 
-__all__ = ["Vocab", "Encoder", "Detok", "Pretok", "ByteLevelSplit", "BLOOM_SEPARATORS", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
+__all__ = ["Vocab", "Encoder", "Detok", "Pretok", "ByteLevelSplit", "Bpe", "BLOOM_SEPARATORS", "RT_EQUAL", "RT_DIFFERS", "DptError", "TokenSpans", "pack_strings", "raise_for_status", "dp_tokenize_batch",
            "STATUS_OK", "STATUS_NO_TOKENIZATION", "STATUS_EMPTY_WORD", "STATUS_TOO_LONG", "STATUS_INTERNAL"]
 
 

@@ -127,6 +127,7 @@ CALLS = {
     "dpt_pretok_destroy": (I32, [P]),
     "dpt_pretok_sizes": (I32, [P, P, P, U64, P, P, P]),
     "dpt_pretok_write": (I32, [P, P, P, U64, P, P, P, P, P]),
+    "dpt_pretok_write_atoms": (I32, [P, P, P, U64, P, P, P, P, P]),
     "dpt_debug_pretok_table": (I32, [P, P, U32, P, U32, P, P, U32, I32, P, U64, PU64]),
     # byte-level (BLOOM) pre-tokenization on the device
     "dpt_bytelevel_create": (I32, [P, U32, I32, PP]),
@@ -134,6 +135,11 @@ CALLS = {
     "dpt_bytelevel_sizes": (I32, [P, P, P, U64, P, P, P]),
     "dpt_bytelevel_write": (I32, [P, P, P, U64, P, P, P, P, P]),
     "dpt_debug_bytelevel_table": (I32, [P, U32, I32, P, U64, PU64]),
+    # the tokenizer's own (greedy BPE) encoding on the device
+    "dpt_bpe_create": (I32, [P, P, P, P, U64, I32, PP]),
+    "dpt_bpe_destroy": (I32, [P]),
+    "dpt_bpe_encode": (I32, [P, P, P, U64, P, P, U64, P, U64, P, P, P, P]),
+    "dpt_debug_bpe_lookup": (I32, [P, P, P, P, U64, P, P, U64, P, P]),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -148,11 +154,14 @@ DECODE_CALLS = {name: CALLS[name][1] for name in CALLS if name in OPTIONAL and n
 # dpt_debug_wave_grid is test-only: ``wave_grid`` below raises without it.
 OPTIONAL_LATER = {"dpt_collate", "dpt_collate_pair", "dpt_debug_wave_grid"}
 # Likewise the pre-tokenization calls: name -> argument types; ``pretok.Pretok`` raises without them (has_pretok).
-PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name}
+PRETOK_CALLS = {name: CALLS[name][1] for name in CALLS if "_pretok_" in name and name != "dpt_pretok_write_atoms"}
 OPTIONAL_PRETOK = set(PRETOK_CALLS)
 # And the byte-level split calls; ``bytelevel.ByteLevelSplit`` raises without them (has_bytelevel).
 BYTELEVEL_CALLS = {name: CALLS[name][1] for name in CALLS if "_bytelevel_" in name}
 OPTIONAL_BYTELEVEL = set(BYTELEVEL_CALLS)
+# And the BPE calls, with the pre-tokenization call that makes their llama input; ``bpe.Bpe`` raises without them (has_bpe).
+BPE_CALLS = {name: CALLS[name][1] for name in CALLS if "_bpe_" in name or name == "dpt_pretok_write_atoms"}
+OPTIONAL_BPE = set(BPE_CALLS)
 
 
 def lib():
@@ -172,7 +181,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL and not hasattr(L, name):
+        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL | OPTIONAL_BPE and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -206,6 +215,12 @@ def has_bytelevel() -> bool:
     """The loaded library exports the byte-level split calls."""
     L = lib()
     return all(hasattr(L, name) for name in BYTELEVEL_CALLS)
+
+
+def has_bpe() -> bool:
+    """The loaded library exports the BPE calls."""
+    L = lib()
+    return all(hasattr(L, name) for name in BPE_CALLS)
 
 
 def wave_grid(n_str: int, waves: int = 4) -> int:

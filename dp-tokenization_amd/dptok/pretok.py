@@ -75,14 +75,17 @@ class Pretok:
               "dpt_pretok_sizes")
 
     def write_device(self, text_ptr: int, off_ptr: int, n_str: int, pre_status_ptr: int, out_text_ptr: int, out_off_ptr: int,
-                     cut_ptr: int, stream: int = 0) -> None:
+                     cut_ptr: int, stream: int = 0, atoms: bool = False) -> None:
         """dpt_pretok_write: string s's pre-split form at out_text + out_off[s] - out_off[0] and its cut mask at
         the same index of cut (out_off: uint64[n_str + 1], the prefix sum of ``sizes_device``'s lengths from any
-        start; pre_status: what it wrote)."""
-        check(_lib.lib().dpt_pretok_write(self.handle, text_ptr, off_ptr, n_str, pre_status_ptr, out_text_ptr, out_off_ptr,
-                                          cut_ptr, stream), "dpt_pretok_write")
+        start; pre_status: what it wrote).  ``atoms``: dpt_pretok_write_atoms -- the same text under a
+        DPT_MODE_ATOMS mask (3 where a word opens, 2 at every other atom's first byte), ``Bpe``'s input."""
+        call = "dpt_pretok_write_atoms" if atoms else "dpt_pretok_write"
+        check(getattr(_lib.lib(), call)(self.handle, text_ptr, off_ptr, n_str, pre_status_ptr, out_text_ptr, out_off_ptr,
+                                        cut_ptr, stream), call)
 
-    def presplit(self, text_t, offs_t):
+    def presplit(self, text_t, offs_t, atoms: bool = False):
         """torch device tensors in (text uint8, offsets int64[n + 1]) -> (text2 uint8, offs2 int64[n + 1] from 0,
         cut uint8, pre_status int32[n]) on the same device: sizes, a cumsum, write.  One host read (the total)."""
-        return two_pass_split(self.sizes_device, self.write_device, text_t, offs_t)
+        write = (lambda *a: self.write_device(*a, atoms=True)) if atoms else self.write_device
+        return two_pass_split(self.sizes_device, write, text_t, offs_t)

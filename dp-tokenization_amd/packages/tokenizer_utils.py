@@ -23,6 +23,12 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   atoms made on the GPU too (dptok/bytelevel.py; the rule: include/dpt.h dpt_bytelevel_create).  The rule is exact, so
   only text that is not well-formed UTF-8 goes through the host path; construction checks the pre-tokenizer's shape,
   the byte alphabet and a probe list, and raises DptError on the first difference.
+* with ``device_pretokenize=True`` both adapters also carry ``dp_tokenize.batch_default(List[str])`` --
+  ``[tokenizer.encode(t) for t in texts]`` with the certified strings pre-tokenized and BPE-merged on the GPU
+  (dptok/bpe.py; include/dpt.h dpt_bpe_encode) -- and ``dp_tokenize.batch_compare(List[str])``, the lengths and per-word
+  token counts of the shortest tokenization next to the default one (reference main_analyze_s2orc.py:269-297,
+  main_biomed_translation.py:74-77).  Construction checks a probe list against ``tokenizer.encode`` and leaves both off,
+  with the reason in ``dp_tokenize.pretok_stats.default_off``, when they disagree.
 * ``dp_tokenize.batch(List[str]) -> List[List[int]]``: the batched form (one GPU launch, in both
   modes).
 * ``dp_tokenize.batch_spans(List[str]) -> List[TokenSpans]``: the batch's ids aligned to the text --
@@ -415,10 +421,12 @@ def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, sp
 
 class PretokStats:
     """``dp_tokenize.pretok_stats``: of the last batch call, the strings the device rule certified and the
-    strings sent through the host tokenizer.  Reads as the tuple (certified, sent_to_host)."""
+    strings sent through the host tokenizer.  Reads as the tuple (certified, sent_to_host).  ``default_off``: None
+    when ``dp_tokenize.batch_default`` / ``batch_compare`` are on, else why construction left them off."""
 
     def __init__(self):
         self.certified = self.sent_to_host = 0
+        self.default_off = None
 
     def set(self, certified: int, sent_to_host: int) -> None:
         self.certified, self.sent_to_host = int(certified), int(sent_to_host)
@@ -578,9 +586,89 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
     literals = _pretok_literals(tokenizer, t2i)
     pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
     presplit, *paths, stats = _device_split_paths(pretok.presplit, "presplit", engine, host.pack)
+    stats.split_atoms = lambda d_text, d_offs: pretok.presplit(d_text, d_offs, atoms=True)   # (_default_surface)
     _probe_check(presplit, stats, PROBES, merge_words, 0xFF, True,
                  "tokenizer is not one the rule holds for (a normalising model, other added-token behaviour)")
     return (*paths, stats)
+
+
+def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab, probes, empty_ids, host_only, stats):
+    """``dp_tokenize.batch_default`` and ``dp_tokenize.batch_compare``: the tokenizer's own ids made on the device
+    (dptok/bpe.py; the rule: include/dpt.h dpt_bpe_encode) next to the shortest tokenization -- the comparison the
+    reference drivers exist for (main_analyze_s2orc.py:269-297, main_biomed_translation.py:74-77).
+
+    ``split_atoms(d_text, d_offs)`` -> the device ATOMS form (text2, offs2, cut, pre_status); ``make_table()`` -> the
+    pair table's four arrays by the route the tokenizer object offers; ``bpe_vocab`` the ``Vocab`` whose ids are the
+    tokenizer's; ``host_only(text)``: the text must go to the host tokenizer whatever the device rule says.
+    Construction runs ``probes`` through ``batch_default`` against ``tokenizer.encode``; when they disagree, when
+    ``tokenizer.encode("")`` is not ``empty_ids`` or when the table cannot be built, both attributes stay off and
+    ``stats.default_off`` says why (None: they are on)."""
+    import torch
+    from dptok.bpe import Bpe
+
+    dev = torch.device("cuda", _device())
+    stats.default_off = None
+
+    def host_encode(text):
+        return [int(i) for i in tokenizer.encode(text)]
+
+    def device_default(texts, want_words):
+        """Per string the default ids (None: the device does not take it) and, with want_words, their word indices."""
+        ids_out: List[Optional[List[int]]] = [None] * len(texts)
+        words_out: List[Optional[np.ndarray]] = [None] * len(texts)
+        take = [i for i, t in enumerate(texts) if not host_only(t)]
+        if not take:
+            return ids_out, words_out
+        text, offs = pack_strings([texts[i] for i in take])
+        with torch.cuda.device(dev):
+            text2, offs2, cut, pre = split_atoms(torch.from_numpy(text.copy()).to(dev), torch.from_numpy(offs.view(np.int64)).to(dev))
+            ids, counts, status, words = bpe.encode_atoms(bpe_vocab, text2, offs2, cut, tok_word=want_words)
+            ids_h, cnt_h, st_h, pre_h, o = (x.cpu().numpy() for x in (ids, counts, status, pre, offs2))
+            words_h = words.cpu().numpy() if want_words else None
+        for k, i in enumerate(take):
+            if pre_h[k] == 0 and st_h[k] == 0:
+                a, c = int(o[k]), int(cnt_h[k])
+                ids_out[i] = ids_h[a:a + c].tolist()
+                if want_words:
+                    words_out[i] = words_h[a:a + c]
+        return ids_out, words_out
+
+    def batch_default(texts: Sequence[str]) -> List[List[int]]:
+        """``[tokenizer.encode(t) for t in texts]``: the strings the device rules certify are pre-tokenized and merged
+        on the GPU (two pre-tokenization kernels and dpt_bpe_encode), the others go to the host tokenizer."""
+        texts = list(texts)
+        got, _ = device_default(texts, False)
+        return [g if g is not None else host_encode(t) for g, t in zip(got, texts)]
+
+    def batch_compare(texts: Sequence[str]) -> dict:
+        """The shortest tokenization against the tokenizer's own, per string: ``dp_lengths`` and ``default_lengths``
+        (int64 arrays: the ``len`` of ``dp_tokenize.batch`` and of ``tokenizer.encode``), ``improved`` (the mask
+        dp < default), and ``dp_word_counts`` / ``default_word_counts``: per string the tokens in each word of its
+        pre-tokenization (bincounts of the word index of every token; the default side's is None for a string that went
+        to the host tokenizer).  The reference's per-word step re-encodes each word as a text of its own, which adds a
+        BOS and a dummy prefix to both sides; here the words are compared in place, inside their string."""
+        texts = list(texts)
+        spans = dp_tokenize.batch_spans(texts)
+        got, words = device_default(texts, True)
+        default = [g if g is not None else host_encode(t) for g, t in zip(got, texts)]
+        dp_len = np.array([len(s.ids) for s in spans], dtype=np.int64)
+        df_len = np.array([len(d) for d in default], dtype=np.int64)
+        dp_words = [np.bincount(np.asarray(s.word_ids, dtype=np.int64)) if s.word_ids else np.zeros(0, dtype=np.int64) for s in spans]
+        df_words = [None if w is None else np.bincount(w.astype(np.int64)) if len(w) else np.zeros(0, dtype=np.int64) for w in words]
+        return {"dp_lengths": dp_len, "default_lengths": df_len, "improved": dp_len < df_len, "dp_word_counts": dp_words,
+                "default_word_counts": df_words}
+
+    try:
+        bpe = Bpe(*make_table(), device=_device())
+        if host_encode("") != list(empty_ids):
+            raise ValueError("tokenizer.encode('') is %r, the rule gives %r" % (host_encode(""), list(empty_ids)))
+        for probe, got in zip(probes, batch_default(probes)):
+            if got != host_encode(probe):
+                raise ValueError("the device rule gives %r for the probe %r, the tokenizer %r" % (got, probe, host_encode(probe)))
+    except (ValueError, KeyError, DptError) as e:
+        stats.default_off = "batch_default is off: %s" % e
+        return
+    dp_tokenize.batch_default, dp_tokenize.batch_compare = batch_default, batch_compare
 
 
 def _presplit_words(presplit, texts, bit: int = 0xFF) -> List[Optional[List[str]]]:
@@ -681,10 +769,35 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama", device_pretok
     # is dropped.  The round trip compares with the ORIGINAL text in both modes.
     decode_batch, batch_roundtrip = _decode_surface(
         lambda: Detok(t2i, "sp", [b for b in [_bos_id(llama_tokenizer)] if b is not None], _device()), True, encode_many)
-    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
+    pair = _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
                            _model_inputs_surface(engine, llama_tokenizer, pack_batch), decode_batch, batch_roundtrip,
                            "SentencePiece's", **({"host_pool": host} if pretokenize_option == "llama" else {}),
                            **({"pretok_stats": pretok_stats} if pretokenize_option == "llama" and device_pretokenize else {}))
+    if pretokenize_option == "llama" and device_pretokenize:
+        # the tokenizer's own ids on the device as well: dp_tokenize.batch_default / batch_compare
+        from dptok.pretok_probes import PROBES
+        bos = _bos_id(llama_tokenizer)
+        _default_surface(dp_tokenize, llama_tokenizer, pretok_stats.split_atoms, lambda: _llama_pairs(llama_tokenizer, t2i),
+                         engine.vocab, PROBES, [] if bos is None else [bos], lambda t: False, pretok_stats)
+    return pair
+
+
+def _llama_pairs(tokenizer, t2i):
+    """The pair table of a Llama-style tokenizer object by the route it offers: the ``merges`` of its
+    ``backend_tokenizer``, else the scores of its SentencePiece processor (``sp_model``; ``sp`` on a bare wrapper)."""
+    from dptok.bpe import pairs_from_scores, pairs_from_tokenizer_json
+    backend = getattr(tokenizer, "backend_tokenizer", None)
+    if backend is not None:
+        return pairs_from_tokenizer_json(backend.to_str())
+    sp = getattr(tokenizer, "sp_model", None) or getattr(tokenizer, "sp", None)
+    if sp is None or not hasattr(sp, "get_score"):
+        raise ValueError("the tokenizer object offers neither backend_tokenizer merges nor sp_model scores")
+    n = sp.get_piece_size()
+    exclude = [i for i in range(n) if sp.is_control(i) or sp.is_unknown(i) or sp.is_unused(i) or sp.is_byte(i)]
+    pieces = {sp.id_to_piece(i): i for i in range(n)}
+    if any(t2i.get(p) != i for p, i in pieces.items()):
+        raise ValueError("the SentencePiece model's ids are not get_vocab()'s")
+    return pairs_from_scores(pieces, {p: sp.get_score(i) for p, i in pieces.items()}, exclude)
 
 
 BLOOM_TOKENIZER_JSON = ("{}/models--bigscience--bloom-3b/snapshots/"
@@ -731,6 +844,7 @@ def _device_bytelevel(tokenizer, vocab_to_index, engine, host_pack, pretokenize)
                            % (back[b], alphabet[b], b))
     splitter = ByteLevelSplit(BLOOM_SEPARATORS, _device())
     presplit, *paths, stats = _device_split_paths(splitter.split, "atoms", engine, host_pack)
+    stats.split_atoms = splitter.split   # (_default_surface)
     _probe_check(presplit, stats, PROBES, pretokenize, 1, False, "pre-tokenizer is not the one the rule holds for")
     return (*paths, stats)
 
@@ -811,7 +925,27 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=False):
     # the UTF-8 of the input
     decode_batch, batch_roundtrip = _decode_surface(lambda: Detok(dict(vocab_to_index), "bytelevel", (), _device()), False,
                                                     encode_many)
-    return _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
+    pair = _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many,
                            _model_inputs_surface(engine, bloom_tokenizer, pack_batch), decode_batch, batch_roundtrip,
                            "ByteLevel's", vocab_to_index=vocab_to_index,
                            **({"pretok_stats": pretok_stats} if device_pretokenize else {}))
+    if device_pretokenize:
+        # the tokenizer's own ids on the device as well: dp_tokenize.batch_default / batch_compare.  ``encode`` matches
+        # the added-token literals before the model does and pre_tokenize_str does not: such a text goes to the host
+        from dptok.bpe import pairs_from_merges
+        from dptok.bytelevel_probes import PROBES
+        model = tokenizer_json["model"]
+        real = model["vocab"]
+        literals = [t for t in dict.fromkeys(list(getattr(bloom_tokenizer, "all_special_tokens", None) or [])
+                                             + list(bloom_tokenizer.get_added_vocab())) if t]
+
+        def make_table():
+            if json.loads(bloom_tokenizer._tokenizer.to_str()).get("normalizer") is not None:
+                raise ValueError("the tokenizer has a normalizer")
+            return pairs_from_merges(real, merges, model)
+
+        same_ids = all(real[t] == i for i, t in enumerate(real))
+        _default_surface(dp_tokenize, bloom_tokenizer, pretok_stats.split_atoms, make_table,
+                         engine.vocab if same_ids else Vocab(dict(real), _device()), PROBES, [],
+                         lambda t: any(x in t for x in literals), pretok_stats)
+    return pair

@@ -21,6 +21,10 @@
  *                        function of the text: DPT_MODE_PRESPLIT input made on the device
  *   dpt_bytelevel_sizes, dpt_bytelevel_write <- the BLOOM adapter's pre_tokenize_str + per-character atoms
  *                        (packages/tokenizer_utils.py:155-162): DPT_MODE_ATOMS input made on the device
+ *   dpt_bpe_encode     <- the other side of both drivers' comparison, the tokenizer's own ids:
+ *                        len(llama_tokenizer.encode(x)), reference main_analyze_s2orc.py:272, :282, and
+ *                        len(bloom_tokenizer.encode(x)), main_biomed_translation.py:74 (dpt_pretok_write_atoms or
+ *                        dpt_bytelevel_write make its input)
  *   dpt_token_histogram <- the length comparison of the S2ORC probe,
  *                        reference main_analyze_s2orc.py:269-297 (len(dp_tokenize(x)))
  *   dpt_token_spans    <- the probe's per-word comparison, reference main_analyze_s2orc.py:275-290
@@ -521,6 +525,15 @@ int dpt_pretok_sizes(const dpt_pretok *p, const uint8_t *text, const uint64_t *s
 int dpt_pretok_write(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
                      const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
                      void *hip_stream);
+/* Added within ABI 6 (DPT_ABI_VERSION unchanged).  dpt_pretok_write with a DPT_MODE_ATOMS mask, the input of
+ * dpt_bpe_encode: the same arguments, the same text, and cut_mask = 3 at the output's first byte and at the first
+ * byte of every word-opening U+2581, 2 at the first byte of every other atom, 0 elsewhere.  The atoms are the BOS
+ * piece (one atom), each U+2581, each character that is a piece of its own, and each <0xNN> group that byte fallback
+ * produced (one atom of 6 bytes).  A literal "<0x41>" typed in the text is six one-character atoms: SentencePiece
+ * keeps the two apart, because byte pieces never take part in merges, and the PRESPLIT form cannot. */
+int dpt_pretok_write_atoms(const dpt_pretok *p, const uint8_t *text, const uint64_t *str_off, uint64_t n_str,
+                           const int32_t *pre_status, uint8_t *out_text, const uint64_t *out_off, uint8_t *cut_mask,
+                           void *hip_stream);
 /* TEST-ONLY, needs no device.  The bytes dpt_pretok_create would upload for these arguments, built on the host
  * (tests/pretok_ref.py holds a model of the format).  which: 0 the known set below U+10000 as a bitmap (2048 uint32:
  * bit cp & 31 of word cp >> 5), 1 the known code points from U+10000 up (uint32, ascending), 2 the literal block
@@ -587,6 +600,53 @@ int dpt_bytelevel_write(const dpt_bytelevel *p, const uint8_t *text, const uint6
 #define DPT_BYTELEVEL_SCALAR_INTS 2
 int dpt_debug_bytelevel_table(const uint32_t *sep_cps, uint32_t n_sep, int which, void *out, uint64_t cap,
                               uint64_t *size);
+
+/*
+ * The tokenizer's own encoding on the device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).  The reference drivers
+ * compare the shortest tokenization with the tokenizer's default one (main_analyze_s2orc.py:272, :282:
+ * len(dp_tokenize(x)) against len(llama_tokenizer.encode(x)); main_biomed_translation.py:74 the same for BLOOM).  Both
+ * defaults are greedy BPE merges over the words of atoms the device pre-tokenizers already produce, so one rule and one
+ * table serve both: every atom becomes the id of the token with exactly its bytes, and within each word the symbols
+ * merge until no adjacent pair is in the pair table, each step merging the adjacent pair of lowest (rank, position).
+ * Nothing merges across a word start.  (Merging every local minimum of a word at once is NOT this rule: with (p,q)->P
+ * at rank 0, (P,r)->Q at rank 1 and (r,s)->R at rank 2 the word p q r s gives [Q, s], not [P, R].)
+ *
+ * dpt_bpe_create: entry k says that the adjacent symbols left[k], right[k] may merge into merged[k]; the lowest rank
+ * merges first, equal ranks on different pairs are allowed (the leftmost pair wins).  DPT_E_ARG for a null pointer,
+ * n_pairs = 0 or >= 2^31, a negative id, a (left, right) key given twice, or the rank 0xFFFFFFFF (a miss's value).
+ * The object is immutable and may be shared by threads and streams.  On the device it is a hash keyed by the 64-bit
+ * pair with the value {merged, rank}: 32 bytes per pair (16-byte entries, load 0.5), two buckets per key and never a
+ * probe chain.
+ *
+ * dpt_bpe_encode: text, n_bytes, str_off, cut_mask, n_str exactly as dpt_encode's DPT_MODE_ATOMS input (cut_mask bit 1
+ * where an atom starts, bit 0 where a word starts; str_off[0] need not be 0; no alignment is assumed; strings < 4 GiB,
+ * str_off monotone; a string's first byte opens a word whatever its mask says).  Output in dpt_encode_padded's layout,
+ * so dpt_collate and the adapters read it as they read the DP's ids: ids[str_off[s] - str_off[0] + k] for
+ * k < counts[s], tok_word (nullable) at the same index = the 0-based word of token k within the string; status[s] =
+ * 0, or DPT_STATUS_NO_TOKENIZATION with counts[s] = 0 when some atom is no token of v (slots of such a string may
+ * hold anything); an empty string gives count 0 and status 0.  ids_cap >= n_bytes is required.  Words of any length are
+ * exact: words of up to 256 atoms merge in LDS, a longer word that does not fit there merges in place in the
+ * string's own output slots (slow; no workspace).
+ * DEVICE pointers on the device of b and v (the same one).  Stream-ordered on hip_stream, never synchronises,
+ * allocates nothing and needs no dpt_ctx and no host state: any number of calls may be in flight.  Every store stays
+ * inside the string's own [str_off[s], str_off[s+1]) slots of ids / tok_word and its own counts / status entry,
+ * whatever the mask holds.  DPT_E_ARG, before any device work, for a null pointer (tok_word excepted) or
+ * ids_cap < n_bytes; n_str == 0 launches nothing.
+ */
+typedef struct dpt_bpe dpt_bpe;
+int dpt_bpe_create(const int32_t *left, const int32_t *right, const int32_t *merged, const uint32_t *rank,
+                   uint64_t n_pairs, int device, dpt_bpe **out);
+int dpt_bpe_destroy(dpt_bpe *b);
+int dpt_bpe_encode(const dpt_bpe *b, const dpt_vocab *v, const uint8_t *text, uint64_t n_bytes,
+                   const uint64_t *str_off, const uint8_t *cut_mask, uint64_t n_str, int32_t *ids, uint64_t ids_cap,
+                   uint64_t *counts, int32_t *status, uint32_t *tok_word, void *hip_stream);
+/* TEST-ONLY, needs no device.  Builds the bytes dpt_bpe_create would upload for its first five arguments and answers
+ * the n_q queries (q_left[k], q_right[k]) from those bytes through the probe function the kernel runs:
+ * out_merged[k], out_rank[k], or -1 and 0xFFFFFFFF for a pair that is not in the table.  DPT_E_ARG as
+ * dpt_bpe_create, or for a null query / result array with n_q > 0. */
+int dpt_debug_bpe_lookup(const int32_t *left, const int32_t *right, const int32_t *merged, const uint32_t *rank,
+                         uint64_t n_pairs, const int32_t *q_left, const int32_t *q_right, uint64_t n_q,
+                         int32_t *out_merged, uint32_t *out_rank);
 
 /*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
