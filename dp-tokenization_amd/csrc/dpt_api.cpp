@@ -622,6 +622,58 @@ int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint6
     return DPT_OK;
 }
 
+// The checks both word-compare calls make of their sides, flags and n_str; 0 with p's common members filled.
+static int words_args(dpt::WordsLaunch *p, const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags,
+                      int32_t *wc_status) {
+    if (!a) return fail(DPT_E_ARG, "null a");
+    if (!b) return fail(DPT_E_ARG, "null b");
+    if (!a->off) return fail(DPT_E_ARG, "null a->off");
+    if (!a->tok_word) return fail(DPT_E_ARG, "null a->tok_word");
+    if (!b->off) return fail(DPT_E_ARG, "null b->off");
+    if (!b->tok_word) return fail(DPT_E_ARG, "null b->tok_word");
+    if (flags == 0 || (flags & ~(DPT_WORDS_LESS | DPT_WORDS_GREATER))) return fail(DPT_E_ARG, "flags: DPT_WORDS_LESS and / or DPT_WORDS_GREATER");
+    if (n_str >= (1ull << 31)) return fail(DPT_E_ARG, "n_str over 2^31 - 1");
+    if (!wc_status) return fail(DPT_E_ARG, "null wc_status");
+    p->a = *a; p->b = *b; p->n_str = n_str; p->flags = flags; p->wc_status = wc_status;
+    return DPT_OK;
+}
+
+static int words_launch(const dpt::WordsLaunch &p, void *hip_stream) {
+    if (p.n_str == 0) return DPT_OK;
+    const hipError_t e = dpt::launch_words(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "word compare launch");
+    return DPT_OK;
+}
+
+int dpt_word_compare_sizes(const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags, uint32_t *n_words,
+                           uint32_t *n_sel, uint32_t *len_a, uint32_t *len_b, int32_t *wc_status, void *hip_stream) {
+    dpt::WordsLaunch p{};
+    if (const int rc = words_args(&p, a, b, n_str, flags, wc_status)) return rc;
+    if (!n_words) return fail(DPT_E_ARG, "null n_words");
+    if (!n_sel) return fail(DPT_E_ARG, "null n_sel");
+    p.write = false;
+    p.n_words = n_words; p.n_sel = n_sel; p.len_a = len_a; p.len_b = len_b;
+    return words_launch(p, hip_stream);
+}
+
+int dpt_word_compare_write(const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags, const uint64_t *word_off,
+                           uint32_t *cnt_a, uint32_t *cnt_b, const uint64_t *sel_off, uint32_t *sel_str, uint32_t *sel_word,
+                           uint32_t *sel_begin, uint32_t *sel_end, uint32_t *sel_a_first, uint32_t *sel_a_count,
+                           uint32_t *sel_b_first, uint32_t *sel_b_count, int32_t *wc_status, void *hip_stream) {
+    dpt::WordsLaunch p{};
+    if (const int rc = words_args(&p, a, b, n_str, flags, wc_status)) return rc;
+    const int n_word_args = (word_off != nullptr) + (cnt_a != nullptr) + (cnt_b != nullptr);
+    if (n_word_args != 0 && n_word_args != 3) return fail(DPT_E_ARG, "word_off, cnt_a and cnt_b go together");
+    const bool any_sel = sel_str || sel_word || sel_begin || sel_end || sel_a_first || sel_a_count || sel_b_first || sel_b_count;
+    if (any_sel && !sel_off) return fail(DPT_E_ARG, "null sel_off");
+    if ((sel_begin || sel_end) && !a->tok_end) return fail(DPT_E_ARG, "sel_begin / sel_end need a->tok_end");
+    p.write = true;
+    p.word_off = word_off; p.cnt_a = cnt_a; p.cnt_b = cnt_b;
+    p.sel_off = sel_off; p.sel_str = sel_str; p.sel_word = sel_word; p.sel_begin = sel_begin; p.sel_end = sel_end;
+    p.sel_a_first = sel_a_first; p.sel_a_count = sel_a_count; p.sel_b_first = sel_b_first; p.sel_b_count = sel_b_count;
+    return words_launch(p, hip_stream);
+}
+
 int dpt_ctx_set_histogram_ex(dpt_ctx *c, int64_t *hist, uint32_t n_bins, int flags) {
     if (!c) return fail(DPT_E_ARG, "null ctx");
     if (hist && (n_bins < 2 || n_bins > DPT_HIST_MAX_BINS)) return fail(DPT_E_ARG, "n_bins outside 2..DPT_HIST_MAX_BINS");

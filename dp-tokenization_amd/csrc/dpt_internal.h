@@ -1,6 +1,6 @@
 // Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp,
 // dpt_pretok.cpp, dpt_bytelevel.cpp, dpt_bpe.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip,
-// dpt_collate.hip, dpt_pretok.hip, dpt_bytelevel.hip, dpt_bpe.hip).
+// dpt_collate.hip, dpt_pretok.hip, dpt_bytelevel.hip, dpt_bpe.hip, dpt_words.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -354,6 +354,27 @@ struct CollatePairLaunch {     // rows of two segments
     uint32_t *b_start;         // nullable
 };
 hipError_t launch_collate_pair(const CollatePairLaunch &p, hipStream_t stream);
+
+// One launch of the per-word comparison kernel (dpt_words.hip; include/dpt.h dpt_word_compare_sizes,
+// dpt_word_compare_write): every pointer a device pointer, the arguments already checked.
+struct WordsLaunch {
+    bool write;                  // false: the sizes pass
+    dpt_word_side a, b;
+    uint64_t n_str;
+    int flags;                   // DPT_WORDS_LESS | DPT_WORDS_GREATER
+    // sizes
+    uint32_t *n_words, *n_sel;
+    uint32_t *len_a, *len_b;     // nullable
+    // write
+    const uint64_t *word_off;    // nullable with cnt_a / cnt_b
+    uint32_t *cnt_a, *cnt_b;
+    const uint64_t *sel_off;     // nullable when every sel_* is
+    uint32_t *sel_str, *sel_word, *sel_begin, *sel_end;           // nullable, each
+    uint32_t *sel_a_first, *sel_a_count, *sel_b_first, *sel_b_count;
+    // both
+    int32_t *wc_status;
+};
+hipError_t launch_words(const WordsLaunch &p, hipStream_t stream);
 
 // Pre-tokenization table of a vocabulary (dpt_pretok.cpp build_pretok_tables; include/dpt.h dpt_pretok_create), as
 // host bytes exactly as dpt_pretok_create uploads them.

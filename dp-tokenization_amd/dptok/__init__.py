@@ -9,6 +9,8 @@ Public surface:
     collate                 padded model inputs from an encoded batch, on the device (collate.py: the
                             ``collate_device`` / ``model_inputs`` calls and their source + target forms
                             ``collate_pair_device`` / ``pair_model_inputs``; imported on demand, it needs torch)
+    words                   two tokenizations of a batch compared word by word, on the device (words.py:
+                            ``compare_device`` / ``selected_ids``; imported on demand, it needs torch)
     pack_strings, TokenSpans  host arrays in and out of the engine (pack.py, pure numpy)
     dp_tokenize_batch       List[str] -> List[List[int]] for a t2i vocabulary
     synth                   synthetic vocabularies/corpora of the BASELINE configs

@@ -56,6 +56,15 @@ class CollateSide(ctypes.Structure):
     _fields_ = [("ids", ctypes.c_void_p), ("off", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class WordSide(ctypes.Structure):
+    """dpt_word_side: device addresses (0 = NULL)"""
+    _fields_ = [("off", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("status", ctypes.c_void_p), ("tok_word", ctypes.c_void_p),
+                ("tok_end", ctypes.c_void_p)]
+
+
+WORDS_LESS, WORDS_GREATER = 1, 2
+
+
 class CollatePairOpts(ctypes.Structure):
     """dpt_collate_pair_opts"""
     _fields_ = [("row_len", ctypes.c_uint32), ("row_stride", ctypes.c_uint64), ("pad_id", ctypes.c_int32),
@@ -140,6 +149,9 @@ CALLS = {
     "dpt_bpe_destroy": (I32, [P]),
     "dpt_bpe_encode": (I32, [P, P, P, U64, P, P, U64, P, U64, P, P, P, P]),
     "dpt_debug_bpe_lookup": (I32, [P, P, P, P, U64, P, P, U64, P, P]),
+    # the two tokenizations compared word by word
+    "dpt_word_compare_sizes": (I32, [ctypes.POINTER(WordSide), ctypes.POINTER(WordSide), U64, I32, P, P, P, P, P, P]),
+    "dpt_word_compare_write": (I32, [ctypes.POINTER(WordSide), ctypes.POINTER(WordSide), U64, I32] + [P] * 14),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -162,6 +174,9 @@ OPTIONAL_BYTELEVEL = set(BYTELEVEL_CALLS)
 # And the BPE calls, with the pre-tokenization call that makes their llama input; ``bpe.Bpe`` raises without them (has_bpe).
 BPE_CALLS = {name: CALLS[name][1] for name in CALLS if "_bpe_" in name or name == "dpt_pretok_write_atoms"}
 OPTIONAL_BPE = set(BPE_CALLS)
+# And the word-compare calls; ``words.compare_device`` raises without them (has_words).
+WORDS_CALLS = {name: CALLS[name][1] for name in CALLS if "_word_compare_" in name}
+OPTIONAL_WORDS = set(WORDS_CALLS)
 
 
 def lib():
@@ -181,7 +196,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL | OPTIONAL_BPE and not hasattr(L, name):
+        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL | OPTIONAL_BPE | OPTIONAL_WORDS and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -221,6 +236,12 @@ def has_bpe() -> bool:
     """The loaded library exports the BPE calls."""
     L = lib()
     return all(hasattr(L, name) for name in BPE_CALLS)
+
+
+def has_words() -> bool:
+    """The loaded library exports the word-compare calls."""
+    L = lib()
+    return all(hasattr(L, name) for name in WORDS_CALLS)
 
 
 def wave_grid(n_str: int, waves: int = 4) -> int:

@@ -27,8 +27,10 @@ MI355X engine.  Same names, argument meaning and error behaviour:
   ``[tokenizer.encode(t) for t in texts]`` with the certified strings pre-tokenized and BPE-merged on the GPU
   (dptok/bpe.py; include/dpt.h dpt_bpe_encode) -- and ``dp_tokenize.batch_compare(List[str])``, the lengths and per-word
   token counts of the shortest tokenization next to the default one (reference main_analyze_s2orc.py:269-297,
-  main_biomed_translation.py:74-77).  Construction checks a probe list against ``tokenizer.encode`` and leaves both off,
-  with the reason in ``dp_tokenize.pretok_stats.default_off``, when they disagree.
+  main_biomed_translation.py:74-77); with ``words=True`` also which words improve and their tokens on both sides, found
+  on the device (dptok/words.py; reference main_analyze_s2orc.py:277-290).  Construction checks a probe list against
+  ``tokenizer.encode`` and leaves both off, with the reason in ``dp_tokenize.pretok_stats.default_off``, when they
+  disagree.
 * ``dp_tokenize.batch(List[str]) -> List[List[int]]``: the batched form (one GPU launch, in both
   modes).
 * ``dp_tokenize.batch_spans(List[str]) -> List[TokenSpans]``: the batch's ids aligned to the text --
@@ -587,12 +589,14 @@ def _device_pretokenizer(tokenizer, t2i, engine, host, merge_words):
     pretok = Pretok(t2i, inverse[bos] if bos is not None else "", literals, _device())
     presplit, *paths, stats = _device_split_paths(pretok.presplit, "presplit", engine, host.pack)
     stats.split_atoms = lambda d_text, d_offs: pretok.presplit(d_text, d_offs, atoms=True)   # (_default_surface)
+    stats.dp_form = (pretok.presplit, "presplit")
     _probe_check(presplit, stats, PROBES, merge_words, 0xFF, True,
                  "tokenizer is not one the rule holds for (a normalising model, other added-token behaviour)")
     return (*paths, stats)
 
 
-def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab, probes, empty_ids, host_only, stats):
+def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab, probes, empty_ids, host_only, stats,
+                     dp_form, dp_pieces, default_pieces):
     """``dp_tokenize.batch_default`` and ``dp_tokenize.batch_compare``: the tokenizer's own ids made on the device
     (dptok/bpe.py; the rule: include/dpt.h dpt_bpe_encode) next to the shortest tokenization -- the comparison the
     reference drivers exist for (main_analyze_s2orc.py:269-297, main_biomed_translation.py:74-77).
@@ -600,6 +604,9 @@ def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab,
     ``split_atoms(d_text, d_offs)`` -> the device ATOMS form (text2, offs2, cut, pre_status); ``make_table()`` -> the
     pair table's four arrays by the route the tokenizer object offers; ``bpe_vocab`` the ``Vocab`` whose ids are the
     tokenizer's; ``host_only(text)``: the text must go to the host tokenizer whatever the device rule says.
+    ``dp_form`` = (split, mode): ``split(d_text, d_offs)`` -> the device form the DP runs on and its engine mode -- the
+    same text as ``split_atoms``' with the words starting at the same bytes; ``dp_pieces`` / ``default_pieces``: id ->
+    token string of the DP's and of the tokenizer's ids (``batch_compare(words=True)``).
     Construction runs ``probes`` through ``batch_default`` against ``tokenizer.encode``; when they disagree, when
     ``tokenizer.encode("")`` is not ``empty_ids`` or when the table cannot be built, both attributes stay off and
     ``stats.default_off`` says why (None: they are on)."""
@@ -640,23 +647,87 @@ def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab,
         got, _ = device_default(texts, False)
         return [g if g is not None else host_encode(t) for g, t in zip(got, texts)]
 
-    def batch_compare(texts: Sequence[str]) -> dict:
+    def device_words(texts):
+        """Per string the words with fewer DP tokens than default tokens, found on the device (dptok/words.py): (their
+        indices, their DP ids word by word, their default ids word by word), or None for a string the device does not
+        take.  Both encodings, the spans and the comparison run back to back on the two device forms of the batch;
+        only the per-string sizes, the selected words' records and their gathered ids come back."""
+        from dptok import words as wcmp
+        from dptok._lib import STATUS_INTERNAL
+        out = [None] * len(texts)
+        take = [i for i, t in enumerate(texts) if not host_only(t)]
+        if not take:
+            return out
+        text, offs = pack_strings([texts[i] for i in take])
+        n, engine = len(take), dp_tokenize.engine
+        split_dp, dp_mode = dp_form
+        with torch.cuda.device(dev):
+            d_text, d_offs = torch.from_numpy(text.copy()).to(dev), torch.from_numpy(offs.view(np.int64)).to(dev)
+            text_b, offs_b, cut_b, pre_b = split_atoms(d_text, d_offs)
+            text_a, offs_a, cut_a, pre_a = (text_b, offs_b, cut_b, pre_b) if split_dp == split_atoms else split_dp(d_text, d_offs)
+            nb = int(text_a.numel())
+            if nb != int(text_b.numel()):
+                raise DptError("batch_compare: the two device forms of the batch differ in length")
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ids, tok_end, tok_word = (torch.empty(max(nb, 1), dtype=torch.int32, device=dev) for _ in range(3))
+            id_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            st, sst = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+            text_ptr, cut_ptr = (text_a.data_ptr(), cut_a.data_ptr()) if nb else (ids.data_ptr(), ids.data_ptr())
+            engine.encode_device(text_ptr, nb, offs_a.data_ptr(), n, ids.data_ptr(), max(nb, 1), id_off.data_ptr(), st.data_ptr(),
+                                 cut_ptr=cut_ptr, stream=stream, mode=dp_mode)
+            engine.spans_device(text_ptr, nb, offs_a.data_ptr(), n, ids.data_ptr(), id_off.data_ptr(), st.data_ptr(), tok_end.data_ptr(),
+                                sst.data_ptr(), tok_word_ptr=tok_word.data_ptr(), cut_ptr=cut_ptr, stream=stream, mode=dp_mode)
+            b_ids, b_cnt, b_st, b_word = bpe.encode_atoms(bpe_vocab, text_b, offs_b, cut_b, tok_word=True)
+            # a refused string keeps its pre-tokenization status; one with nothing to tokenize has no words on either side
+            nothing = torch.diff(offs_a) == 0
+            st_a = torch.where(pre_a != 0, pre_a, torch.where(nothing, torch.zeros_like(sst), sst))
+            st_b = torch.where(pre_b != 0, pre_b, b_st)
+            r = wcmp.compare_device(wcmp.Side(id_off, tok_word, status=st_a, tok_end=tok_end),
+                                    wcmp.Side(offs_b, b_word, counts=b_cnt, status=st_b), wcmp.WORDS_LESS)
+            a_sel, a_off = wcmp.selected_ids(ids, id_off, None, r.sel_str, r.sel_a_first, r.sel_a_count)
+            b_sel, b_off = wcmp.selected_ids(b_ids, offs_b, b_cnt, r.sel_str, r.sel_b_first, r.sel_b_count)
+            status, sel_off, sel_word, a_sel, a_off, b_sel, b_off = (x.cpu().numpy() for x in (r.status, r.sel_off, r.sel_word, a_sel, a_off,
+                                                                                                b_sel, b_off))
+        if (status == STATUS_INTERNAL).any():
+            k = int(np.flatnonzero(status == STATUS_INTERNAL)[0])
+            raise DptError("batch_compare: the two tokenizations of %r do not number the same words" % texts[take[k]][:60])
+        a_sel, b_sel, sel_word, so, ao, bo = a_sel.tolist(), b_sel.tolist(), sel_word.tolist(), sel_off.tolist(), a_off.tolist(), b_off.tolist()
+        for k, i in enumerate(take):
+            if status[k] == 0:
+                q = range(so[k], so[k + 1])
+                out[i] = (sel_word[so[k]:so[k + 1]], [a_sel[ao[d]:ao[d + 1]] for d in q], [b_sel[bo[d]:bo[d + 1]] for d in q])
+        return out
+
+    def batch_compare(texts: Sequence[str], words: bool = False) -> dict:
         """The shortest tokenization against the tokenizer's own, per string: ``dp_lengths`` and ``default_lengths``
         (int64 arrays: the ``len`` of ``dp_tokenize.batch`` and of ``tokenizer.encode``), ``improved`` (the mask
         dp < default), and ``dp_word_counts`` / ``default_word_counts``: per string the tokens in each word of its
         pre-tokenization (bincounts of the word index of every token; the default side's is None for a string that went
         to the host tokenizer).  The reference's per-word step re-encodes each word as a text of its own, which adds a
-        BOS and a dummy prefix to both sides; here the words are compared in place, inside their string."""
+        BOS and a dummy prefix to both sides; here the words are compared in place, inside their string.
+
+        ``words=True`` adds, per string, the words the shortest tokenization improves -- the reference's per-word step
+        (main_analyze_s2orc.py:277-290) for the whole batch, found on the device by one streaming comparison of the two
+        word-index streams: ``improved_word_ids`` (the words with fewer DP tokens than default tokens, ascending),
+        ``improved_tokens`` (per improved word the DP's token strings) and ``worse_tokens`` (the default's, of the same
+        words) -- the reference frame's two columns, ``[]`` for a string without an improved word and None for a string
+        that went to the host tokenizer on either side.  Every other key holds what it holds without it."""
         texts = list(texts)
         spans = dp_tokenize.batch_spans(texts)
-        got, words = device_default(texts, True)
+        got, default_words = device_default(texts, True)
         default = [g if g is not None else host_encode(t) for g, t in zip(got, texts)]
         dp_len = np.array([len(s.ids) for s in spans], dtype=np.int64)
         df_len = np.array([len(d) for d in default], dtype=np.int64)
         dp_words = [np.bincount(np.asarray(s.word_ids, dtype=np.int64)) if s.word_ids else np.zeros(0, dtype=np.int64) for s in spans]
-        df_words = [None if w is None else np.bincount(w.astype(np.int64)) if len(w) else np.zeros(0, dtype=np.int64) for w in words]
-        return {"dp_lengths": dp_len, "default_lengths": df_len, "improved": dp_len < df_len, "dp_word_counts": dp_words,
-                "default_word_counts": df_words}
+        df_words = [None if w is None else np.bincount(w.astype(np.int64)) if len(w) else np.zeros(0, dtype=np.int64) for w in default_words]
+        out = {"dp_lengths": dp_len, "default_lengths": df_len, "improved": dp_len < df_len, "dp_word_counts": dp_words,
+               "default_word_counts": df_words}
+        if words:
+            found = device_words(texts)
+            out["improved_word_ids"] = [None if f is None else f[0] for f in found]
+            out["improved_tokens"] = [None if f is None else [[dp_pieces[i] for i in w] for w in f[1]] for f in found]
+            out["worse_tokens"] = [None if f is None else [[default_pieces[i] for i in w] for w in f[2]] for f in found]
+        return out
 
     try:
         bpe = Bpe(*make_table(), device=_device())
@@ -778,7 +849,8 @@ def dp_tokenize_llama(llama_tokenizer, pretokenize_option="llama", device_pretok
         from dptok.pretok_probes import PROBES
         bos = _bos_id(llama_tokenizer)
         _default_surface(dp_tokenize, llama_tokenizer, pretok_stats.split_atoms, lambda: _llama_pairs(llama_tokenizer, t2i),
-                         engine.vocab, PROBES, [] if bos is None else [bos], lambda t: False, pretok_stats)
+                         engine.vocab, PROBES, [] if bos is None else [bos], lambda t: False, pretok_stats,
+                         pretok_stats.dp_form, vocab_bidict.inverse, vocab_bidict.inverse)
     return pair
 
 
@@ -845,6 +917,7 @@ def _device_bytelevel(tokenizer, vocab_to_index, engine, host_pack, pretokenize)
     splitter = ByteLevelSplit(BLOOM_SEPARATORS, _device())
     presplit, *paths, stats = _device_split_paths(splitter.split, "atoms", engine, host_pack)
     stats.split_atoms = splitter.split   # (_default_surface)
+    stats.dp_form = (splitter.split, "atoms")
     _probe_check(presplit, stats, PROBES, pretokenize, 1, False, "pre-tokenizer is not the one the rule holds for")
     return (*paths, stats)
 
@@ -947,5 +1020,6 @@ def dp_tokenize_bloom(bloom_tokenizer, HF_CACHE_DIR, device_pretokenize=False):
         same_ids = all(real[t] == i for i, t in enumerate(real))
         _default_surface(dp_tokenize, bloom_tokenizer, pretok_stats.split_atoms, make_table,
                          engine.vocab if same_ids else Vocab(dict(real), _device()), PROBES, [],
-                         lambda t: any(x in t for x in literals), pretok_stats)
+                         lambda t: any(x in t for x in literals), pretok_stats, pretok_stats.dp_form, vocab_to_index.inverse,
+                         vocab_to_index.inverse if same_ids else {i: t for t, i in real.items()})
     return pair

@@ -649,6 +649,67 @@ int dpt_debug_bpe_lookup(const int32_t *left, const int32_t *right, const int32_
                          int32_t *out_merged, uint32_t *out_rank);
 
 /*
+ * Two tokenizations of a batch compared word by word on the device.  Added within ABI 6 (DPT_ABI_VERSION unchanged).
+ * The reference's S2ORC probe lists, for every abstract the shortest tokenization improves, the improved words and
+ * their tokens on both sides (main_analyze_s2orc.py:277-290, the improved_tokens / worse_tokens columns of its
+ * frame).  Both word-index streams are already on the device -- dpt_token_spans writes tok_word / tok_end for the DP
+ * ids, dpt_bpe_encode tok_word for the default ids -- so the answer is a short list of records and only those leave
+ * the GPU.  Two calls in the manner of dpt_decode_sizes -> dpt_decode: the sizes, the caller's two prefix sums, the
+ * write.
+ *
+ * A side is one tokenization by word, in either layout, each side independently: off / counts / status as
+ * dpt_collate_side's (counts NULL: off is an id_off and n = off[s+1] - off[s]; else off is a str_off and
+ * n = counts[s]), tok_word and tok_end at off[s] - off[0] + k for token k < n of string s (n < 2^32; a side with
+ * more is malformed).  The rule is defined on the values alone.  For string s and side X with the word values
+ * w_0..w_{n-1}:
+ *   validity   X is well-formed when n == 0, or w_0 == 0 and every w_k - w_{k-1} is 0 or 1; its word count W_X is
+ *              then w_{n-1} + 1 (0 when n == 0), the count of word w the length of its run of equal values and
+ *              first(w) the token index where the run starts.
+ *   wc_status[s] = status_a[s] when non-zero, else status_b[s] when non-zero, else DPT_STATUS_INTERNAL when a side
+ *              is malformed or W_a != W_b, else 0 (pre-tokenization values such as DPT_PRETOK_NEEDS_HOST pass
+ *              through a side's status).
+ *   len_a[s], len_b[s] (nullable) = that side's n when that side's own status is 0, else 0.
+ *   n_words[s] = W_a and n_sel[s] = the words the flags select when wc_status[s] == 0, else both 0.  DPT_WORDS_LESS
+ *              selects cnt_a(w) < cnt_b(w), DPT_WORDS_GREATER cnt_a(w) > cnt_b(w), both flags !=.
+ * dpt_word_compare_write takes the exclusive prefix sums of n_words and n_sel as word_off and sel_off (n_str + 1
+ * entries each; entry 0 need not be 0).  word_off, cnt_a and cnt_b are nullable together; the sel_* arrays are
+ * nullable one by one, sel_off with all of them.  For a string of status 0:
+ *   cnt_a, cnt_b at word_off[s] - word_off[0] + w = the two counts of word w;
+ *   the selected words in ascending w at sel_off[s] - sel_off[0] + d: sel_str = s, sel_word = w, sel_a_first /
+ *   sel_a_count / sel_b_first / sel_b_count = first(w) and the count on each side, token indices within the string
+ *   (no id is read: the caller gathers them), sel_begin / sel_end = a->tok_end of the last token of word w - 1 (0
+ *   for w = 0) and of word w: the word's bytes in the text dpt_token_spans was given (RAW's leading ' ' included).
+ * Every store of write stays inside the string's own [word_off[s], word_off[s+1]) and [sel_off[s], sel_off[s+1]),
+ * whatever the inputs hold; a string whose derived counts do not fill those ranges exactly gets
+ * DPT_STATUS_INTERNAL and unspecified contents in its own ranges only; a string of non-zero status gets nothing
+ * but the status.
+ * DPT_E_ARG, before any device work (also with n_str == 0): null a, b, off or tok_word of a side, a null n_words,
+ * n_sel or wc_status, word_off / cnt_a / cnt_b not all given or all null, a sel_* array without sel_off, sel_begin
+ * or sel_end with a null a->tok_end, flags 0 or with unknown bits, n_str >= 2^31.  n_str == 0 launches nothing.
+ * DEVICE pointers on the current device; stream-ordered on hip_stream, never synchronises, allocates nothing and
+ * needs no dpt_ctx and no vocabulary: any number of calls may be in flight.  No host-buffer form.
+ */
+typedef struct {             /* one tokenization of the batch, by word */
+    const uint64_t *off;      /* n_str + 1 entries; off[0] need not be 0, tok_word / tok_end correspond to it */
+    const uint64_t *counts;   /* nullable, as dpt_collate_side: NULL -> n = off[s+1]-off[s]; else n = counts[s] */
+    const int32_t  *status;   /* nullable: all 0 */
+    const uint32_t *tok_word; /* word index of token k of string s at off[s]-off[0]+k */
+    const uint32_t *tok_end;  /* nullable; side a's is read for the word byte spans */
+} dpt_word_side;
+#define DPT_WORDS_LESS    1   /* select the words with fewer tokens on a than on b */
+#define DPT_WORDS_GREATER 2   /* ... with more */
+int dpt_word_compare_sizes(const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags,
+                           uint32_t *n_words, uint32_t *n_sel, uint32_t *len_a, uint32_t *len_b,
+                           int32_t *wc_status, void *hip_stream);
+int dpt_word_compare_write(const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags,
+                           const uint64_t *word_off, uint32_t *cnt_a, uint32_t *cnt_b,
+                           const uint64_t *sel_off, uint32_t *sel_str, uint32_t *sel_word,
+                           uint32_t *sel_begin, uint32_t *sel_end,
+                           uint32_t *sel_a_first, uint32_t *sel_a_count,
+                           uint32_t *sel_b_first, uint32_t *sel_b_count,
+                           int32_t *wc_status, void *hip_stream);
+
+/*
  * Fold the token-count histogram of dpt_token_histogram into the NEXT dpt_encode call on this ctx
  * (dpt_encode only: dpt_encode_host, dpt_encode_padded and dpt_dp_host* leave it armed; a dpt_encode
  * that fails still consumes it)
