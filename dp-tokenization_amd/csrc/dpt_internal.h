@@ -1,6 +1,7 @@
 // Internal interface between the C-ABI (dpt_api.cpp), the host table builders (dpt_vocab.cpp, dpt_detok.cpp,
-// dpt_pretok.cpp, dpt_bytelevel.cpp, dpt_bpe.cpp) and the kernels (dpt_kernels.hip, dpt_spans.hip, dpt_decode.hip,
-// dpt_collate.hip, dpt_pretok.hip, dpt_bytelevel.hip, dpt_bpe.hip, dpt_words.hip).
+// dpt_pretok.cpp, dpt_bytelevel.cpp, dpt_bpe.cpp) and the kernels (the dpt_kernels.hip unit -- that file with
+// dpt_long.hip and dpt_tok_*.h -- and dpt_spans.hip, dpt_decode.hip, dpt_collate.hip, dpt_pretok.hip,
+// dpt_bytelevel.hip, dpt_bpe.hip, dpt_words.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -110,7 +111,7 @@ struct EncodeLaunch {
     int32_t ws_node, ws_base, ws_id;   // the trie node after U+2581, its base word and id (-1: none)
 };
 
-// first-pass work partitions (dpt_kernels.hip tokenize_kernel): up to NPART_MAX counters, one per
+// first-pass work partitions (dpt_kernels.hip, TokPass::body): up to NPART_MAX counters, one per
 // PART_STRIDE uint32 (a 256-byte line each), from byte PART_CTR_OFFSET of the counter block, then the
 // used-up mask; the counter block is CTR_ALLOC_BYTES long (the host path copies its first 64 bytes)
 constexpr unsigned NPART_MAX = 32;
@@ -164,8 +165,8 @@ __host__ __device__ inline unsigned child_bit(unsigned b) { return (b ^ (b >> 5)
 // dwords, zero past its length, plus the length.  Buckets of two {fp, id} entries (fp != 0; 0 marks a
 // free entry), two choices per key (cuckoo placement, round 5): bucket h & mask or its partner
 // tokhash_alt(h & mask, fp).  The kernels load a key's home bucket first and its partner only when the
-// key is not in its home bucket (one more load round for the wave, never a chain; DPT_HASH_BOTH=1 in
-// dpt_kernels.hip loads both at once -- measured slower on cfg2 / cfg5, round 5 r05aj) -- a lookup never
+// key is not in its home bucket (one more load round for the wave, never a chain; loading both
+// at once for every key measured slower on cfg2 / cfg5, round 5 r05aj, and is gone) -- a lookup never
 // walks a probe chain (with linear probing 5.7 % of cfg4's hashed tokens were not in their home bucket,
 // and almost every 64-token round ran the serial probe loop for some lane).  The builder checks that the first entry carrying a key's
 // fp among its two buckets (in the kernel's order) is its own (else it re-seeds): a span the DP

@@ -38,6 +38,19 @@
 // Strings are claimed from 16 partition counters (see tokenize_kernel).  Strings whose single word
 // exceeds CH bytes are re-run by the 2048-byte, one-string-per-wave instantiation, longer ones by
 // the unbounded pass (dpt_long.hip).  The finish kernel turns the staging rows into CSR ids.
+//
+// One translation unit.  What the kernels read but a change to them seldom edits is in headers:
+//   dpt_wave.h         the wave primitives
+//   dpt_tok_knobs.h    every compile-time option of the unit: the numeric tunables and the diagnostics
+//   dpt_tok_lds.h      group geometry, a wave's LDS layout, trie access, the kernel arguments, the stamp macros
+// This file: window loading and prep, TokPass (the phases and the slot loop) with tokenize_kernel and
+// tokenize_lean_kernel, the finish / scan / reset / histogram kernels, the fallback and 512-byte kernels, the launch
+// plan, the choice -> instantiation tables, the launchers and the debug entry points.
+//
+// Compile-time options are numeric tunables and diagnostics only (dpt_tok_knobs.h; the diagnostics -- DPT_STOP,
+// DPT_C2STOP, DPT_DIAG_PREP, DPT_STAMPS, DPT_WSTAMPS -- give wrong results or extra counters by design and are
+// never in the product build).  The alternatives measured slower or neutral are gone from the source, the
+// losing sides of the decided A/B knobs included; DESIGN.md §9 lists them with their numbers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -49,384 +62,10 @@
 // the unbounded pass (namespace dpt::lng): one translation unit with fallback_kernel, which runs it
 // in the same launch as the 2048-byte pass
 #include "dpt_long.hip"
+#include "dpt_tok_knobs.h"
+#include "dpt_tok_lds.h"
 
 namespace dpt {
-
-// Compile-time options are diagnostics only (DPT_STOP, DPT_C2STOP, DPT_STAMPS: wrong results or extra
-// counters by design, never in the product build).  The alternatives measured slower or neutral are
-// gone from the source (the round-4 self-copy and pipelined CSR pass: git tag r04-experiments);
-// DESIGN.md §9 lists them with their numbers.
-
-// ------------------------------------------------------------------ wave primitives
-// (lane_id, uni, ballot, wave_incl_scan_add and wave_shift_in: dpt_wave.h, shared with dpt_long.hip and dpt_spans.hip)
-
-// inclusive max-scan over 64 lanes (values >= 0; the same DPP steps as the add scan)
-__device__ __forceinline__ unsigned wave_incl_scan_max(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, true));  // row_shr:1
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x112, 0xF, 0xF, true));  // row_shr:2
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x114, 0xF, 0xF, true));  // row_shr:4
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x118, 0xF, 0xF, true));  // row_shr:8
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false)); // row_bcast:15
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false)); // row_bcast:31
-    return v;
-}
-
-// min within each row of 16 lanes, result in every lane of the row
-// (mov_dpp with bound_ctrl lets hipcc fold each step into one v_min_u32_dpp)
-__device__ __forceinline__ unsigned row_min_u32(unsigned v) {
-    v = min(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v = min(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    v = min(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));  // row_half_mirror
-    v = min(v, (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));  // row_mirror
-    return v;
-}
-
-// min over 64 lanes, result uniform (SGPR)
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    v = row_min_u32(v);
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false)); // row_bcast:15
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false)); // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// lane l receives x[l-1]; the first lane of each row receives `in` (row_shr:1; the wave's: wave_shift_in)
-__device__ __forceinline__ unsigned row_shift_in(unsigned x, unsigned in) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)in, (int)x, 0x111, 0xF, 0xF, false);
-}
-
-// Lane-group shifts for lane-mode B: lane l of a group of LW lanes receives x of lane l + K (gshl) / l - K (gshr),
-// `fill` past the group's edge.  LW = 16: one DPP row op (row_shl / row_shr:K); LW = 64 (one string across the
-// wave, the one-string kernel): ds_bpermute.
-template <int LW, unsigned K>
-__device__ __forceinline__ unsigned gshl(unsigned x, unsigned fill) {
-    if constexpr (LW == 16) {
-        return (unsigned)__builtin_amdgcn_update_dpp((int)fill, (int)x, 0x100 | K, 0xF, 0xF, false);
-    } else {
-        const unsigned l = lane_id();
-        const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute((int)(((l + K) & 63u) << 2), (int)x);
-        return l + K < 64u ? v : fill;
-    }
-}
-template <int LW, unsigned K>
-__device__ __forceinline__ unsigned gshr(unsigned x, unsigned fill) {
-    if constexpr (LW == 16) {
-        return (unsigned)__builtin_amdgcn_update_dpp((int)fill, (int)x, 0x110 | K, 0xF, 0xF, false);
-    } else {
-        const unsigned l = lane_id();
-        const unsigned v = (unsigned)__builtin_amdgcn_ds_bpermute((int)(((l - K) & 63u) << 2), (int)x);
-        return l >= K ? v : fill;
-    }
-}
-
-// x behind an empty asm (no instruction): the optimizer cannot see through it, so a select on a loaded value is not
-// turned back into an exec-mask branch (a load that only one side of a select needs is sunk under a branch of its own)
-__device__ __forceinline__ unsigned opaque(unsigned x) {
-    asm("" : "+v"(x));
-    return x;
-}
-// max over the 64 lanes, wave-uniform (an SGPR): row_shr maxima, then the rows' last lanes
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true));
-    return uni(max(max((unsigned)__builtin_amdgcn_readlane((int)v, 15), (unsigned)__builtin_amdgcn_readlane((int)v, 31)),
-                   max((unsigned)__builtin_amdgcn_readlane((int)v, 47), (unsigned)__builtin_amdgcn_readlane((int)v, 63))));
-}
-
-// 64-bit inclusive add-scan over the wave (ds_bpermute shifts)
-__device__ __forceinline__ uint64_t wave_incl_scan_add64(uint64_t v, unsigned lane) {
-#pragma unroll
-    for (unsigned k = 1; k < 64; k <<= 1) {
-        const int src = (int)((lane >= k ? lane - k : lane) << 2);
-        const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)v);
-        const unsigned hi = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)(v >> 32));
-        v += lane >= k ? (((uint64_t)hi << 32) | lo) : 0ull;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t uni64(uint64_t x) {
-    return ((uint64_t)uni((unsigned)(x >> 32)) << 32) | uni((unsigned)x);
-}
-
-// lowest set bit (v_ffbl_b32: 0xFFFFFFFF for 0, no select needed where 0 cannot matter)
-__device__ __forceinline__ unsigned ffbl(unsigned x) {
-    unsigned r;
-    asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// ------------------------------------------------------------------ group geometry
-
-template <int G> struct Group;
-
-// G = 16: four strings per wave, one per DPP row.  Per atom: {cpos, ~span mask} in one
-// dword (after phase B the mask half of a word-end atom holds the word's final key, Wfin<16>,
-// and in C1 the mask halves take the selected tokens); per end position i, one u16 `fin`:
-// the back distances (minus one) of the largest reachable j in E(i) attaining G[i] (dg) and
-// of the largest reachable j in E(i) (de), 4 bits each.  Both exist at every position of a
-// valid word's selected path (Appendix A: a reachable i has a reachable j attaining its key),
-// and C1 walks valid words only, so no "none" code is stored.
-template <> struct Group<16> {
-    using M = uint16_t;
-    // smask: until phase B, the inverted END mask of end position i: bit d clear = atoms
-    // i-1-d .. i-1 are a token (phase A clears the bits with LDS atomics)
-    struct Rec { uint16_t cpos; uint16_t smask; };
-    struct Fin { uint8_t v; };   // dg | de << 4
-    static __device__ __forceinline__ unsigned dg(const Fin &x) { return x.v & 15u; }
-    static __device__ __forceinline__ unsigned de(const Fin &x) { return (x.v >> 4) & 15u; }
-};
-
-// G = 64: one string per wave (vocabularies with tokens of 17..64 code points).
-template <> struct Group<64> {
-    using M = uint64_t;
-    struct Rec { uint64_t smask; uint16_t cpos; uint16_t pad[3]; };
-    struct Fin { uint32_t d; uint32_t w; };   // w: the final key (Wfin<64>)
-    static __device__ __forceinline__ unsigned dg(const Fin &x) { return x.d & 127u; }
-    static __device__ __forceinline__ unsigned de(const Fin &x) { return (x.d >> 8) & 127u; }
-};
-
-// ------------------------------------------------------------------ LDS layout
-
-constexpr uint16_t CP_WS = 0x8000;        // cpos bit: atom starts a word
-constexpr unsigned MAX_ATOM_BYTES = 8;    // expanded atom = one u64 (raw: '▁'+4-byte code point = 7)
-
-// final state at a word end.  G = 16: 16 bits in the word-end atom's mask half:
-// cost << 6 | invalid << 5 | 31-G, straight from the key (its bits 10..14 are constant 1s);
-// cost 1023 = the uncapped DP's "inf" (0xFFFF, inspect_tokenizer.py:80), capped costs <= CH
-template <int G> struct Wfin;
-template <> struct Wfin<16> {
-    using T = uint16_t;
-    // one v_bfi: bits 5..15 from r >> 10, the rest from r (bits 16+ fall off in the u16)
-    static __device__ __forceinline__ T pack(unsigned r) {
-        unsigned o;
-        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(o) : "s"(0xFFE0u), "v"(r >> 10), "v"(r));
-        return (T)o;
-    }
-    static __device__ __forceinline__ unsigned cost(T x) { return (x >> 6) == 1023u ? 0xFFFFu : (x >> 6); }
-    static __device__ __forceinline__ bool invalid(T x) { return (x >> 5) & 1u; }
-    static __device__ __forceinline__ unsigned gmax(T x) { return 31u - (x & 31u); }
-};
-template <> struct Wfin<64> {
-    using T = uint32_t;   // the group-min key itself: cost<<16 | invalid<<15 | 0x7FFF-G
-    static __device__ __forceinline__ T pack(unsigned r) { return r; }
-    static __device__ __forceinline__ unsigned cost(T x) { return x >> 16; }
-    static __device__ __forceinline__ bool invalid(T x) { return (x >> 15) & 1u; }
-    static __device__ __forceinline__ unsigned gmax(T x) { return 0x7FFFu - (x & 0x7FFFu); }
-};
-
-// G = 64: rec[] as two arrays (span masks, code-point prefixes) -- 10 bytes per atom instead of the
-// 16 of an aligned struct, so LDS per wave (5.2 KB) holds more resident waves than the 24 that 80
-// VGPRs allow; rec[j] yields references to both fields, so the shared code reads L.rec[j].cpos alike
-template <int NA> struct RecSoA {
-    uint64_t sm[NA];
-    uint16_t cp[NA];
-    struct Ref { uint64_t &smask; uint16_t &cpos; };
-    struct CRef { const uint64_t &smask; const uint16_t &cpos; };
-    __device__ __forceinline__ Ref operator[](unsigned i) { return {sm[i], cp[i]}; }
-    __device__ __forceinline__ CRef operator[](unsigned i) const { return {sm[i], cp[i]}; }
-};
-
-template <int CH, int G>
-struct GroupLDS {
-    using M = typename Group<G>::M;
-    static constexpr int NA = CH + 2;            // atoms + sentinel
-    // rec[j]: code-point prefix of atom j (| CP_WS at word starts and at the window end) and the
-    //         span mask of tokens of 1..G atoms starting at j; after phase B the mask field holds
-    //         the first atom of selected token j (tokens tile the window)
-    std::conditional_t<(G == 64), RecSoA<NA>, typename Group<G>::Rec[NA]> rec;
-    typename Group<G>::Fin fin[NA];   // per end position, see Group<G>
-    // the final key of the word ending at atom e
-    __device__ __forceinline__ typename Wfin<G>::T wkey(unsigned e) const {
-        if constexpr (G == 16) return rec[e].smask;
-        else return fin[e].w;
-    }
-    // CH = 256: u8, stored mod 256 -- offsets and word starts are < 256; the sentinels (wlen,
-    // n_atoms <= 256) are recovered with modular differences (atom_len, word_end)
-    using Idx = std::conditional_t<(CH <= 256), uint8_t, uint16_t>;
-    // word -> first atom: in global scratch for 256-byte windows (WSLG; LDS is what limits the
-    // resident waves there), in LDS for the 2048-byte pass
-    static constexpr bool WSLG = CH <= 256;
-    static constexpr int WSL_STRIDE = (NA + 15) & ~15;
-    Idx aoff[NA];                   // atom -> byte offset in the window
-    Idx wsl[WSLG ? 1 : NA];
-    __device__ __forceinline__ unsigned atom_len(unsigned j) const { return (Idx)(aoff[j + 1] - aoff[j]); }
-    // word w's first atom / its end (= the next word's first atom, or n_atoms)
-    __device__ __forceinline__ unsigned word_start(const uint8_t *gw, unsigned w) const {
-        if constexpr (WSLG) return gw[w];
-        else return wsl[w];
-    }
-    __device__ __forceinline__ unsigned word_end(const uint8_t *gw, unsigned w) const {
-        if constexpr (WSLG) return (((unsigned)gw[w + 1] + 255u) & 0xFFu) + 1u;
-        else return wsl[w + 1];
-    }
-    __device__ __forceinline__ void set_word_start(uint8_t *gw, unsigned w, unsigned v) {
-        if constexpr (WSLG) gw[w] = (uint8_t)v;
-        else wsl[w] = (Idx)v;
-    }
-    // the window's input bytes (expanded on the fly); the dword reads of the last atoms run up to
-    // 12 bytes past the end, into the next group or the slot states -- masked off, never used
-    alignas(16) uint8_t bytes[CH];
-    // G = 64, 256-byte windows, non-raw modes (no expansions: a token's bytes are the window's): per byte
-    // position p <= wlen, byte[p] | BF_ATOM (an atom starts at p, or p == wlen) | BF_STOP (a word starts
-    // at p, or p == wlen) -- phase A's byte-stream walker reads ONE u16 per trie step
-    // (zero-length when unused: one spare byte here rounded the 16-lane group up 16 bytes -- 21 resident
-    // waves per CU instead of 22, and the slots' bank interleaving off; the static_assert below holds it)
-    static constexpr bool BSTREAM = G == 64 && CH == 256;
-    uint16_t bf[BSTREAM ? CH + 2 : 0];
-    // ... and per atom: 1 = it starts a word that is one vocabulary token (the whole-word shortcut)
-    uint8_t scf[BSTREAM ? CH + 2 : 0];
-};
-constexpr unsigned BF_ATOM = 0x100u, BF_STOP = 0x200u;
-
-// strings are < 4 GiB (dpt.h); abase: atoms of the string's earlier windows
-// (48 bytes: LDS per slot is what bounds the resident waves)
-struct SlotState {
-    uint64_t sb;
-    uint32_t s, slen, pos, ntok, capsum, wtok;
-    uint32_t abase;
-    uint16_t wlen, n_atoms, n_words;
-    uint8_t active, status, inval, capb;   // capb: some atom of the window is not a token by itself (the cap can bind)
-    uint8_t cpw;   // a '\u2581'-compressed PRESPLIT window (prep_window): raw mode's ASCII paths, no first-atom rule
-    uint8_t pad;
-};
-static_assert(sizeof(SlotState) == 48, "slot state layout");
-
-template <int CH, int G>
-constexpr int group_lds_bytes() { return (int)((sizeof(GroupLDS<CH, G>) + 15) & ~size_t(15)); }
-
-// A wave's LDS: per slot g its group's arrays, then its SlotState -- slot g at g * group_stride.  The
-// 16-lane kernel's stride (1856 B = 464 dwords, 16 mod 32) puts the two DPP rows of a 32-lane LDS lane group
-// (slots 0 / 1, 2 / 3) half a bank row apart: lane-mode B and C1 step through chunks 17 atoms apart, and
-// two slots 452 dwords apart (the arrays back to back, then the slot states) made most of those reads
-// 2-way bank conflicts; interleaved, the same bytes are conflict-free.
-template <int CH, int G>
-constexpr int group_stride() { return group_lds_bytes<CH, G>() + (int)sizeof(SlotState); }
-static_assert(group_stride<256, 16>() == 1856, "16-lane group stride: 21 resident waves per CU (512-B LDS granule), slots 16 dwords mod 32 apart");
-template <int CH, int G>
-constexpr int block_lds_bytes() { return (64 / G) * group_stride<CH, G>(); }
-
-// ------------------------------------------------------------------ trie access
-
-struct TrieView {
-    // .x = base | TERM<<31 | LEAF<<30, .y = check (parent slot, -1 free); followed by the 65536-entry
-    // two-byte root table (entry b0 << 8 | b1 at slots[n_slots + ...], see dpt_api.cpp)
-    const int2 *__restrict__ slots;
-    const int32_t *__restrict__ ids;  // token id of a terminal slot
-    const int4 *__restrict__ slots4;  // {base, check, id, 0}: C2's walks get the id with the last node
-    int32_t root_base;
-    uint32_t n_slots;
-    // [b0 << 8 | b1]: id of the two-byte token, [65536 + b0]: of the one-byte one (-1: none); then, from
-    // element PAIR16_N, A0's uint2 table [b0 << 8 | b1]: flags (root child b0, b0 a token, node b0 b1, its
-    // TERM, LEAF) + that node's child filter
-    const int16_t *__restrict__ pair16;
-};
-
-// Trie reads through buffer resources: 32-bit slot offsets (no 64-bit address arithmetic) and a
-// range check that makes any index safe (out of range reads {0, 0}: a failed transition).
-__device__ __forceinline__ int2 trie_slot(const TrieView &tv, int32_t t) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)tv.slots, (short)0, (int)((tv.n_slots + 65536u) * 8u), 0x00020000);
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, (unsigned)t * 8u, 0, 0);
-    return make_int2((int32_t)v[0], (int32_t)v[1]);
-}
-// phase A: {base, check, id, child filter} per slot, then the root table as {.x, .y, 0, child
-// filter} (dpt_api.cpp), so one 16-byte load serves both
-__device__ __forceinline__ int4 trie_slotA(const TrieView &tv, int32_t t) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)tv.slots4, (short)0, (int)((tv.n_slots + 65536u) * 16u), 0x00020000);
-    return __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)t * 16u, 0, 0));
-}
-__device__ __forceinline__ int4 trie_slot4(const TrieView &tv, int32_t t) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)tv.slots4, (short)0, (int)(tv.n_slots * 16u), 0x00020000);
-    return __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)t * 16u, 0, 0));
-}
-
-[[maybe_unused]] constexpr int32_t TERM_BIT = (int32_t)0x80000000;
-[[maybe_unused]] constexpr int32_t LEAF_BIT = 0x40000000;  // no children (dpt_long.hip ends walks on it; this kernel uses the child filters)
-constexpr int32_t BASE_MASK = 0x3FFFFFFF;
-
-// ------------------------------------------------------------------ arguments
-
-struct EncodeArgs {
-    const uint8_t *text;
-    const uint64_t *str_off;
-    const uint8_t *cut_mask;    // PRESPLIT / ATOMS only
-    uint64_t n_str;
-    int32_t *staging;           // ids staged at (str_off[s]-str_off[0]) + k
-    int16_t *staging16;         // non-null: the ids are staged here as int16 instead (half the bytes)
-    uint64_t *counts;           // per string
-    unsigned long long *bsum;   // nullable: the batch lines (dpt_internal.h BS_LINE): per FIN_BATCH strings, the sum of
-                                //   their counts (atomics as strings finish)
-    int32_t *status;
-    int32_t *capped;            // nullable
-    uint32_t *retry_list;       // strings for the 2048-byte pass
-    uint32_t *retry_count;
-    uint32_t *long_list;        // strings for the unbounded pass (dpt_long.hip)
-    uint32_t *long_count;
-    const uint32_t *work_list;  // 2048-byte pass: the retry list
-    const uint32_t *work_count;
-    uint32_t *work_next;        // 2048-byte pass: its work counter (zeroed per launch)
-    uint32_t *part_ctr;         // first pass: NPART partition counters (PART_STRIDE apart), then the used-up mask
-    uint8_t *wsl_scratch;       // word lists of the 256-byte pass: grid x NG x WSL_STRIDE bytes
-    uint4 *pend;                // 16-lane first pass: per wave, 64 pending residual tokens (walk_pending)
-    int32_t ws_node, ws_base, ws_id;   // the trie node after U+2581, its base word and id (-1: none)
-    int long_span;              // the vocabulary has tokens longer than 64 code points
-    uint64_t *edges;            // nullable: per atom end, the E(i) & reachable back-distance mask
-    int mode;                   // DPT_MODE_* | DPT_FLAG_*
-    unsigned long long *hist_zero;   // 2048-byte pass, fin_fold calls with DPT_HIST_OVERWRITE: the histogram to
-    uint32_t n_hist;                 //   zero before the finish pass adds to it (the scan kernel's duty otherwise)
-    uint64_t *id_off;
-    int32_t *ids;
-    // one-string host-path calls (EncodeLaunch::solo): the string's ids go straight to ids (staging =
-    // ids, counts = id_off + 1) and the lone wave writes id_off[0] and resets the counter block (its
-    // first 64 bytes to ctr_snap) -- no fallback, scan or finish launch follows
-    int solo;
-    uint64_t *ctr_snap;
-};
-
-#ifdef DPT_STAMPS
-// diagnostic build only: cycles per phase summed over waves (never in the product build)
-__device__ unsigned long long g_stamps[10];
-// (the wave's stamps: the driver's, handed to the one phase that stamps inside itself, C2)
-struct Stamps {
-    unsigned long long acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long prev = __builtin_amdgcn_s_memtime();
-};
-#define STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); st.acc[k] += _t - st.prev; st.prev = _t; } while (0)
-#define STAMP_FLUSH do { if (lane == 0) for (int _k = 0; _k < 10; _k++) atomicAdd(&g_stamps[_k], st.acc[_k]); } while (0)
-#else
-struct Stamps {};
-#define STAMP(k)
-#define STAMP_FLUSH
-#endif
-#ifdef DPT_WSTAMPS
-// diagnostic build only (its own library, no phase stamps): the first pass's per-wave timeline (tools/wave_timeline.py): per wave (blockIdx), [0] its first
-// instruction, [1 + k] the end of its k-th slot round (| the round's busy slots << 56), [WST_N - 1] its exit
-// (| its rounds << 48); s_memrealtime (100 MHz, one clock for the whole chip)
-constexpr unsigned WST_MAXW = 8192, WST_N = 128;
-__device__ unsigned long long g_wst[WST_MAXW * WST_N];
-#define WST_REC(k, v) do { if (!BIG && lane == 0 && bid < WST_MAXW && (unsigned)(k) < WST_N) g_wst[(size_t)bid * WST_N + (k)] = (v); } while (0)
-#define WST_NOW() ((unsigned long long)__builtin_amdgcn_s_memrealtime())
-#else
-#define WST_REC(k, v)
-#define WST_NOW() 0ull
-#endif
 
 // Phase A's per-atom descriptor: byte offset | byte length << PB | "a word or the window ends
 // after it" << PB+4 | "first atom of the string" << PB+5 (16 bits for 256-byte windows).  It is
@@ -594,7 +233,6 @@ __device__ __forceinline__ bool token_hash_long(const uint8_t *bytes, unsigned p
 }
 
 // ------------------------------------------------------------------ prep: one slot's window
-
 
 // The bytes (and cut-mask bytes) of a window, in registers: lane l holds bytes
 // [256c + 4l, 256c + 4l + 4) of chunk c, little-endian; *_end is the byte at CH (the probe
@@ -840,13 +478,6 @@ __device__ bool prep_window(GroupLDS<CH, G> &L, uint8_t *gw, const WinRegs<CH> &
     return ballot(bad) == 0;
 }
 
-#ifndef DPT_LEAN_NOSCAN   // A/B knob: the lean prep of a window without '\n' takes its code-point prefixes from the index
-#define DPT_LEAN_NOSCAN 0
-#endif
-constexpr bool LEAN_NOSCAN = DPT_LEAN_NOSCAN != 0;
-#ifndef DPT_LEAN_SETPRIO  // A/B knob: the lean kernel raises its wave priority around lane-mode B and its C1 walk
-#define DPT_LEAN_SETPRIO 0
-#endif
 // The lean first pass's prep (raw mode, 256-byte 16-lane rows; tokenize_body LEAN = 1): the window [pos, pos + wlen) is
 // pure ASCII (the caller tested it), so atom j is byte j -- no aoff[] (the lean readers use the index), no word list,
 // no walk descriptors -- and rec[j] = the end mask all dead | the code-point prefix | the word-start bit as prep_window
@@ -863,9 +494,9 @@ __device__ __forceinline__ void prep_window_lean(GroupLDS<256, 16> &L, const Win
     for (int u = 0; u < 4; u++) cl[u] = 1u + 5u * ((nl >> (8 * u + 7)) & 1u);
     if (pos == 0 && lane == 0) cl[0] = 2u;
     const unsigned sum = cl[0] + cl[1] + cl[2] + cl[3];
-    unsigned cp;
-    if (LEAN_NOSCAN && !ballot(nl != 0)) cp = k0 + ((pos == 0 && lane > 0) ? 1u : 0u);   // a code point per byte: no scan
-    else cp = wave_incl_scan_add(sum) - sum;
+    // (always the scan: taking the prefixes of a window without '\n' from the index measured nothing -- the scan is
+    // ~12 DPP ops of ~1,700 instructions per window; profiles/lean_ab.log, third session)
+    unsigned cp = wave_incl_scan_add(sum) - sum;
     uint4 r;
     r.x = 0xFFFF0000u | cp | ((lane == 0 || (sp & 0x80u)) ? (unsigned)CP_WS : 0u);
     cp += cl[0];
@@ -892,8 +523,6 @@ __device__ __forceinline__ void prep_window_lean(GroupLDS<256, 16> &L, const Win
 
 // ------------------------------------------------------------------ the tokenize kernel
 
-constexpr unsigned NPART = 16;   // first-pass work partitions (<= NPART_MAX)
-static_assert(NPART >= 1 && NPART <= NPART_MAX, "NPART");
 // First-pass partition p of npart over n strings: the FIN_BATCH-string chunks c with c % npart == p,
 // in order.  part_size: its strings; part_string: the string at partition-local index v (< part_size).
 // (32-bit arithmetic: a call has fewer than 2^31 strings)
@@ -908,97 +537,6 @@ __device__ __forceinline__ unsigned part_size(unsigned n, unsigned npart, unsign
 __device__ __forceinline__ unsigned part_string(unsigned npart, unsigned p, unsigned v) {
     return ((v / FIN_BATCH) * npart + p) * FIN_BATCH + v % FIN_BATCH;
 }
-#ifndef DPT_NEAR_CUT   // A/B knob: lane-mode B snaps chunk starts to the nearest cut point (else the next one)
-#define DPT_NEAR_CUT 1
-#endif
-constexpr bool NEAR_CUT = DPT_NEAR_CUT != 0;
-// (the 64-lane push recurrence keeps the next cut: nearest measured 0.9 % slower on BLOOM, r05e)
-constexpr bool NEAR_CUT64 = false;
-// A/B knobs: the shape of lane-mode B's loops (forward_lanes, G = 16; DESIGN.md 4, "the shape of the lane loops")
-#ifndef DPT_CUT_SEL     // the cut-point pass without a branch per boundary: a clamped read and a predicated min / mask
-#define DPT_CUT_SEL 1   // update, so the reads of the unrolled steps are in flight together (0: `if (i <= c1)`)
-#endif
-constexpr bool CUT_SEL = DPT_CUT_SEL != 0;
-#ifndef DPT_LOOP_UNI    // the recurrence and C1 walk loops count the wave's longest lane down in an SGPR: their state
-#define DPT_LOOP_UNI 1  // is then not copied across the loop edge (0: the ballot of the lanes' own guard per step)
-#endif
-constexpr bool LOOP_UNI = DPT_LOOP_UNI != 0;
-#ifndef DPT_A0_SWAR     // A/B knob: phase A0's per-byte flags four bytes per VALU op (bit 7 of each byte)
-#define DPT_A0_SWAR 1
-#endif
-constexpr bool A0_SWAR = DPT_A0_SWAR != 0;
-#ifndef DPT_BULK_U      // A/B knob: C2's bulk pass, tokens per lane per round (their lookups before their stores)
-#define DPT_BULK_U 4
-#endif
-#ifndef DPT_HASH_BOTH   // A/B knob: C2's hash lookups load both buckets at once (0: the partner only on a miss)
-#define DPT_HASH_BOTH 0
-#endif
-constexpr bool HASH_BOTH = DPT_HASH_BOTH != 0;
-#ifndef DPT_HP_U        // A/B knob: C2 hash-pass token rounds of 64 per iteration (loads before stores)
-#define DPT_HP_U 2
-#endif
-#ifndef DPT_A0_R2       // A/B knob: A0's third-byte round for walks that go on past two bytes
-#define DPT_A0_R2 1
-#endif
-constexpr bool A0_R2 = DPT_A0_R2 != 0;
-#ifndef DPT_A0_R2_MIN   // ... taken when at least this many lanes of the slot have such a walk
-#define DPT_A0_R2_MIN 24
-#endif
-constexpr int A0_R2_MIN = DPT_A0_R2_MIN;
-constexpr unsigned A_REFILL = 32;     // phase A: idle lanes needed before a batched refill (1/8/16/32 within 2 %)
-constexpr unsigned A_REFILL64 = 32;   // the same for the 64-lane kernels (8 / 1: neutral / -0.5 %, r03aa)
-#ifndef DPT_STOP     // diagnostic builds only (wrong results): 1 = prep only, 21 = + A0, 2 = + A, 25 / 26 / 27 =
-                     // + lane-mode B's cut points / recurrence / transfer scan + fix-up, 3 = + B/C0/C1
-#define DPT_STOP 9
-#endif
-#ifndef DPT_DIAG_PREP   // diagnostic builds only (cfg2-shaped input): 1 = static claims (no counter atomics),
-#define DPT_DIAG_PREP 0  // 2 = offsets computed as 256 s (no str_off loads), 3 = both, 4 = a second dependent claim
-#endif                   // atomic, 8 = no batch-sum atomics (wrong CSR offsets) -- the refill chain's and the atomics' cost
-#ifndef DPT_C2STOP   // diagnostic builds only (wrong results): C2 stops after its bulk pass (1) / hash pass (2)
-#define DPT_C2STOP 0
-#endif
-#define DPT_RUN_B (DPT_STOP >= 3 && DPT_STOP != 21)
-#define DPT_RUN_C2 (DPT_STOP == 9)
-
-// Waves per SIMD by VGPRs (<= 80 VGPRs each).  The 256-byte 16-lane rows: LDS (22 waves per CU) then
-// binds (96 VGPRs / 5 waves: no scratch spills, cfg2 -1.9 %, r03e).  The 256-byte 64-lane kernel: BLOOM
-// 17.4 -> 19.8 GB/s against no cap (95 VGPRs, 20 waves; 7 or 8 waves spill more: r03aa, r03ac).
-#ifndef DPT_WPC_LO      // small calls: the persistent grid's fewest resident waves per CU (launch_tok)
-#define DPT_WPC_LO 20
-#endif
-#ifndef DPT_WPC_GRAN    // LDS allocation granule (bytes) that caps the resident waves per CU (launch_tok)
-#define DPT_WPC_GRAN 512
-#endif
-#ifndef DPT_PLAIN_RAW   // A/B knob: the RAW kernels without the edges / uncapped / len_only loop versions too
-#define DPT_PLAIN_RAW 0
-#endif
-#ifndef DPT_WPE16
-#define DPT_WPE16 6
-#endif
-constexpr int WPE16 = DPT_WPE16;
-#ifndef DPT_WPE64
-#define DPT_WPE64 6
-#endif
-constexpr int WPE64 = DPT_WPE64;
-// The kernel's arguments, as one struct at the start of the kernarg segment
-struct KernArgs {
-    EncodeArgs ea;
-    TrieView tv;
-};
-typedef __attribute__((address_space(4))) const KernArgs ConstKernArgs;
-// Arguments are read through the kernarg segment pointer, which KREFRESH makes opaque at every phase
-// boundary: each phase then loads (s_load, scalar-cache hits) the few arguments it uses instead of
-// the compiler keeping all ~30 of them in SGPRs across the whole loop -- the hot kernel sits at the
-// SGPR limit and spills.
-// (a field-wise copy: only the fields a use reads are loaded)
-__device__ __forceinline__ TrieView tv_of(ConstKernArgs *kp) {
-    TrieView t;
-    t.slots = kp->tv.slots; t.ids = kp->tv.ids; t.slots4 = kp->tv.slots4;
-    t.root_base = kp->tv.root_base; t.n_slots = kp->tv.n_slots; t.pair16 = kp->tv.pair16;
-    return t;
-}
-// (the 16-lane instantiations: the 64-lane ones do not spill, and measured 1.7 % slower with it)
-#define KREFRESH() do { if constexpr (G == 16) asm volatile("" : "+s"(kp)); } while (0)
 
 // Reset the counter block (CounterBlock, then the partition counters: dpt_internal.h) for the next call
 // (the claimed arena bytes and far pairs stay readable as the call's "last need" / "last far").
@@ -1038,8 +576,10 @@ struct TokPass {
     using M = typename GR::M;
     static constexpr unsigned GSTR = (unsigned)group_stride<CH, G>();
     // PLAIN: the mode-constant instantiations serve only calls without edges, the uncapped DP or len_only
-    // (launch_encode sends those to the runtime-mode kernels): their loop versions are compiled out
-    static constexpr bool PLAIN = ((RAW && DPT_PLAIN_RAW) || MC >= 0 || LEAN == 1) && !SOLO;
+    // (launch_encode sends those to the runtime-mode kernels): their loop versions are compiled out.  (Not the RAW
+    // kernels: stripped, they spilled 9 VGPRs with the reloads inside B's loops, 435 -> 572 MB fetched per 1M-string
+    // launch at the same speed -- profiles/r06_ab.log r06x)
+    static constexpr bool PLAIN = (MC >= 0 || LEAN == 1) && !SOLO;
     // LITM: phase B records the edge masks as include/dpt.h words them (forward, below).  Not in the raw-mode first
     // passes, which plan_encode never picks for a call with edges (their edge loop versions are never run, and stay
     // as they were so that the kernels stay the same code)
@@ -1248,33 +788,23 @@ struct TokPass {
                     tt[u] = t; hh2[u] = h & hh.mask; fpv[u] = fp; oqv[u] = q.ob + k; hs[u] = hashed; inr[u] = in;
                 }
                 int32_t idv[HP_U];
-                if constexpr (HASH_BOTH) {
-                    // every round's two buckets (the key's two choices) at once, then the stores
+                // every round's home bucket, then the partner buckets of the keys not found there
+                // (one more load round for the wave, never a chain), then the stores.  (Both buckets at once for
+                // every key measured slower on cfg2 / cfg5: r05aj)
+#pragma unroll
+                for (int u = 0; u < HP_U; u++) {
+                    const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
+                    idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : (e[2] == fpv[u] ? (int32_t)e[3] : INT32_MIN);
+                }
+                bool miss = false;
+#pragma unroll
+                for (int u = 0; u < HP_U; u++) miss |= hs[u] && idv[u] == INT32_MIN;
+                if (ballot(miss)) {
 #pragma unroll
                     for (int u = 0; u < HP_U; u++) {
-                        const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
-                        const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
-                        idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : e[2] == fpv[u] ? (int32_t)e[3] :
-                                 f[0] == fpv[u] ? (int32_t)f[1] : f[2] == fpv[u] ? (int32_t)f[3] : -1;
-                    }
-                } else {
-                    // every round's home bucket, then the partner buckets of the keys not found there
-                    // (one more load round for the wave, never a chain), then the stores
-#pragma unroll
-                    for (int u = 0; u < HP_U; u++) {
-                        const auto e = __builtin_amdgcn_raw_buffer_load_b128(hr, hh2[u] * 16u, 0, 0);
-                        idv[u] = e[0] == fpv[u] ? (int32_t)e[1] : (e[2] == fpv[u] ? (int32_t)e[3] : INT32_MIN);
-                    }
-                    bool miss = false;
-#pragma unroll
-                    for (int u = 0; u < HP_U; u++) miss |= hs[u] && idv[u] == INT32_MIN;
-                    if (ballot(miss)) {
-#pragma unroll
-                        for (int u = 0; u < HP_U; u++) {
-                            if (hs[u] && idv[u] == INT32_MIN) {
-                                const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
-                                idv[u] = f[0] == fpv[u] ? (int32_t)f[1] : (f[2] == fpv[u] ? (int32_t)f[3] : -1);
-                            }
+                        if (hs[u] && idv[u] == INT32_MIN) {
+                            const auto f = __builtin_amdgcn_raw_buffer_load_b128(hr, tokhash_alt(hh2[u], fpv[u], hh.mask) * 16u, 0, 0);
+                            idv[u] = f[0] == fpv[u] ? (int32_t)f[1] : (f[2] == fpv[u] ? (int32_t)f[3] : -1);
                         }
                     }
                 }
@@ -1904,10 +1434,9 @@ struct TokPass {
                 // get every walk's first lookup here, byte-parallel with four loads in flight per lane;
                 // the walks it cannot finish (word starts, the string's first atom, '\n', and walks that
                 // go on past the two-byte root entry: ~6 % in cfg2 with the child filters) are marked
-                // (bit 4g + u of `mark`: atom 4 * lane + u of slot g) and redone by the walker below,
-                // which also takes every atom of the other slots.
+                // (listed in the slot's fin[]) and redone by the walker below, which also takes every atom of
+                // the other slots.
                 unsigned a0mask = 0;
-                uint32_t mark = 0;
                 if constexpr (G == 16 && !BIG) {
                     if (!raw) {   // PRESPLIT: the '\u2581'-compressed windows (prep_window)
 #pragma unroll
@@ -1988,7 +1517,6 @@ struct TokPass {
                 };
                 if constexpr (G == 16 && !BIG) {
                     if (a0mask) {
-                        constexpr unsigned END = 0x100u;
 #pragma unroll
                         for (int g = 0; g < NG; g++) {
                             if (!((a0mask >> g) & 1u)) continue;
@@ -1998,189 +1526,117 @@ struct TokPass {
                             const unsigned gbase = (unsigned)g * GSTR;
                             const uint32_t *b32 = reinterpret_cast<const uint32_t *>(grp(g).bytes);
                             const unsigned k0 = 4u * lane;
-                            if constexpr (A0_SWAR) {
-                                // The lane's four bytes as one 32-bit word (SWAR): every per-byte flag is bit 7 of
-                                // its byte, so one VALU op tests four bytes.  Views: w0 = bytes k0..k0+3 (b), n1w =
-                                // k0+1.. (the next byte), n2w = k0+2.. (the one after).
-                                constexpr uint32_t H = 0x80808080u;
-                                const uint32_t w0 = b32[lane], w1 = b32[lane + 1u];
-                                const uint32_t n1w = __builtin_amdgcn_alignbyte(w1, w0, 1u);
-                                const uint32_t n2w = __builtin_amdgcn_alignbyte(w1, w0, 2u);
-                                // lookups at (b, n1) as read: the table holds (b, '<')'s entry at (b, '\n') too,
-                                // and (b, END)'s flags of b are (b, anything)'s (dpt_api.cpp)
-                                uint2 ent[4];
-#pragma unroll
-                                for (int u = 0; u < 4; u++)
-                                    ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[
-                                        __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)];
-                                // bytes past the window (END): byte q of the 8 is valid while q < nv
-                                const unsigned nv = wl > k0 ? min(wl - k0, 8u) : 0u;
-                                const uint64_t vm = nv >= 8u ? ~0ull : ((1ull << (8u * nv)) - 1ull);
-                                const uint32_t vlo = (uint32_t)vm, vhi = (uint32_t)(vm >> 32);
-                                const uint32_t v0 = vlo & H, v1 = __builtin_amdgcn_alignbyte(vhi, vlo, 1u) & H,
-                                               v2 = __builtin_amdgcn_alignbyte(vhi, vlo, 2u) & H;
-                                auto eq80 = [](uint32_t x, uint32_t c) -> uint32_t {   // bit 7 of each byte of x equal to c's
-                                    const uint32_t t = x ^ c;
-                                    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-                                };
-                                const uint32_t sp0 = eq80(w0, 0x20202020u), sp1w = eq80(w1, 0x20202020u);
-                                const uint32_t nl0 = eq80(w0, 0x0A0A0A0Au), nl1w = eq80(w1, 0x0A0A0A0Au);
-                                const uint32_t sp1 = __builtin_amdgcn_alignbyte(sp1w, sp0, 1u), sp2 = __builtin_amdgcn_alignbyte(sp1w, sp0, 2u);
-                                const uint32_t nl1 = __builtin_amdgcn_alignbyte(nl1w, nl0, 1u), nl2 = __builtin_amdgcn_alignbyte(nl1w, nl0, 2u);
-                                const uint32_t special = sp0 | nl0 | ((first && lane == 0) ? 0x80u : 0u);   // the walker's
-                                const uint32_t norm = v0 & ~special;
-                                const uint32_t cont = v1 & ~sp1;   // n1 is in the word
-                                // the entries' flag bytes side by side (bit 0 root child, 1 b a token, 2 node b n1,
-                                // 3 it ends a token, 4 it is a leaf) and their child-filter bits for n2
-                                const uint32_t xs = __builtin_amdgcn_perm(ent[1].x, ent[0].x, 0x0C0C0400u) |
-                                                    (__builtin_amdgcn_perm(ent[3].x, ent[2].x, 0x0C0C0400u) << 16);
-                                const uint32_t cb = n2w ^ ((n2w >> 5) & 0x07070707u);   // child_bit(byte) in each byte's low 5 bits
-                                const uint32_t f0 = ent[0].y >> (cb & 31u), f1 = ent[1].y >> ((cb >> 8) & 31u),
-                                               f2 = ent[2].y >> ((cb >> 16) & 31u), f3 = ent[3].y >> ((cb >> 24) & 31u);
-                                const uint32_t fb = (__builtin_amdgcn_perm(f1, f0, 0x0C0C0400u) |
-                                                     (__builtin_amdgcn_perm(f3, f2, 0x0C0C0400u) << 16)) << 7;
-                                const uint32_t tok1 = (xs << 7) & (xs << 6);
-                                const uint32_t has2 = norm & cont & (xs << 5);
-                                // go on past two bytes: n2 in the word with a child for it; '\n' at n1 or n2 ("<0x0A>")
-                                // always (the walker redoes such starts whole)
-                                const uint32_t more = has2 & ~(xs << 3) & (nl1 | (v2 & (nl2 | (~sp2 & fb))));
-                                const uint32_t tk1 = norm & tok1;                  // a one-atom token ends at k0+1+u
-                                const uint32_t tk2 = has2 & ~nl1 & (xs << 4);      // a two-atom token ends at k0+2+u
-                                uint32_t mk = ((v0 & special) | more) & H;   // walker starts
-                                if constexpr (A0_R2) {
-                                    // Third-byte round: a walk that goes on past two plain bytes of the word takes
-                                    // its root-table step (the node after the pair) and its third step here,
-                                    // byte-parallel, and stays for the walker only if it goes on past three
-                                    // (cfg4: ~97 % of these walks end there).  The three-atom token, if any, is
-                                    // recorded here.  Slots with few such walks leave them to the walker.
-                                    const uint32_t r2 = more & ~nl1 & ~nl2 & H;
-                                    if (__builtin_popcountll(ballot(r2 != 0)) >= A0_R2_MIN) {
-                                        const uint32_t v3 = __builtin_amdgcn_alignbyte(vhi, vlo, 3u) & H;
-                                        const uint32_t sp3 = __builtin_amdgcn_alignbyte(sp1w, sp0, 3u);
-                                        const uint32_t nl3 = __builtin_amdgcn_alignbyte(nl1w, nl0, 3u);
-                                        const uint32_t n3w = __builtin_amdgcn_alignbyte(w1, w0, 3u);
-                                        constexpr int32_t OOB = 0x7FFFFFF;   // past the table: the buffer load returns zeros
-                                        int4 e2r[4], e3[4];
-#pragma unroll
-                                        for (int u = 0; u < 4; u++)   // the root table's entry of (b, n1)
-                                            e2r[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ? (int32_t)(tv.n_slots +
-                                                     __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)) : OOB);
-#pragma unroll
-                                        for (int u = 0; u < 4; u++)   // the node after n2
-                                            e3[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ?
-                                                    (int32_t)((e2r[u].x & BASE_MASK) + ((n2w >> (8 * u)) & 0xFFu)) : OOB);
-                                        uint32_t c3 = 0, t3 = 0;
-#pragma unroll
-                                        for (int u = 0; u < 4; u++) {
-                                            const unsigned n3 = (n3w >> (8 * u)) & 0xFFu;
-                                            const unsigned ok3 = ((r2 >> (8 * u + 7)) & 1u) & (unsigned)(e3[u].y == (e2r[u].y & 0x3FFFFFFF));
-                                            const unsigned leaf3 = ((unsigned)e3[u].x >> 30) & 1u;
-                                            const unsigned in3 = ((v3 & ~sp3) >> (8 * u + 7)) & 1u;
-                                            const unsigned ch3 = (((unsigned)e3[u].w >> child_bit(n3)) & 1u) | ((nl3 >> (8 * u + 7)) & 1u);
-                                            t3 |= (ok3 & ((unsigned)e3[u].x >> 31)) << (8 * u + 7);
-                                            c3 |= (ok3 & (leaf3 ^ 1u) & in3 & ch3) << (8 * u + 7);
-                                        }
-                                        mk = ((v0 & special) | (more & ~r2) | c3) & H;
-                                        if (ballot(t3 != 0)) {   // a three-atom token ends at k0+3+u
-                                            uint32_t *q32 = reinterpret_cast<uint32_t *>(smem + gbase);
-#pragma unroll
-                                            for (int u = 0; u < 4; u++)
-                                                __hip_atomic_fetch_and(&q32[k0 + 3u + u],
-                                                                       ~(((t3 >> (8 * u + 7)) & 1u) << 18),
-                                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                        }
-                                    }
-                                }
-                                const uint32_t t2e = (tk2 << 8) | wave_shift_in(tk2 >> 24, 0u);
-                                // end k0+1+u: bit 0 of byte u of d a one-atom token, bit 1 a two-atom one
-                                const uint32_t d = ((tk1 & H) >> 7) | ((t2e & H) >> 6);
-                                uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
-                                if (ballot(d != 0)) {
-#pragma unroll
-                                    for (int u = 0; u < 4; u++)
-                                        __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~(((d >> (8 * u)) & 3u) << 16),
-                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                }
-                                if (ballot((norm & ~tok1) != 0) && lane == 0) SSr(g).capb = 1;
-                                // the slot's marked atoms, in order, into its fin[] (free until phase B)
-                                const unsigned c = (unsigned)__builtin_popcount(mk);
-                                const unsigned incl = wave_incl_scan_add(c);
-                                unsigned o = incl - c;
-                                GL &Lg = grp(g);
-#pragma unroll
-                                for (int u = 0; u < 4; u++)
-                                    if ((mk >> (8 * u + 7)) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
-                                nstart[g] = __builtin_amdgcn_readlane(incl, 63);
-                                continue;
-                            }
-                            // bytes k0 .. k0+7 (past the window: masked by wl below)
-                            const uint64_t w = (uint64_t)b32[lane] | ((uint64_t)b32[lane + 1u] << 32);
-                            auto byte_at = [&](unsigned q) -> unsigned {   // byte k0+q, END past the window
-                                return k0 + q < wl ? (unsigned)((w >> (8u * q)) & 0xFFu) : END;
-                            };
-                            uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
-                            bool nocap = false;
-                            unsigned tk1 = 0, tk2 = 0;
-                            // the packed byte-pair table over (byte, next byte): the flags of the first byte do
-                            // not depend on the second; four lookups in flight per lane
+                            // The lane's four bytes as one 32-bit word (SWAR): every per-byte flag is bit 7 of
+                            // its byte, so one VALU op tests four bytes.  Views: w0 = bytes k0..k0+3 (b), n1w =
+                            // k0+1.. (the next byte), n2w = k0+2.. (the one after).  (226 -> 133 VALU per slot against a
+                            // flag per byte: cfg2 -3.4 %, 125k -2.5 %, cfg4 -3.0 %, r05o)
+                            constexpr uint32_t H = 0x80808080u;
+                            const uint32_t w0 = b32[lane], w1 = b32[lane + 1u];
+                            const uint32_t n1w = __builtin_amdgcn_alignbyte(w1, w0, 1u);
+                            const uint32_t n2w = __builtin_amdgcn_alignbyte(w1, w0, 2u);
+                            // lookups at (b, n1) as read: the table holds (b, '<')'s entry at (b, '\n') too,
+                            // and (b, END)'s flags of b are (b, anything)'s (dpt_api.cpp)
                             uint2 ent[4];
 #pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const unsigned b = byte_at(u), n1 = byte_at(u + 1);
-                                const unsigned e1 = n1 == '\n' ? (unsigned)'<' : n1;
-                                ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[((b & 0xFFu) << 8) | (e1 & 0xFFu)];
-                            }
-                            // Per byte: tk1 bit u = a one-atom token ends at k0+1+u, tk2 bit u = a two-atom
-                            // token ends at k0+2+u (the end masks are written once below)
-                            // (flags as 0/1 integers combined with & and |: short-circuit forms become
-                            // exec-mask branches here)
+                            for (int u = 0; u < 4; u++)
+                                ent[u] = reinterpret_cast<const uint2 *>(tv.pair16 + PAIR16_N)[
+                                    __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)];
+                            // bytes past the window (END): byte q of the 8 is valid while q < nv
+                            const unsigned nv = wl > k0 ? min(wl - k0, 8u) : 0u;
+                            const uint64_t vm = nv >= 8u ? ~0ull : ((1ull << (8u * nv)) - 1ull);
+                            const uint32_t vlo = (uint32_t)vm, vhi = (uint32_t)(vm >> 32);
+                            const uint32_t v0 = vlo & H, v1 = __builtin_amdgcn_alignbyte(vhi, vlo, 1u) & H,
+                                           v2 = __builtin_amdgcn_alignbyte(vhi, vlo, 2u) & H;
+                            auto eq80 = [](uint32_t x, uint32_t c) -> uint32_t {   // bit 7 of each byte of x equal to c's
+                                const uint32_t t = x ^ c;
+                                return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
+                            };
+                            const uint32_t sp0 = eq80(w0, 0x20202020u), sp1w = eq80(w1, 0x20202020u);
+                            const uint32_t nl0 = eq80(w0, 0x0A0A0A0Au), nl1w = eq80(w1, 0x0A0A0A0Au);
+                            const uint32_t sp1 = __builtin_amdgcn_alignbyte(sp1w, sp0, 1u), sp2 = __builtin_amdgcn_alignbyte(sp1w, sp0, 2u);
+                            const uint32_t nl1 = __builtin_amdgcn_alignbyte(nl1w, nl0, 1u), nl2 = __builtin_amdgcn_alignbyte(nl1w, nl0, 2u);
+                            const uint32_t special = sp0 | nl0 | ((first && lane == 0) ? 0x80u : 0u);   // the walker's
+                            const uint32_t norm = v0 & ~special;
+                            const uint32_t cont = v1 & ~sp1;   // n1 is in the word
+                            // the entries' flag bytes side by side (bit 0 root child, 1 b a token, 2 node b n1,
+                            // 3 it ends a token, 4 it is a leaf) and their child-filter bits for n2
+                            const uint32_t xs = __builtin_amdgcn_perm(ent[1].x, ent[0].x, 0x0C0C0400u) |
+                                                (__builtin_amdgcn_perm(ent[3].x, ent[2].x, 0x0C0C0400u) << 16);
+                            const uint32_t cb = n2w ^ ((n2w >> 5) & 0x07070707u);   // child_bit(byte) in each byte's low 5 bits
+                            const uint32_t f0 = ent[0].y >> (cb & 31u), f1 = ent[1].y >> ((cb >> 8) & 31u),
+                                           f2 = ent[2].y >> ((cb >> 16) & 31u), f3 = ent[3].y >> ((cb >> 24) & 31u);
+                            const uint32_t fb = (__builtin_amdgcn_perm(f1, f0, 0x0C0C0400u) |
+                                                 (__builtin_amdgcn_perm(f3, f2, 0x0C0C0400u) << 16)) << 7;
+                            const uint32_t tok1 = (xs << 7) & (xs << 6);
+                            const uint32_t has2 = norm & cont & (xs << 5);
+                            // go on past two bytes: n2 in the word with a child for it; '\n' at n1 or n2 ("<0x0A>")
+                            // always (the walker redoes such starts whole)
+                            const uint32_t more = has2 & ~(xs << 3) & (nl1 | (v2 & (nl2 | (~sp2 & fb))));
+                            const uint32_t tk1 = norm & tok1;                  // a one-atom token ends at k0+1+u
+                            const uint32_t tk2 = has2 & ~nl1 & (xs << 4);      // a two-atom token ends at k0+2+u
+                            uint32_t mk = ((v0 & special) | more) & H;   // walker starts
+                            // Third-byte round: a walk that goes on past two plain bytes of the word takes
+                            // its root-table step (the node after the pair) and its third step here,
+                            // byte-parallel, and stays for the walker only if it goes on past three
+                            // (cfg4: ~97 % of these walks end there).  The three-atom token, if any, is
+                            // recorded here.  Slots with few such walks leave them to the walker (cfg4 -4.2 %, the
+                            // others within noise: r05ae).
+                            const uint32_t r2 = more & ~nl1 & ~nl2 & H;
+                            if (__builtin_popcountll(ballot(r2 != 0)) >= A0_R2_MIN) {
+                                const uint32_t v3 = __builtin_amdgcn_alignbyte(vhi, vlo, 3u) & H;
+                                const uint32_t sp3 = __builtin_amdgcn_alignbyte(sp1w, sp0, 3u);
+                                const uint32_t nl3 = __builtin_amdgcn_alignbyte(nl1w, nl0, 3u);
+                                const uint32_t n3w = __builtin_amdgcn_alignbyte(w1, w0, 3u);
+                                constexpr int32_t OOB = 0x7FFFFFF;   // past the table: the buffer load returns zeros
+                                int4 e2r[4], e3[4];
 #pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const unsigned k = k0 + (unsigned)u;
-                                const unsigned b = byte_at(u), n1 = byte_at(u + 1), n2 = byte_at(u + 2);
-                                const auto e = ent[u];
-                                const unsigned valid = (unsigned)(b != END);
-                                const unsigned special = (unsigned)(b == ' ') | (unsigned)(b == '\n') | ((unsigned)first & (unsigned)(k == 0));   // the walker's
-                                const unsigned norm = valid & (special ^ 1u);
-                                // n1 ends the word: the lookup was the atom's own root slot
-                                const unsigned wend = (unsigned)(n1 == END) | (unsigned)(n1 == ' ');
-                                const unsigned xterm = ((unsigned)e.x >> 3) & 1u, xleaf = ((unsigned)e.x >> 4) & 1u;
-                                const unsigned tok1 = (unsigned)e.x & ((unsigned)e.x >> 1) & 1u;
-                                const unsigned node2 = ((unsigned)e.x >> 2) & 1u;
-                                const unsigned filt = (unsigned)e.y;
-                                nocap |= (norm & (tok1 ^ 1u)) != 0;
-                                // a node after two bytes: n1 = '\n' leaves the walk inside "<0x0A>" after
-                                // its '<'; otherwise atom k+1 is consumed (the span k .. k+2)
-                                const unsigned has2 = norm & (wend ^ 1u) & node2;
-                                const unsigned nl1 = (unsigned)(n1 == '\n');
-                                const unsigned e2 = nl1 ? (unsigned)'0' : (n2 == '\n' ? (unsigned)'<' : n2);
-                                const unsigned more = has2 & (xleaf ^ 1u) & (nl1 | ((unsigned)(n2 != END) & (unsigned)(n2 != ' '))) &
-                                                      ((filt >> child_bit(e2)) & 1u);
-                                tk1 |= (norm & tok1) << u;
-                                tk2 |= (has2 & (nl1 ^ 1u) & xterm) << u;
-                                mark |= ((valid & special) | more) << (4 * g + u);
+                                for (int u = 0; u < 4; u++)   // the root table's entry of (b, n1)
+                                    e2r[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ? (int32_t)(tv.n_slots +
+                                             __builtin_amdgcn_perm(w0, n1w, 0x0C0C0000u | ((4u + (unsigned)u) << 8) | (unsigned)u)) : OOB);
+#pragma unroll
+                                for (int u = 0; u < 4; u++)   // the node after n2
+                                    e3[u] = trie_slotA(tv, ((r2 >> (8 * u + 7)) & 1u) ?
+                                            (int32_t)((e2r[u].x & BASE_MASK) + ((n2w >> (8 * u)) & 0xFFu)) : OOB);
+                                uint32_t c3 = 0, t3 = 0;
+#pragma unroll
+                                for (int u = 0; u < 4; u++) {
+                                    const unsigned n3 = (n3w >> (8 * u)) & 0xFFu;
+                                    const unsigned ok3 = ((r2 >> (8 * u + 7)) & 1u) & (unsigned)(e3[u].y == (e2r[u].y & 0x3FFFFFFF));
+                                    const unsigned leaf3 = ((unsigned)e3[u].x >> 30) & 1u;
+                                    const unsigned in3 = ((v3 & ~sp3) >> (8 * u + 7)) & 1u;
+                                    const unsigned ch3 = (((unsigned)e3[u].w >> child_bit(n3)) & 1u) | ((nl3 >> (8 * u + 7)) & 1u);
+                                    t3 |= (ok3 & ((unsigned)e3[u].x >> 31)) << (8 * u + 7);
+                                    c3 |= (ok3 & (leaf3 ^ 1u) & in3 & ch3) << (8 * u + 7);
+                                }
+                                mk = ((v0 & special) | (more & ~r2) | c3) & H;
+                                if (ballot(t3 != 0)) {   // a three-atom token ends at k0+3+u
+                                    uint32_t *q32 = reinterpret_cast<uint32_t *>(smem + gbase);
+#pragma unroll
+                                    for (int u = 0; u < 4; u++)
+                                        __hip_atomic_fetch_and(&q32[k0 + 3u + u],
+                                                               ~(((t3 >> (8 * u + 7)) & 1u) << 18),
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                }
                             }
-                            // end k0+1+u: tk1 bit u, and tk2 bit u-1 (u = 0: the previous lane's bit 3)
-                            const unsigned t2e = ((tk2 << 1) & 0xEu) | wave_shift_in((tk2 >> 3) & 1u, 0u);
-                            if (ballot((tk1 | t2e) != 0)) {
-                                // (lane l's dwords are 4l+1 .. 4l+4: lanes l, l+8, l+16, l+24 of a 32-lane group hit
-                                // one bank; a rotated order (r03) and a transposed one -- round q's lane l taking
-                                // end 64q+l+1, its bits gathered by ds_bpermute (r04) -- cost VGPR spills instead)
+                            const uint32_t t2e = (tk2 << 8) | wave_shift_in(tk2 >> 24, 0u);
+                            // end k0+1+u: bit 0 of byte u of d a one-atom token, bit 1 a two-atom one
+                            const uint32_t d = ((tk1 & H) >> 7) | ((t2e & H) >> 6);
+                            uint32_t *r32 = reinterpret_cast<uint32_t *>(smem + gbase);
+                            if (ballot(d != 0)) {
 #pragma unroll
                                 for (int u = 0; u < 4; u++)
-                                    __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~((((tk1 >> u) & 1u) << 16) | (((t2e >> u) & 1u) << 17)),
+                                    __hip_atomic_fetch_and(&r32[k0 + 1u + u], ~(((d >> (8 * u)) & 3u) << 16),
                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                             }
-                            if (ballot(nocap) && lane == 0) SSr(g).capb = 1;
+                            if (ballot((norm & ~tok1) != 0) && lane == 0) SSr(g).capb = 1;
                             // the slot's marked atoms, in order, into its fin[] (free until phase B)
-                            const unsigned mg = (mark >> (4 * g)) & 15u;
-                            const unsigned c = (unsigned)__builtin_popcount(mg);
+                            const unsigned c = (unsigned)__builtin_popcount(mk);
                             const unsigned incl = wave_incl_scan_add(c);
                             unsigned o = incl - c;
                             GL &Lg = grp(g);
 #pragma unroll
                             for (int u = 0; u < 4; u++)
-                                if ((mg >> u) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
+                                if ((mk >> (8 * u + 7)) & 1u) Lg.fin[o++].v = (uint8_t)(k0 + (unsigned)u);
                             nstart[g] = __builtin_amdgcn_readlane(incl, 63);
                         }
                     }
@@ -2735,8 +2191,9 @@ struct TokPass {
                     unsigned mloc = 0xFFFFu;
                     CutM lcut = 0;
                     // the branch-free pass where it costs no registers: not in the 512-byte pass (33 reads in flight:
-                    // 136 -> 194 VGPRs) nor in the lean pair's list-fed general kernel (2 more VGPR spills)
-                    constexpr bool CUT_FLAT = CUT_SEL && CMAX <= 32u && LEAN != 2;
+                    // 136 -> 194 VGPRs) nor in the lean pair's list-fed general kernel (2 more VGPR spills); cfg2 -0.8
+                    // to -1.1 % against the branch per boundary (profiles/cutuni_ab.log, the cut lever)
+                    constexpr bool CUT_FLAT = CMAX <= 32u && LEAN != 2;
 #pragma unroll 4
                     for (int k = (int)CMAX - 1; k >= 0; k--) {
                         const unsigned i = c0 + 1u + (unsigned)k;
@@ -2778,26 +2235,24 @@ struct TokPass {
                         rs = min(rs, gshl<LW, 16>(rs, na));
                         rs = min(rs, gshl<LW, 32>(rs, na));
                     }
-                    if constexpr (NEAR_CUT) {
-                        // the NEAREST cut to c0 instead of the first one after it: snapping up made the longest
-                        // chunk of a wave ~2x the mean on cfg4's long words (a 256-atom window: 36.7 ends
-                        // against C = 17), and the wave steps as long as its longest chunk; nearest-cut
-                        // rounding is monotone in c0, so the chunks still tile (0, na]
-                        unsigned lastc = 0;   // (0 is a cut)
-                        if constexpr (CMAX > 32u) lastc = cut ? c0 + (63u - (unsigned)__builtin_clzll(cut)) : 0u;
-                        else lastc = cut ? c0 + (31u - (unsigned)__builtin_clz((unsigned)cut)) : 0u;
-                        unsigned pm = lastc;   // max over the lanes <= d of the group, then shifted: lanes < d
-                        pm = max(pm, gshr<LW, 1>(pm, 0u));
-                        pm = max(pm, gshr<LW, 2>(pm, 0u));
-                        pm = max(pm, gshr<LW, 4>(pm, 0u));
-                        pm = max(pm, gshr<LW, 8>(pm, 0u));
-                        if constexpr (LW == 64) {
-                            pm = max(pm, gshr<LW, 16>(pm, 0u));
-                            pm = max(pm, gshr<LW, 32>(pm, 0u));
-                        }
-                        const unsigned prevc = gshr<LW, 1>(pm, 0u);
-                        rs = (c0 - prevc < rs - c0) ? prevc : rs;
+                    // the NEAREST cut to c0 instead of the first one after it: snapping up made the longest
+                    // chunk of a wave ~2x the mean on cfg4's long words (a 256-atom window: 36.7 ends
+                    // against C = 17), and the wave steps as long as its longest chunk; nearest-cut
+                    // rounding is monotone in c0, so the chunks still tile (0, na]
+                    unsigned lastc = 0;   // (0 is a cut)
+                    if constexpr (CMAX > 32u) lastc = cut ? c0 + (63u - (unsigned)__builtin_clzll(cut)) : 0u;
+                    else lastc = cut ? c0 + (31u - (unsigned)__builtin_clz((unsigned)cut)) : 0u;
+                    unsigned pm = lastc;   // max over the lanes <= d of the group, then shifted: lanes < d
+                    pm = max(pm, gshr<LW, 1>(pm, 0u));
+                    pm = max(pm, gshr<LW, 2>(pm, 0u));
+                    pm = max(pm, gshr<LW, 4>(pm, 0u));
+                    pm = max(pm, gshr<LW, 8>(pm, 0u));
+                    if constexpr (LW == 64) {
+                        pm = max(pm, gshr<LW, 16>(pm, 0u));
+                        pm = max(pm, gshr<LW, 32>(pm, 0u));
                     }
+                    const unsigned prevc = gshr<LW, 1>(pm, 0u);
+                    rs = (c0 - prevc < rs - c0) ? prevc : rs;
                     const unsigned re = gshl<LW, 1>(rs, na);
                     if (DPT_STOP == 25) return;   // diagnostic: cut points only
 
@@ -2808,9 +2263,11 @@ struct TokPass {
                     unsigned T = 0;                  // tokens of the chunk: the pieces' costs
                     // (reading the next position's first candidates a step ahead, or two candidates per inner
                     // iteration, measured slower: r03y, r03)
-                    unsigned nrec = 0;   // LOOP_UNI: the wave's longest chunk
-                    if constexpr (LOOP_UNI) nrec = wave_umax(re - min(rs, re));   // (rs <= re: the chunks tile (0, na])
-                    while (LOOP_UNI ? nrec-- != 0u : ballot(i < re) != 0ull) {
+                    // the loop counts the wave's longest chunk down in an SGPR: its state is then not copied across the loop
+                    // edge, as it is with the ballot of the lanes' own guard per step (cfg2 -1.4 to -2.0 %,
+                    // profiles/cutuni_ab.log, the uni lever; the C1 walk below alike)
+                    unsigned nrec = wave_umax(re - min(rs, re));   // (rs <= re: the chunks tile (0, na])
+                    while (nrec-- != 0u) {
                         if (i < re) {
                             i++;
                             const unsigned r = nxt;
@@ -2935,9 +2392,8 @@ struct TokPass {
                         unsigned ii = re, k = walk ? tb + T : tb, A = left_of_q ? ls1 : 0u, Ls = ls1;
                         unsigned pend = rec32[re] & 0x7FFu;
                         bool inp1 = true;
-                        unsigned nst = 0;   // LOOP_UNI: the wave's longest walk
-                        if constexpr (LOOP_UNI) nst = wave_umax(k - tb);
-                        while (LOOP_UNI ? nst-- != 0u : ballot(k > tb) != 0ull) {
+                        unsigned nst = wave_umax(k - tb);   // the wave's longest walk (counted down in an SGPR, as the recurrence)
+                        while (nst-- != 0u) {
                             if (k > tb) {
                                 const unsigned rr = rec32[ii];
                                 const unsigned cpi = rr & 0x7FFu;
@@ -3037,29 +2493,11 @@ struct TokPass {
                         }
                         return res;
                     };
-                    // the last cut at or before c (0 is a cut)
-                    auto prevcut = [&](unsigned c) -> unsigned {
-                        unsigned res = 0;
-#pragma unroll
-                        for (int r = 0; r < (CH + 64) / 64; r++) {
-                            const unsigned lo = 64u * (unsigned)r;
-                            const uint64_t keep = c < lo ? 0ull : (c >= lo + 63u ? ~0ull : (~0ull >> (63u - (c - lo))));
-                            const uint64_t m = cm[r] & keep;
-                            res = m ? lo + 63u - (unsigned)__builtin_clzll(m) : res;
-                        }
-                        return res;
-                    };
-                    // chunk bounds snapped to the NEAREST cut (as forward_lanes, DPT_NEAR_CUT): monotone in c, so
-                    // lane l's end is lane l+1's start
-                    auto snap = [&](unsigned c) -> unsigned {
-                        const unsigned nx = nextcut(c);
-                        if constexpr (!NEAR_CUT64) return nx;
-                        const unsigned pv = prevcut(c);
-                        return (c - pv < nx - c) ? pv : nx;
-                    };
+                    // chunk bounds snapped to the NEXT cut (monotone in c, so lane l's end is lane l+1's start); the nearest
+                    // cut, forward_lanes' rule, measured 0.9 % slower on BLOOM here (r05e)
                     const unsigned C = (na + 63u) >> 6;   // (odd chunk lengths: -0.5 %, r03ad)
                     const unsigned c0 = min(lane * C, na), c1 = min(c0 + C, na);
-                    const unsigned rs = snap(c0);
+                    const unsigned rs = nextcut(c0);
                     // (c1 = the next lane's c0: its start, by wave_shl:1; lane 63 ends at na)
                     const unsigned re = (unsigned)__builtin_amdgcn_update_dpp((int)na, (int)rs, 0x130, 0xF, 0xF, false);
                     (void)c1;
@@ -3166,9 +2604,8 @@ struct TokPass {
 #pragma unroll
                 for (int g = 0; g < NG; g++) capb |= uni(SSr(g).capb);
                 if constexpr (LEAN == 1) {   // (capless windows only: the others were deferred after A)
-                    if constexpr (DPT_LEAN_SETPRIO != 0) __builtin_amdgcn_s_setprio(DPT_LEAN_SETPRIO);
+                    // (a raised wave priority around it: 125k -3.8 %, but cfg2 +0.4 % -- profiles/lean_ab.log, third session)
                     forward_lanes();
-                    if constexpr (DPT_LEAN_SETPRIO != 0) __builtin_amdgcn_s_setprio(0);
                     lane_mode = true;
                 } else if (!PLAIN && a.edges) {
                     if (!capb) forward(T_{}, C2_{}); else if (uncapped) forward(T_{}, C1_{}); else forward(T_{}, C0_{});
@@ -3305,17 +2742,11 @@ tokenize_lean_kernel(KernArgs ka) {
     TokPass<SMALL_CH, 16, false, false, SW, true, false, -1, LEAN>::body(blockIdx.x);
 }
 
-// ------------------------------------------------------------------ compaction
-
 // ------------------------------------------------------------------ finish: offsets + CSR ids in one pass
 
 constexpr unsigned FIN_U = 8;                 // loads in flight per thread of the copy (8 / 12 beat 4, 16 and 32: r04n)
 constexpr unsigned FIN_THREADS = 512;         // threads per finish block (>= FIN_BATCH): all of them copy
 constexpr unsigned FIN_MAP_ROWS = 8192;       // s_map entries (u8 string index): rows of 64 ids, coarser past 512k ids
-#ifndef DPT_FIN_PIPE    // A/B knob: the finish copy issues round r+1's loads before round r's stores
-#define DPT_FIN_PIPE 1
-#endif
-constexpr bool FIN_PIPE = DPT_FIN_PIPE != 0;
 constexpr unsigned SCAN_THREADS = 1024;       // threads of the batch-scan block
 constexpr uint64_t FIN_TARGET_BLOCKS = 2048;  // small batches: each batch's copy is split over slices until the grid has this many blocks
 constexpr uint64_t FIN_MAX_SLICES = 8;
@@ -3339,7 +2770,6 @@ __device__ __forceinline__ uint64_t block_incl_scan_add64(uint64_t v, uint64_t *
     __syncthreads();
     return incl;
 }
-
 
 // Batch prefixes: the tokenize passes add every string's count to its FIN_BATCH-string batch's sum
 // as the string finishes (one no-return atomic per string, dpt_kernels.hip / dpt_long.hip); this ONE
@@ -3543,7 +2973,7 @@ __global__ void __launch_bounds__(FIN_THREADS) finish_kernel(FinishArgs f) {
         }
     };
     constexpr uint64_t STEP = (uint64_t)FIN_THREADS * U;
-    if (FIN_PIPE && f.slices > 1 && total < (1ull << 30)) {
+    if (f.slices > 1 && total < (1ull << 30)) {
         // Calls split into slices (under ~512k strings, the strong-scaling shards): the next round's
         // loads go out before this round's stores -- a load waits for every older vector-memory op of
         // the wave, stores included, so loads behind the stores put a store's latency on every round.

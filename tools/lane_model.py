@@ -7,8 +7,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "dp-tokenization_amd"), os.path.join(RO
 from oracle import ref_port
 
 FRESH = 31
-NEAR_CUT = True   # mirrors dpt_kernels.hip DPT_NEAR_CUT
-NEAR_CUT64 = False   # ... and NEAR_CUT64 (the 64-lane push recurrence)
+NEAR_CUT = True   # what the kernel does (dpt_kernels.hip forward_lanes: chunk starts snap to the nearest cut); False models the next cut
+NEAR_CUT64 = False   # ... and the 64-lane push recurrence (forward_lanes64), which keeps the next cut
 
 def relax(sj, span):
     a1 = sj + 64
@@ -76,7 +76,7 @@ def model(text, vocab, verbose=False, fold=True, stats=None):
         lanes[d]["lc"] = c0 + cut.bit_length() - 1 if cut else 0   # the lane's last cut
     for d in range(16):
         lanes[d]["rs"] = min([l["fc"] for l in lanes[d:]])
-    if NEAR_CUT:   # the kernel's DPT_NEAR_CUT: the nearest cut to c0 (ties: the later one)
+    if NEAR_CUT:   # the kernel's rule: the nearest cut to c0 (ties: the later one)
         for d in range(16):
             c0 = lanes[d]["c0"]
             prev = max([l["lc"] for l in lanes[:d]] + [0])
@@ -241,7 +241,7 @@ def model64(text, vocab, verbose=False):
     nextcut = lambda c: next(p for p in range(c, na + 1) if cut[p])
     prevcut = lambda c: max(p for p in range(0, min(c, na) + 1) if cut[p])
 
-    def snap(c):   # the kernel's nearest-cut rule (DPT_NEAR_CUT), else the next cut
+    def snap(c):   # forward_lanes' nearest-cut rule with NEAR_CUT64, else the next cut (the kernel's)
         nx = nextcut(c)
         if not NEAR_CUT64:
             return nx

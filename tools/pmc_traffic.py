@@ -10,7 +10,10 @@ keyed by the sha256 of the kernel sources so bench.py only reports it for the sa
 import csv, glob, hashlib, json, os, re, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = ["dpt_kernels.hip", "dpt_long.hip", "dpt_wave.h", "dpt_api.cpp", "dpt_vocab.cpp", "dpt_internal.h"]
+# the dpt_kernels.hip unit -- every file under csrc/ it reaches by quoted #include, in include order
+# (tests/test_traffic_key.py holds the list to that) -- then the table builders the kernels read
+SRC = ["dpt_kernels.hip", "dpt_internal.h", "dpt_bpe_table.h", "dpt_lean_hint.h", "dpt_wave.h", "dpt_long.hip",
+       "dpt_tok_knobs.h", "dpt_tok_lds.h", "dpt_api.cpp", "dpt_vocab.cpp"]
 
 
 def normalized(src: str) -> str:

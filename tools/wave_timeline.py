@@ -3,8 +3,8 @@
     python tools/wave_timeline.py [ascii|s2orc] n1 n2 ...        (default: ascii 125000 250000 1000000)
 
 Every wave of the persistent grid stamps s_memrealtime (100 MHz, one clock for the chip) at its first
-instruction, at the end of each slot round (with the round's busy slots) and at its exit (WST_REC in
-dpt_kernels.hip).  Per call size this splits the pass's span T into
+instruction, at the end of each slot round (with the round's busy slots) and at its exit (WST_REC:
+dpt_tok_lds.h, recorded by TokPass::body in dpt_kernels.hip). Per call size this splits the pass's span T into
   ramp   mean over waves of (first instruction - the grid's first instruction)
   tail   mean over waves of (the grid's last exit - the wave's exit)
   work   the rest (mean wave span), and the work into its rounds: mean duration of round k, of rounds with
