@@ -622,6 +622,83 @@ int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint6
     return DPT_OK;
 }
 
+// The option and size checks of the packing calls: collate's, with DPT_COLLATE_PAD_LEFT unknown here.
+constexpr uint32_t PACK_OTHERS = DPT_COLLATE_TRUNC_LEFT | DPT_COLLATE_I64 | DPT_PACK_MASK_FIRST;
+static int pack_rows(dpt::CollateRows *r, const dpt_pack_opts *opts, uint64_t n_str, void *input_ids, void *labels) {
+    if (const int rc = collate_rows(r, opts, DPT_COLLATE_BOS | DPT_COLLATE_EOS, "BOS / EOS", PACK_OTHERS, n_str, input_ids, nullptr, labels,
+                                    nullptr))
+        return rc;
+    if (n_str >= (1ull << 31)) return fail(DPT_E_ARG, "n_str over 2^31 - 1");
+    return DPT_OK;
+}
+
+int dpt_pack_sizes(const uint64_t *off, const uint64_t *counts, const int32_t *status, uint64_t n_str, const dpt_pack_opts *opts,
+                   uint32_t *lengths, void *hip_stream) {
+    if (!off) return fail(DPT_E_ARG, "null off");
+    if (!opts) return fail(DPT_E_ARG, "null opts");
+    if (!lengths) return fail(DPT_E_ARG, "null lengths");
+    dpt::CollateRows r{};
+    if (const int rc = pack_rows(&r, opts, n_str, nullptr, nullptr)) return rc;
+    const uint32_t n_special = (uint32_t)__builtin_popcount(opts->flags & (DPT_COLLATE_BOS | DPT_COLLATE_EOS));
+    const hipError_t e = dpt::launch_pack_sizes({nullptr, off, counts, status}, (uint32_t)n_str, r.row_len - n_special, n_special, lengths,
+                                                (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "pack sizes launch");
+    return DPT_OK;
+}
+
+int dpt_pack_plan_workspace(uint64_t n_str, uint64_t *bytes) {
+    if (!bytes) return fail(DPT_E_ARG, "null bytes");
+    if (n_str >= (1ull << 31)) return fail(DPT_E_ARG, "n_str over 2^31 - 1");
+    *bytes = dpt::pack_plan_workspace_bytes(n_str);
+    return DPT_OK;
+}
+
+int dpt_pack_plan(const uint64_t *tok_off, uint64_t n_str, uint32_t row_len, uint64_t row_cap, uint32_t *str_row, uint32_t *str_col,
+                  uint32_t *row_first, uint32_t *row_fill, uint64_t *n_rows, void *ws, uint64_t ws_bytes, void *hip_stream) {
+    if (!tok_off) return fail(DPT_E_ARG, "null tok_off");
+    if (!n_rows) return fail(DPT_E_ARG, "null n_rows");
+    if (row_len == 0) return fail(DPT_E_ARG, "row_len is 0");
+    if (row_len > (1u << 31)) return fail(DPT_E_ARG, "row_len over 2^31");
+    if (n_str >= (1ull << 31)) return fail(DPT_E_ARG, "n_str over 2^31 - 1");
+    if (row_cap >= (1ull << 31)) return fail(DPT_E_ARG, "row_cap over 2^31 - 1");
+    if (n_str && !ws) return fail(DPT_E_ARG, "null ws");
+    if ((uintptr_t)ws % 4) return fail(DPT_E_ARG, "ws is not 4-byte aligned");
+    if (ws_bytes < dpt::pack_plan_workspace_bytes(n_str)) return fail(DPT_E_CAP, "ws_bytes under dpt_pack_plan_workspace(n_str)");
+    const dpt::PackPlanLaunch p{tok_off, (uint32_t)n_str, row_len, (uint32_t)row_cap, str_row, str_col, row_first, row_fill, n_rows, ws};
+    const hipError_t e = dpt::launch_pack_plan(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "pack plan launch");
+    return DPT_OK;
+}
+
+int dpt_pack_write(const dpt_collate_side *side, uint64_t n_str, const uint64_t *tok_off, const uint32_t *row_first,
+                   const uint64_t *n_rows, uint64_t row_cap, const dpt_pack_opts *opts, void *input_ids, void *position_ids,
+                   void *segment_ids, void *labels, void *hip_stream) {
+    if (!side) return fail(DPT_E_ARG, "null side");
+    if (!side->ids) return fail(DPT_E_ARG, "null side->ids");
+    if (!side->off) return fail(DPT_E_ARG, "null side->off");
+    if (!tok_off) return fail(DPT_E_ARG, "null tok_off");
+    if (!row_first) return fail(DPT_E_ARG, "null row_first");
+    if (!n_rows) return fail(DPT_E_ARG, "null n_rows");
+    if (!opts) return fail(DPT_E_ARG, "null opts");
+    if (!input_ids) return fail(DPT_E_ARG, "null input_ids");
+    dpt::PackWriteLaunch p{};
+    if (const int rc = pack_rows(&p.r, opts, n_str, input_ids, labels)) return rc;
+    if (row_cap >= (1ull << 31)) return fail(DPT_E_ARG, "row_cap over 2^31 - 1");
+    p.src = {side->ids, side->off, side->counts, side->status};
+    p.tok_off = tok_off; p.row_first = row_first; p.n_rows = n_rows; p.row_cap = row_cap;
+    p.position_ids = position_ids; p.segment_ids = segment_ids;
+    const hipError_t e = dpt::launch_pack_write(p, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "pack write launch");
+    return DPT_OK;
+}
+
+int dpt_debug_pack_geometry(uint32_t *strings_per_block, uint32_t *grid_cap) {
+    if (!strings_per_block || !grid_cap) return fail(DPT_E_ARG, "null argument");
+    *strings_per_block = dpt::PACK_BLOCK_STRINGS;
+    *grid_cap = dpt::PACK_GRID_CAP;
+    return DPT_OK;
+}
+
 // The checks both word-compare calls make of their sides, flags and n_str; 0 with p's common members filled.
 static int words_args(dpt::WordsLaunch *p, const dpt_word_side *a, const dpt_word_side *b, uint64_t n_str, int flags,
                       int32_t *wc_status) {

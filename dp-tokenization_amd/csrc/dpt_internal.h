@@ -356,6 +356,35 @@ struct CollatePairLaunch {     // rows of two segments
 };
 hipError_t launch_collate_pair(const CollatePairLaunch &p, hipStream_t stream);
 
+// The launches of the packing kernels (dpt_packing.hip; include/dpt.h dpt_pack_sizes, dpt_pack_plan, dpt_pack_write):
+// every pointer a device pointer, the arguments already checked (n_str, row_cap < 2^31, the options as collate's).
+constexpr uint32_t PACK_BLOCK_STRINGS = 1024;   // B: the strings of one plan block
+constexpr uint32_t PACK_GRID_CAP = 512;         // the plan's blocks at most (two of B threads per CU); more chunks: they stride
+uint64_t pack_plan_workspace_bytes(uint64_t n_str);
+hipError_t launch_pack_sizes(const CollateSide &src, uint32_t n_str, uint32_t room, uint32_t n_special, uint32_t *lengths, hipStream_t stream);
+struct PackPlanLaunch {
+    const uint64_t *tok_off;   // n_str + 1
+    uint32_t n_str;
+    uint32_t row_len;
+    uint32_t row_cap;
+    uint32_t *str_row, *str_col;       // nullable, n_str each
+    uint32_t *row_first, *row_fill;    // nullable, row_cap + 1 and row_cap
+    uint64_t *n_rows;
+    void *ws;                  // pack_plan_workspace_bytes(n_str)
+};
+hipError_t launch_pack_plan(const PackPlanLaunch &p, hipStream_t stream);
+struct PackWriteLaunch {
+    CollateSide src;
+    CollateRows r;             // (mask, lengths unused; flags: DPT_COLLATE_* and DPT_PACK_MASK_FIRST)
+    const uint64_t *tok_off;   // n_str + 1
+    const uint32_t *row_first; // row_cap + 1
+    const uint64_t *n_rows;
+    uint64_t row_cap;
+    void *position_ids;        // nullable
+    void *segment_ids;         // nullable
+};
+hipError_t launch_pack_write(const PackWriteLaunch &p, hipStream_t stream);
+
 // One launch of the per-word comparison kernel (dpt_words.hip; include/dpt.h dpt_word_compare_sizes,
 // dpt_word_compare_write): every pointer a device pointer, the arguments already checked.
 struct WordsLaunch {

@@ -49,6 +49,8 @@ class CollateOpts(ctypes.Structure):
 
 COLLATE_BOS, COLLATE_EOS, COLLATE_PAD_LEFT, COLLATE_TRUNC_LEFT, COLLATE_I64 = 1, 2, 4, 8, 16
 COLLATE_SEP, COLLATE_MASK_A, COLLATE_TRIM_A_FIRST = 32, 64, 128   # dpt_collate_pair only
+PACK_MASK_FIRST = 256   # dpt_pack_write only
+PACK_NONE = 0xFFFFFFFF
 
 
 class CollateSide(ctypes.Structure):
@@ -152,6 +154,12 @@ CALLS = {
     # the two tokenizations compared word by word
     "dpt_word_compare_sizes": (I32, [ctypes.POINTER(WordSide), ctypes.POINTER(WordSide), U64, I32, P, P, P, P, P, P]),
     "dpt_word_compare_write": (I32, [ctypes.POINTER(WordSide), ctypes.POINTER(WordSide), U64, I32] + [P] * 14),
+    # sequence packing of an encoded batch into fixed rows
+    "dpt_pack_sizes": (I32, [P, P, P, U64, ctypes.POINTER(CollateOpts), P, P]),
+    "dpt_pack_plan_workspace": (I32, [U64, PU64]),
+    "dpt_pack_plan": (I32, [P, U64, U32, U64, P, P, P, P, P, P, U64, P]),
+    "dpt_pack_write": (I32, [ctypes.POINTER(CollateSide), U64, P, P, P, U64, ctypes.POINTER(CollateOpts), P, P, P, P, P]),
+    "dpt_debug_pack_geometry": (I32, [ctypes.POINTER(U32), ctypes.POINTER(U32)]),
 }
 # These came within ABI 6: a libdpt.so from before them (DPT_LIB) lacks the symbols and still encodes;
 # ``Detok`` then raises (has_decode).
@@ -177,6 +185,9 @@ OPTIONAL_BPE = set(BPE_CALLS)
 # And the word-compare calls; ``words.compare_device`` raises without them (has_words).
 WORDS_CALLS = {name: CALLS[name][1] for name in CALLS if "_word_compare_" in name}
 OPTIONAL_WORDS = set(WORDS_CALLS)
+# And the packing calls; ``packing.*_device`` raise without them (has_packing).
+PACKING_CALLS = {name: CALLS[name][1] for name in CALLS if "_pack_" in name}
+OPTIONAL_PACKING = set(PACKING_CALLS)
 
 
 def lib():
@@ -196,7 +207,7 @@ def lib():
         raise DptError(f"HIP extension not built: {LIB_PATH} missing (run __graft_entry__.build())")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in CALLS.items():
-        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL | OPTIONAL_BPE | OPTIONAL_WORDS and not hasattr(L, name):
+        if name in OPTIONAL | OPTIONAL_LATER | OPTIONAL_PRETOK | OPTIONAL_BYTELEVEL | OPTIONAL_BPE | OPTIONAL_WORDS | OPTIONAL_PACKING and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -242,6 +253,12 @@ def has_words() -> bool:
     """The loaded library exports the word-compare calls."""
     L = lib()
     return all(hasattr(L, name) for name in WORDS_CALLS)
+
+
+def has_packing() -> bool:
+    """The loaded library exports the packing calls."""
+    L = lib()
+    return all(hasattr(L, name) for name in PACKING_CALLS)
 
 
 def wave_grid(n_str: int, waves: int = 4) -> int:

@@ -45,6 +45,9 @@ MI355X engine.  Same names, argument meaning and error behaviour:
 * ``dp_tokenize.batch_pair_model_inputs(sources, targets, ...) -> dict``: source + target rows as padded
   ``input_ids`` / ``attention_mask`` / ``labels`` tensors on the GPU (one dpt_encode_padded + one dpt_collate_pair;
   what reference main_biomed_translation.py:138-145 and its collator, :104-124, build on the host); see its docstring.
+* ``dp_tokenize.batch_packed_inputs(List[str], max_length, ...) -> dict``: the batch packed in order into rows of
+  ``max_length`` tokens on the GPU, with ``position_ids`` / ``segment_ids`` and every string's row and column
+  (dpt_encode_padded + dpt_pack_sizes / dpt_pack_plan / dpt_pack_write); see its docstring.
 * ``decode_dp_tokenization.batch(List[List[int]]) -> List[str]`` and ``dp_tokenize.batch_roundtrip(List[str])
   -> List[Optional[int]]``: the tokenizer's own decode of a batch, and the caller's round-trip assert
   (reference main_analyze_s2orc.py:84-87), each in one GPU launch; ``decode_dp_tokenization`` itself stays
@@ -290,6 +293,21 @@ a row with a failed side is all pad, and ``status_source`` / ``status_target`` (
 ValueError when the two lists differ in length."""
 
 
+_PACKED_INPUTS_DOC = """``dp_tokenize.batch_packed_inputs(texts, max_length, add_bos=False, add_eos=False, labels=False,
+mask_first=False, truncation_side="right", errors="raise") -> dict``: the batch packed into rows of ``max_length``
+tokens on the GPU -- consecutive strings share a row, in order, no sequence split (include/dpt.h dpt_pack_plan has the
+rule).  The packed text goes up, dpt_encode_padded and the three packing calls run back to back, and nothing comes
+back but the statuses and the number of rows.  ``input_ids`` / ``position_ids`` / ``segment_ids`` (/ ``labels``, pad
+positions -100) are int64 ``[n_rows, max_length]`` tensors on the engine's device: the position of a token inside its own
+sequence, and per row 1, 2, ... per sequence with 0 at pad (the attention mask is ``segment_ids != 0``; sequences of a
+row must not attend to each other).  ``mask_first``: the labels are -100 on the first token of every sequence.  Also
+returned: ``lengths``, ``str_row``, ``str_col`` (int32 per string; ``str_row`` -1: the string holds no token and is not
+placed), ``row_first``, ``row_fill`` (int32 per row) and ``n_rows``.  A string longer than ``max_length`` is truncated as
+in ``batch_model_inputs``; the pad id and ``add_bos`` / ``add_eos`` are that call's too.  ``errors="raise"``: what
+``dp_tokenize.batch`` raises, for the first failed string in order; ``"mask"``: a failed string is not placed, and
+``status`` (int32 per string) is returned too."""
+
+
 def _special_ids(tokenizer):
     """(bos, eos, pad) ids of a tokenizer object: bos / eos None when it has none; pad is its ``pad_token_id``,
     else its ``eos_token_id``, else 0."""
@@ -300,7 +318,7 @@ def _special_ids(tokenizer):
 
 
 def _model_inputs_surface(engine, tokenizer, pack_batch):
-    """(``batch_model_inputs``, ``batch_pair_model_inputs``) over one adapter's packing: ``pack_batch(texts) -> (text, offs, mode, cut, none,
+    """(``batch_model_inputs``, ``batch_pair_model_inputs``, ``batch_packed_inputs``) over one adapter's packing: ``pack_batch(texts) -> (text, offs, mode, cut, none,
     outcome)``, the buffers of its ``batch`` call with ``none`` / ``outcome`` as ``_batch_spans`` takes them."""
 
     def encode_padded(texts):
@@ -399,9 +417,28 @@ def _model_inputs_surface(engine, tokenizer, pack_batch):
                 raise_for_status(int(st_h[n + i]), targets[i])
         return out
 
+    def batch_packed_inputs(texts, max_length, add_bos=False, add_eos=False, labels=False, mask_first=False,
+                            truncation_side="right", errors="raise"):
+        import torch
+        from dptok.packing import packed_inputs
+        bos, eos, pad = checked_specials(errors, add_bos, add_eos)
+        texts = list(texts)
+        dev, ids, d_offs, st, counts, _ = encode_padded(texts)
+        with torch.cuda.device(dev):
+            out = packed_inputs(ids, d_offs, st, counts, max_length=max_length, labels=labels, mask_first=mask_first, pad_id=pad,
+                                bos_id=bos if add_bos else None, eos_id=eos if add_eos else None,
+                                truncation_side=truncation_side)
+            if errors == "mask":
+                out["status"] = st
+                return out
+            for i in np.flatnonzero(st.cpu().numpy()).tolist()[:1]:
+                raise_for_status(int(st[i]), texts[i])
+        return out
+
     batch_model_inputs.__doc__ = _MODEL_INPUTS_DOC
     batch_pair_model_inputs.__doc__ = _PAIR_INPUTS_DOC
-    return batch_model_inputs, batch_pair_model_inputs
+    batch_packed_inputs.__doc__ = _PACKED_INPUTS_DOC
+    return batch_model_inputs, batch_pair_model_inputs, batch_packed_inputs
 
 
 def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, spans_many, inputs_surface, decode_batch,
@@ -414,7 +451,7 @@ def _finish_adapter(dp_tokenize, decode_dp_tokenization, engine, encode_many, sp
     dp_tokenize.batch_roundtrip = batch_roundtrip
     dp_tokenize.batch = encode_many
     dp_tokenize.batch_spans = spans_many
-    dp_tokenize.batch_model_inputs, dp_tokenize.batch_pair_model_inputs = inputs_surface
+    dp_tokenize.batch_model_inputs, dp_tokenize.batch_pair_model_inputs, dp_tokenize.batch_packed_inputs = inputs_surface
     dp_tokenize.engine = engine
     for name, value in extra.items():
         setattr(dp_tokenize, name, value)
@@ -698,7 +735,7 @@ def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab,
                 out[i] = (sel_word[so[k]:so[k + 1]], [a_sel[ao[d]:ao[d + 1]] for d in q], [b_sel[bo[d]:bo[d + 1]] for d in q])
         return out
 
-    def batch_compare(texts: Sequence[str], words: bool = False) -> dict:
+    def batch_compare(texts: Sequence[str], words: bool = False, pack_length: Optional[int] = None) -> dict:
         """The shortest tokenization against the tokenizer's own, per string: ``dp_lengths`` and ``default_lengths``
         (int64 arrays: the ``len`` of ``dp_tokenize.batch`` and of ``tokenizer.encode``), ``improved`` (the mask
         dp < default), and ``dp_word_counts`` / ``default_word_counts``: per string the tokens in each word of its
@@ -711,7 +748,11 @@ def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab,
         word-index streams: ``improved_word_ids`` (the words with fewer DP tokens than default tokens, ascending),
         ``improved_tokens`` (per improved word the DP's token strings) and ``worse_tokens`` (the default's, of the same
         words) -- the reference frame's two columns, ``[]`` for a string without an improved word and None for a string
-        that went to the host tokenizer on either side.  Every other key holds what it holds without it."""
+        that went to the host tokenizer on either side.  Every other key holds what it holds without it.
+
+        ``pack_length=L`` adds ``dp_rows`` and ``default_rows``: the rows of L tokens each side's lengths pack into, in
+        order and without splitting a sequence (dptok/packing.py ``plan_lengths``; a sequence longer than L counts as L
+        tokens, as truncated) -- what a shorter tokenization saves a training loop that packs its batches."""
         texts = list(texts)
         spans = dp_tokenize.batch_spans(texts)
         got, default_words = device_default(texts, True)
@@ -722,6 +763,11 @@ def _default_surface(dp_tokenize, tokenizer, split_atoms, make_table, bpe_vocab,
         df_words = [None if w is None else np.bincount(w.astype(np.int64)) if len(w) else np.zeros(0, dtype=np.int64) for w in default_words]
         out = {"dp_lengths": dp_len, "default_lengths": df_len, "improved": dp_len < df_len, "dp_word_counts": dp_words,
                "default_word_counts": df_words}
+        if pack_length is not None:
+            from dptok.packing import plan_lengths
+            with torch.cuda.device(dev):
+                for key, lens in (("dp_rows", dp_len), ("default_rows", df_len)):
+                    out[key] = plan_lengths(torch.from_numpy(np.minimum(lens, int(pack_length))).to(dev), int(pack_length))["n_rows"]
         if words:
             found = device_words(texts)
             out["improved_word_ids"] = [None if f is None else f[0] for f in found]

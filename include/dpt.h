@@ -462,6 +462,73 @@ int dpt_collate_pair(const dpt_collate_side *a, const dpt_collate_side *b, uint6
                      void *token_type_ids, uint32_t *lengths, uint32_t *b_start, void *hip_stream);
 
 /*
+ * Sequence packing: consecutive strings of an encoded batch packed into rows of L = row_len tokens, in order and
+ * greedily, no sequence split -- the rows a training loop makes of dpt_collate's one-row-per-string output when most
+ * of that is padding (S2ORC abstracts of a few hundred tokens against max_length = 2048, reference
+ * main_analyze_s2orc.py:68, :209).  Added within ABI 6 (DPT_ABI_VERSION unchanged): a binding that may meet an older
+ * libdpt.so probes for the symbols.  Three calls, in the dpt_decode_sizes -> dpt_decode pattern (the prefix sum
+ * between them is the caller's):
+ *
+ * 1. dpt_pack_sizes: lengths[s] (uint32) of every string, exactly dpt_collate's lengths: with the source described by
+ *    (off, counts, status) as there, n_special = the number of DPT_COLLATE_BOS / DPT_COLLATE_EOS set,
+ *      len[s] = 0 when status[s] != 0, else min(n, L - n_special) + n_special          (so len[s] <= L)
+ *    The caller takes the exclusive prefix sum of lengths into tok_off (uint64, n_str + 1 entries; tok_off[0] need
+ *    not be 0).
+ * 2. dpt_pack_plan: the placement, from tok_off alone (no ids, no vocabulary: any lengths <= row_len pack this way).
+ *    A string with len[s] == 0 -- a failed string, an empty string without specials -- is never placed.  The others:
+ *      r = -1; fill = L + 1
+ *      for s in 0..n_str-1, len[s] > 0:
+ *          if fill + len[s] > L: r += 1; fill = 0; row_first[r] = s
+ *          str_row[s] = r; str_col[s] = fill; fill += len[s]
+ *      n_rows = r + 1
+ *    str_row[s] = DPT_PACK_NONE and str_col[s] = 0 for an unplaced string; row_fill[r] = the tokens of row r;
+ *    row_first[r] = n_str for n_rows <= r <= row_cap and row_fill[r] = 0 for n_rows <= r < row_cap.  str_row, str_col
+ *    (uint32, n_str entries), row_first (uint32, row_cap + 1 entries) and row_fill (uint32, row_cap entries) are
+ *    nullable; entries of rows >= row_cap (row_first: > row_cap) are not written, and *n_rows (uint64, on the device)
+ *    always reports the need, also above row_cap.  ws: dpt_pack_plan_workspace(n_str) bytes of the caller's device
+ *    memory, 4-byte aligned (at most 16 bytes per string plus a constant; nullable when n_str == 0); DPT_E_CAP when
+ *    ws_bytes is smaller.
+ * 3. dpt_pack_write: the rows r < min(n_rows, row_cap), elements and row_stride as in dpt_collate:
+ *      input_ids:     the sequences [bos_id] + kept + [eos_id] of the row's placed strings, back to back from column
+ *                     0, pad_id in the rest; kept = the first len - n_special tokens, or with DPT_COLLATE_TRUNC_LEFT
+ *                     the last
+ *      position_ids:  the position inside its own sequence, from 0; 0 at pad
+ *      segment_ids:   s - row_first[r] + 1 on every position of string s, 0 at pad (distinct per sequence of a row;
+ *                     the attention mask is segment_ids != 0)
+ *      labels:        the id inside a sequence, ignore_id at pad; with DPT_PACK_MASK_FIRST ignore_id also on position
+ *                     0 of every sequence (the token no earlier token of its own sequence predicts)
+ *    Rows [n_rows, row_cap) are all pad: 0, 0 and ignore_id.  Rows >= row_cap, elements [row_len, row_stride) of a row
+ *    and everything outside the arrays are never written.  side describes the source as dpt_collate's first four
+ *    arguments do; tok_off, row_first and n_rows are the plan's.  position_ids, segment_ids and labels are nullable.
+ *
+ * DPT_E_ARG, before any device work (also with n_str == 0): a null required pointer (sizes: off, opts, lengths; plan:
+ * tok_off, n_rows, and ws when n_str > 0; write: side, side->ids, side->off, tok_off, row_first, n_rows, opts,
+ * input_ids); row_len 0, < n_special or > 2^31; row_stride non-zero and < row_len; unknown flags or
+ * DPT_COLLATE_PAD_LEFT; n_str >= 2^31; row_cap >= 2^31.
+ * All three take DEVICE pointers on the current device, are stream-ordered on hip_stream, never synchronise, allocate
+ * nothing and need no dpt_ctx.  n_str == 0 launches nothing: the plan then still sets *n_rows = 0, row_first[0..row_cap]
+ * = 0 and row_fill = 0 (stream-ordered fills), the write leaves every row as it is.
+ * tok_off and row_first are the caller's data: whatever they hold, every store lands inside the arrays as sized
+ * above, an id is loaded only from inside its string's own token range, and every loop has a bound fixed before it
+ * starts; a tok_off that is no prefix sum of lengths <= row_len gives unspecified values, never a fault or a hang.
+ */
+#define DPT_PACK_MASK_FIRST 256     /* labels = ignore_id on position 0 of every sequence */
+#define DPT_PACK_NONE 0xFFFFFFFFu   /* str_row of a string that is not placed */
+typedef dpt_collate_opts dpt_pack_opts;   /* flags: DPT_COLLATE_BOS, _EOS, _TRUNC_LEFT, _I64 and DPT_PACK_MASK_FIRST */
+int dpt_pack_sizes(const uint64_t *off, const uint64_t *counts, const int32_t *status, uint64_t n_str,
+                   const dpt_pack_opts *opts, uint32_t *lengths, void *hip_stream);
+int dpt_pack_plan_workspace(uint64_t n_str, uint64_t *bytes);
+int dpt_pack_plan(const uint64_t *tok_off, uint64_t n_str, uint32_t row_len, uint64_t row_cap, uint32_t *str_row,
+                  uint32_t *str_col, uint32_t *row_first, uint32_t *row_fill, uint64_t *n_rows, void *ws,
+                  uint64_t ws_bytes, void *hip_stream);
+int dpt_pack_write(const dpt_collate_side *side, uint64_t n_str, const uint64_t *tok_off, const uint32_t *row_first,
+                   const uint64_t *n_rows, uint64_t row_cap, const dpt_pack_opts *opts, void *input_ids,
+                   void *position_ids, void *segment_ids, void *labels, void *hip_stream);
+/* TEST-ONLY, needs no device: the strings one block of the plan takes (B) and the plan's grid cap (more than
+ * grid_cap * B strings: the blocks stride), so tests take their edge sizes from the library. */
+int dpt_debug_pack_geometry(uint32_t *strings_per_block, uint32_t *grid_cap);
+
+/*
  * Llama-mode pre-tokenization on the device: text in, DPT_MODE_PRESPLIT input (text + cut mask) out -- what the
  * reference's default pre-tokenizer, pretokenize_with_llama + merge_tokens (packages/tokenizer_utils.py:7-31,
  * selected at :52, main_analyze_s2orc.py:74, :256), keeps of SentencePiece's output: the concatenation of the pieces
